@@ -11,7 +11,9 @@ Random-init weights of the reference architectures, synthetic data (no network /
 N > 1: one process per GPU (torch.distributed nccl = RCCL), per-rank batch 8 (weak scaling), gradient
 all-reduce of the trainable parameters, max-over-ranks timing.
 
-The ONE JSON line rank 0 prints carries, besides the headline `value` (inputs resident in HBM, as the contract says):
+A plain run sets up, warms up, times --steps steps (no event records inside them), writes --dump-outputs if asked and prints
+ONE JSON line: the headline `value` (inputs resident in HBM, as the contract says) and `ms_per_step`.  With --full that line
+also carries (the --no-* options drop parts of it):
   roofline      dominant kernel family (MFMA implicit-GEMM conv), live HIP-event durations inside the timed region;
                 `traffic` = HBM bytes per launch from two rocprofv3 PMC passes THIS invocation drives (N=1; --no-pmc skips)
   stages        per-stage rooflines measured live after the timed region (HIP events, N=1): voxelizer (uniform and
@@ -56,6 +58,14 @@ DOMINANT_ONE = re.compile(r"conv3x3_lstm_w128_kernel")          # THE dominant k
 DOMINANT = re.compile(r"conv3x3_lstm_w128_kernel|conv3x3_halo_kernel<[01]>|conv3x3_halo_group_kernel<1>|conv3x3_halo256_group_kernel|conv5x5s2_halo(_group)?_kernel|"
                       r"conv_fwd_dma_kernel<(128|64), 128, [24], (true|false), [01](, 256)?>|conv_fwd_dma_kernel<256, 256, 2, true, 0(, 512)?>|"
                       r"conv_fwd_dma32_kernel<128, true, 0, 3")
+
+
+T_START = time.perf_counter()
+
+
+def _progress(what):
+    """--full: one line per block on stderr (stdout carries only the JSON line)."""
+    print(f"# bench.py --full: {what} at {time.perf_counter() - T_START:.0f} s", file=sys.stderr, flush=True)
 
 
 def make_events(rank, structured=False):
@@ -132,8 +142,9 @@ def cpu_baseline(sample_events, rectify_map):
     from concurrent.futures import ThreadPoolExecutor
     from oracle import events as oe
     from oracle.step import OracleStep
-    ncores = os.cpu_count() or 1
-    nthr = min(ncores, 64)           # more torch threads oversubscribe: the same step took 345 s with 256 threads on a 256-core host
+    # the CPUs this process may use (OMP_NUM_THREADS / affinity), not the host's count: more torch threads oversubscribe (the
+    # same step took 345 s with 256 threads on a 256-core host)
+    nthr = min(torch.get_num_threads(), len(os.sched_getaffinity(0)), 64)
     torch.set_num_threads(nthr)
     torch.manual_seed(1205)
     x, y, t, p = sample_events
@@ -289,6 +300,7 @@ class Workload:
             self.voxels.append(torch.empty_like(self.voxels[0]))
         vox = self.voxels[i & 1]             # step i + 1 is voxelized while step i's front may still read its tensor
         self.voxelize(self.ev, vox)
+        self.last_voxels = vox
         batch = self.batch_of(vox)
         return batch, self.step.front(batch)
 
@@ -302,6 +314,7 @@ class Workload:
         self.reducer()
         for opt in self.step.optimizers_dict.values():
             opt.step()
+        self.last_losses = losses
         return t_loss
 
     def train(self, voxels):
@@ -309,6 +322,7 @@ class Workload:
 
     def one_step(self):
         self.voxelize(self.ev, self.voxels[0])
+        self.last_voxels = self.voxels[0]
         return self.train(self.voxels[0])
 
     def run(self, n):
@@ -396,6 +410,40 @@ class Workload:
             dist.all_reduce(tt, op=dist.ReduceOp.MAX)
             dt = float(tt.item())
         return dt
+
+
+# ------------------------------------------------------------------------------------------------ --dump-outputs
+DUMP_ELEMS = 1 << 22            # float32 elements per dumped array at most (16 MB): a fixed, seeded sample of anything larger
+DUMP_BYTES = 64_000_000         # all dumped arrays together: 64 MB
+
+
+def _sample(t, seed):
+    """t flattened to float32 on the host; above DUMP_ELEMS elements the values at a fixed set of positions (drawn from
+    `seed`, sorted, duplicates dropped), the same on every run and every build."""
+    flat = t.detach().reshape(-1)
+    if flat.numel() > DUMP_ELEMS:
+        idx = np.unique(np.random.default_rng(seed).integers(0, flat.numel(), DUMP_ELEMS))
+        flat = flat[torch.from_numpy(idx).to(flat.device)]
+    return flat.float().cpu().numpy()
+
+
+def dump_outputs(wl, loss, out_dir):
+    """What the last timed step computed, as the step's caller has it: the total loss and each loss term, the updated state
+    (parameters + running statistics, state_dict order, one array per model the optimisers update) and the voxel grid the
+    step trained on."""
+    arrays = {"loss": np.asarray(loss, dtype=np.float32)}
+    for k, v in wl.last_losses.items():
+        arrays["loss_" + k] = v.detach().float().cpu().numpy()
+    for seed, (name, m) in enumerate(wl.step.models_dict.items()):
+        if any(p.requires_grad for p in m.parameters()):
+            state = [v.reshape(-1).float() for v in m.state_dict().values() if v.is_floating_point()]
+            arrays["state_" + name] = _sample(torch.cat(state), 1000 + seed)
+    arrays["voxels"] = _sample(wl.last_voxels, 1205)
+    total = sum(v.nbytes for v in arrays.values())
+    assert total <= DUMP_BYTES, f"--dump-outputs: {total} bytes > {DUMP_BYTES}"
+    os.makedirs(out_dir, exist_ok=True)
+    for k, v in arrays.items():
+        np.save(os.path.join(out_dir, k + ".npy"), v)
 
 
 # ------------------------------------------------------------------------------------------------ per-stage rooflines
@@ -515,11 +563,18 @@ def main():
                     "encoder side streams, no cross-step pipelining (A/B; same results)")
     ap.add_argument("--no-pipeline", action="store_true", help="frozen half of step i+1 NOT enqueued ahead of the trainable half of step i "
                     "(the teacher / encoder side streams inside a step stay; A/B; same results)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-pmc", action="store_true", help="skip the two rocprofv3 PMC child passes (roofline.traffic = null)")
-    ap.add_argument("--no-extras", action="store_true", help="headline + roofline only: no stages / configs / ingest blocks")
+    ap.add_argument("--full", action="store_true", help="everything beside the headline as well: roofline (HIP events around the conv "
+                    "launches of the timed region + a one-stream serial region), PMC traffic, stages, configs, ingest, train loop, "
+                    "CPU baseline.  Without it a run sets up, warms up, times --steps steps and prints the headline")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps write what the last one computed as DIR/<name>.npy "
+                    "(float32; seeded samples of the large arrays)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: no cpu_baseline block")
+    ap.add_argument("--no-pmc", action="store_true", help="with --full: skip the two rocprofv3 PMC child passes (roofline.traffic = null)")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: headline + roofline only: no stages / configs / ingest blocks")
     ap.add_argument("--child", action="store_true", help=argparse.SUPPRESS)        # profiled child of pmc_traffic(): steps only
     a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
     if a.no_s2_group:
         from openess_amd.e2vid.model.unet import UNetRecurrent
         UNetRecurrent.group_s2 = False
@@ -551,19 +606,23 @@ def main():
     # is why the serial region reads ~3 % under an uninstrumented one-stream run).  OESS_BENCH_EVENTS=dominant brackets only the dominant
     # kernel's 22 launches in the timed region (A/B: 221.3 -> 221.9 event-frames/s, the other streams hide most of it); the default
     # keeps all 115 so that `timed_region` carries the family figure as well.
+    # A plain run (no --full) times the steps without any event records: the headline alone.
     lstm_only_timed = bool(getattr(wl.step, "overlap_teacher", False)) and os.environ.get("OESS_BENCH_EVENTS", "all") == "dominant" and \
         not os.environ.get("OESS_CONV_BREAKDOWN")
-    dt, loss, conv_stats = wl.timed(a.steps, a.warmup, conv_timing="lstm" if lstm_only_timed else True)
+    dt, loss, conv_stats = wl.timed(a.steps, a.warmup, conv_timing=("lstm" if lstm_only_timed else True) if a.full else False)
+    if rank == 0 and a.dump_outputs:
+        dump_outputs(wl, loss, a.dump_outputs)
     if rank == 0 and os.environ.get("OESS_CONV_BREAKDOWN") and conv_stats:
         for k, (n, tm, fl) in sorted(conv_stats["by_shape"].items(), key=lambda kv: -kv[1][1]):
             print(f"# conv HxWxCin->Cout k,s,d {k}: {n // a.steps:3d}/step {tm / a.steps:7.3f} ms/step {fl / tm / 1e9:7.1f} TF/s", file=sys.stderr)
-    extras = not a.no_extras
+    extras = a.full and not a.no_extras
     out = None
     # The product step runs the frozen teacher on a second HIP stream under the recurrent encoder, so the per-launch durations of
     # the timed region include the time two kernels share the CUs.  A short second region on ONE stream (all ranks; same process,
     # same box) gives the launches' own durations: `roofline.serial_reference`.
     serial = None
-    if getattr(wl.step, "overlap_teacher", False):
+    if a.full and getattr(wl.step, "overlap_teacher", False):
+        _progress("serial region")
         n_ser = max(10, a.steps // 5)
         keep = wl.pipeline
         wl.step.overlap_teacher, wl.pipeline = False, False
@@ -655,6 +714,7 @@ def main():
                            "buckets": len(wl.reducer.buckets), "bucket_bytes": wl.reducer.exposed_bytes()}
     # ---- ingest-inclusive rate of the same workload (all ranks take part: the reducer is a collective)
     if extras:
+        _progress("ingest")
         n_in = max(10, a.steps // 4)
         dt_in = wl.timed_with_ingest(n_in, 2)
         if rank == 0:
@@ -663,6 +723,7 @@ def main():
                              "note": "raw event columns start in PINNED HOST buffers every step; H2D + voxelizer of batch i+1 on a side "
                                      "HIP stream under step i (north_star 'straight from pinned host event buffers'); never `value`"}
         if world == 1:
+            _progress("stages")
             out["stages"] = stage_rooflines(wl, rank, device)
             if rank == 0 and out.get("roofline") is not None:
                 # the stage fractions north_star sets targets for, inside the `roofline` object the driver's record keeps
@@ -679,12 +740,13 @@ def main():
         torch.cuda.empty_cache()
         cfgs = {}
         for name in ("frame2voxel_full", "frame2recon_full", "frame2voxel_pixel_distill+wavefront"):
+            _progress("configs: " + name)
             n2 = max(10, a.steps // 4)
             if world == 1:
                 # each configuration in its OWN process, as a user would run it: in this process, behind the headline / ingest /
                 # stage blocks, frame2recon_full read 294 event-frames/s where the same command alone reads 327 (allocator state)
                 cmd = [sys.executable, os.path.abspath(__file__), "--workload", name.split("+")[0], "--steps", str(n2), "--warmup", "3",
-                       "--no-extras", "--no-pmc", "--no-cpu-baseline"] + (["--wavefront"] if name.endswith("+wavefront") else [])
+                       "--full", "--no-extras", "--no-pmc", "--no-cpu-baseline"] + (["--wavefront"] if name.endswith("+wavefront") else [])
                 try:
                     r = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
                     line = json.loads([l for l in r.stdout.split("\n") if l.startswith("{")][-1])
@@ -708,6 +770,7 @@ def main():
             out["configs"] = cfgs
     if rank == 0 and extras and world == 1 and a.workload == "frame2voxel_pixel_distill":
         # the PRODUCT loop (train.py dispatch, DataLoader workers, pin thread, side-stream ingest) beside the headline
+        _progress("train loop")
         try:
             torch.cuda.empty_cache()
             sys.path.insert(0, os.path.join(ROOT, "tools"))
@@ -723,6 +786,7 @@ def main():
         # 8-GPU dry run of the host side: eight 2-worker loader pools drained by one process on this box, every
         # batch copied to the device out of its pinned slot; to be read against 8 x the headline (tools/bench_host_pools.py).
         # In its own process: the pools fork 16 workers, which must not inherit this process's 20 GB of device-side state.
+        _progress("eight loader pools")
         try:
             r = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "bench_host_pools.py"), "--json"], capture_output=True, text=True, timeout=420)
             pools = json.loads([l for l in r.stdout.split("\n") if l.startswith("{")][-1])
@@ -744,6 +808,7 @@ def main():
                 sys.path.insert(0, os.path.join(ROOT, "tools"))
             import bench_stage2
             for case in [c[0] for c in bench_stage2.CASES]:
+                _progress("configs: stage2:" + case)
                 r = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "bench_stage2.py"), "--only", case, "--steps",
                                     str(max(10, a.steps // 5))], capture_output=True, text=True, timeout=600)
                 lines = [l for l in r.stdout.split("\n") if l.startswith("{")]
@@ -754,8 +819,9 @@ def main():
         except Exception as e:      # never cost the headline
             out["configs"]["stage2_error"] = repr(e)[:300]
     if rank == 0:
-        if world == 1 and not a.no_pmc and out["roofline"] is not None:
+        if world == 1 and a.full and not a.no_pmc and out["roofline"] is not None:
             torch.cuda.empty_cache()
+            _progress("PMC traffic")
             tr, err = pmc_traffic()
             if tr is not None:
                 one = tr["dominant_kernel"] or tr["family"]
@@ -765,14 +831,17 @@ def main():
                                                                     "kernel's launches, `family` = all launches of its conv family")
             else:
                 out["roofline"]["traffic_error"] = err
-        if not a.no_cpu_baseline and world == 1:
+        if a.full and not a.no_cpu_baseline and world == 1:
             from openess_amd.datasets import _synth
+            _progress("CPU baseline")
             sample = _synth.dsec_raw_events(NWIN * N_PER, H_SENSOR, W_SENSOR, seed=1205)
             try:
                 out["cpu_baseline"] = cpu_baseline(sample, _synth.rectify_map(H_SENSOR, W_SENSOR))
                 out["parity_full_size"] = out["cpu_baseline"].pop("parity_full_size", None)
             except Exception as e:      # the baseline must never cost the GPU number
                 out["cpu_baseline"] = {"error": repr(e)}
+        if a.full:
+            _progress("done")
         print(json.dumps(out))
     if launched:
         dist.destroy_process_group()

@@ -1,5 +1,6 @@
 """Plugin surface: Settings attribute names, every reference YAML loads (when the reference tree is
-present), trainer dispatch order, checkpoint format, DDD17 on-disk reader."""
+present), YAML variants of every kind that tree holds load and dispatch, trainer dispatch order, checkpoint format,
+DDD17 on-disk reader."""
 import glob
 import os
 
@@ -44,6 +45,60 @@ def test_every_reference_yaml_loads_and_dispatches(monkeypatch):
             # quirk reproduced: top-level if_linear_probing is ignored -> these files dispatch to OpenESSModel
             assert kind in ('openess', 'ft', 'pre', 'sup')
     assert {'pre', 'ft'} <= kinds
+
+
+def test_yaml_variants_load_and_dispatch(tmp_path, monkeypatch):
+    """(v) of SURVEY.md section 4: YAML round trip of the kinds of file the reference's config/ tree holds (pre-training,
+    fine-tuning, linear probing with the flag at top level, supervised only, the joint stage; DSEC and DDD17 blocks; every
+    config_option; dataset directories that do not exist here), written as variants of this suite's own configs: runs
+    everywhere, beside the round trip of the reference's own files above."""
+    import yaml
+    from openess_amd.config.settings import Settings
+    monkeypatch.setenv("OPENESS_ALLOW_MISSING_DATA", "1")
+    base = {n: yaml.safe_load(open(os.path.join(CFG, f"{n}_dsec_synthetic.yaml"))) for n in ("pretrain", "finetune", "openess")}
+    ddd17 = {'name_b': 'DDD17_events',
+             'DDD17_events': dict(base['pretrain']['dataset']['DSEC_events'], dataset_path='data/DDD17', shape=[200, 346],
+                                  split_train='train', nr_events_data=20, nr_events_window=32000)}
+
+    def variant(name, src, clip=None, dataset=None, top=None, classes=None):
+        cfg = yaml.safe_load(yaml.safe_dump(base[src]))
+        cfg['dataset'][cfg['dataset']['name_b']]['dataset_path'] = 'data/DSEC'        # missing here: synthetic provider
+        cfg['clip'].update(clip or {})
+        cfg['dataset'] = dataset or cfg['dataset']
+        cfg['task']['semseg_num_classes'] = classes or cfg['task']['semseg_num_classes']
+        cfg.update(top or {})
+        d = tmp_path / name.split('/')[0]
+        d.mkdir(exist_ok=True)
+        (tmp_path / name).write_text(yaml.safe_dump(cfg))
+        return str(tmp_path / name)
+
+    cases = [(variant('pretrain/frame2voxel.yaml', 'pretrain'), 'pre'),
+             (variant('pretrain/frame2recon.yaml', 'pretrain', clip={'config_option': 'frame2recon'}), 'pre'),
+             (variant('pretrain/recon2voxel_ddd17.yaml', 'pretrain', clip={'config_option': 'recon2voxel'}, dataset=ddd17, classes=6), 'pre'),
+             (variant('finetunes/frame2recon.yaml', 'finetune'), 'ft'),
+             (variant('finetunes/frame2recon_ddd17.yaml', 'finetune', dataset=ddd17, classes=6), 'ft'),
+             # quirk reproduced: top-level if_linear_probing is ignored -> the file dispatches on its clip flags (pre-training
+             # when clip.if_pretraining is set, otherwise OpenESSModel)
+             (variant('linear_probe/frame2voxel.yaml', 'pretrain', top={'if_linear_probing': True}), 'pre'),
+             (variant('linear_probe/frame2recon.yaml', 'openess', top={'if_linear_probing': True}), 'openess'),
+             (variant('linear_probe_clip_flag/frame2recon.yaml', 'openess', clip={'if_linear_probing': True}), 'lp'),
+             (variant('supervised/frame2recon.yaml', 'openess', clip={'if_supervised_only': True}), 'sup'),
+             (variant('openess/frame2recon.yaml', 'openess'), 'openess')]
+    kinds = set()
+    for fpath, want in cases:
+        s = Settings(fpath, generate_log=False)
+        assert s.config_option in ('recon2voxel', 'frame2voxel', 'frame2recon')
+        assert s.synthetic_data and s.dataset_path_b in ('data/DSEC', 'data/DDD17')
+        kind = ('sup' if s.if_supervised_only else 'pre' if getattr(s, 'if_pretraining', False)
+                else 'ft' if getattr(s, 'if_finetuning', False) else 'lp' if s.if_linear_probing else 'openess')
+        assert kind == want, fpath
+        kinds.add(kind)
+        if s.dataset_name_b == 'DDD17_events':
+            assert s.semseg_num_classes == 6 and s.semseg_color_map.shape == (6, 3) and s.split_train_b == 'train'
+            assert s.img_size_b == [200, 346] and s.semseg_label_train_b
+        if '/linear_probe/' in fpath:
+            assert s.if_linear_probing is False
+    assert kinds == {'pre', 'ft', 'lp', 'sup', 'openess'}
 
 
 def test_reference_trainer_module_paths_exist():

@@ -10,7 +10,7 @@ rm -rf $O; mkdir -p $O
 timeout 1200 python -m pytest tests -m gpu -q 2>&1 | tail -4 > $O/pytest_gpu.txt
 timeout 1200 python -m pytest tests -m gpu -q 2>&1 | tail -4 > $O/pytest_gpu_run2.txt
 timeout 300 python -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" > $O/smoke.txt 2>&1
-timeout 1200 python bench.py > $O/bench.txt 2>&1
+timeout 1200 python bench.py --full > $O/bench.txt 2>&1
 # same box, same code, recurrent encoder in the plain order (one ConvLSTM launch per level and sub-window): the A/B of the skewed schedule
 # (alternating short runs: the 100-step line above and a 30-step run are not the same thermal state)
 for i in 1 2; do
