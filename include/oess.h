@@ -35,7 +35,7 @@ typedef void* oess_stream_t; /* hipStream_t */
 /* Library / device identification.  OESS_ABI_VERSION is bumped whenever a signature of this header changes or an entry point
  * is removed; oess_abi_version() returns the value the library was built with and the ctypes binding (openess_amd/_lib.py,
  * ABI_VERSION) refuses a library whose value differs. */
-#define OESS_ABI_VERSION 10
+#define OESS_ABI_VERSION 11
 int oess_abi_version(void);
 const char* oess_build_info(void);           /* "liboess <ver> gfx950 hipcc <ver>" */
 const char* oess_strerror(int code);
@@ -545,6 +545,31 @@ int oess_aspp_pool_fwd_f32(const float* pooled, float in_scale, const float* w, 
 int oess_aspp_pool_bwd_f32(const float* grad_z, const float* pooled, float in_scale, const float* w, const float* gamma, const float* y_pre,
                            const float* stat, const float* z, int B, int Cin, int Cout, float* dy_scratch, float* grad_w,
                            float* grad_gamma, float* grad_beta, void* grad_pooled_bf16, oess_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
+ * E2VID post-processing: the reference's PostProcessor.process (e2vid/image_reconstructor.py:126-140) on the reconstructed frame,
+ * UnsharpMaskFilter (e2vid/utils/inference_utils.py:234-252) then IntensityRescaler (:90-129), fused (bilateral filter: no).
+ *   img: fp32 [N x 1 x H x W] VIEW, last dimension contiguous, image stride img_stride and row stride row_stride in elements (a crop
+ *   window of a larger map is fine: the blur's zero padding sits at the edge of the view).  weights_host: the 25 fp32 weights of
+ *   gkern(5, sigma), row-major, read on the host; may be NULL when amount <= 0 (the filter is then skipped, as in the reference).
+ *   out_u8 [N x H x W]: trunc(clamp(255 (s - Imin) / (Imax - Imin), 0, 255)); out_f32 (nullable) [N x 1 x H x W]: out_u8 / 255.
+ * Fixed bounds: ONE launch; imax > imin required.
+ * Auto-HDR: TWO launches, no host synchronisation: the whole-tensor min / max of the sharpened image (all N images together),
+ *   clipped to [0, 0.45] / [0.55, 1], enter a window of up to filter_size + 1 entries whose float64 medians are Imin / Imax.
+ *   state: caller-owned device buffer of oess_e2vid_postproc_state_bytes(filter_size) bytes, 8-byte aligned, zero-filled for a
+ *   fresh window, then passed unchanged to every call of the sequence (same filter_size); it is stream-ordered like any output.
+ *   Layout: 48-byte header, then ring_lo[filter_size + 1], ring_hi[filter_size + 1] (float64); the header holds the current
+ *   medians as two float64 at byte offset 32 (Imin, Imax).
+ * Bit-repeatable (no floating-point atomics).  0 <= filter_size <= OESS_E2VID_POSTPROC_MAX_FILTER.
+ * ------------------------------------------------------------------------------------------ */
+#define OESS_E2VID_POSTPROC_MAX_FILTER 255
+size_t oess_e2vid_postproc_state_bytes(int filter_size);      /* 0 for a filter_size out of range */
+int oess_e2vid_postprocess_f32(const float* img, long long img_stride, long long row_stride, int N, int H, int W,
+                               const float* weights_host, double amount, double imin, double imax, uint8_t* out_u8, float* out_f32,
+                               oess_stream_t stream);
+int oess_e2vid_postprocess_auto_hdr_f32(const float* img, long long img_stride, long long row_stride, int N, int H, int W,
+                                        const float* weights_host, double amount, int filter_size, void* state, size_t state_bytes,
+                                        uint8_t* out_u8, float* out_f32, oess_stream_t stream);
 
 #ifdef __cplusplus
 }

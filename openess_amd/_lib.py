@@ -10,7 +10,7 @@ import os
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("OESS_LIB_PATH") or os.path.join(_HERE, "liboess.so")      # override: A/B builds of the same ABI
 
-ABI_VERSION = 10         # == OESS_ABI_VERSION of include/oess.h (tests/test_abi.py keeps the two equal)
+ABI_VERSION = 11         # == OESS_ABI_VERSION of include/oess.h (tests/test_abi.py keeps the two equal)
 
 c_i64 = ctypes.c_int64
 c_ll = ctypes.c_longlong
@@ -134,6 +134,10 @@ SIGNATURES = {
     "oess_dropout_nhwc_bf16": (c_int, [c_vp, c_ll, c_vp, c_ll, c_ll, c_int, c_f, c_u64, c_u64, c_vp]),
     "oess_aspp_pool_fwd_f32": (c_int, [c_vp, c_f, c_vp, c_vp, c_vp, c_vp, c_vp, c_f, c_f, c_int, c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "oess_aspp_pool_bwd_f32": (c_int, [c_vp, c_vp, c_f, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "oess_e2vid_postproc_state_bytes": (c_sz, [c_int]),
+    "oess_e2vid_postprocess_f32": (c_int, [c_vp, c_ll, c_ll, c_int, c_int, c_int, c_vp, c_d, c_d, c_d, c_vp, c_vp, c_vp]),
+    "oess_e2vid_postprocess_auto_hdr_f32": (c_int, [c_vp, c_ll, c_ll, c_int, c_int, c_int, c_vp, c_d, c_int, c_vp, c_sz, c_vp, c_vp,
+                                                    c_vp]),
 }
 
 _lib = None

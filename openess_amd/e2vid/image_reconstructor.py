@@ -1,10 +1,12 @@
 """Mirror of e2vid/image_reconstructor.py:ImageReconstructor (:18-123) for the training path:
-preprocess -> pad -> recurrent model step -> keep state.  No CudaTimer syncs in the hot loop."""
+preprocess -> pad -> recurrent model step -> keep state.  No CudaTimer syncs in the hot loop.
+PostProcessor (:126-140) of the offline reconstruction: unsharp mask + intensity rescaling in one HIP pass."""
 from types import SimpleNamespace
 
 import torch
 
-from .utils.inference_utils import CropParameters, EventPreprocessor
+from .. import hip
+from .utils.inference_utils import CropParameters, EventPreprocessor, gkern
 
 
 class ImageReconstructor:
@@ -60,3 +62,48 @@ class ImageReconstructor:
             img, states, latent = self.model(x, self.last_states_for_each_channel['grayscale'], reconstruct=reconstruct, **kw)
             self.last_states_for_each_channel['grayscale'] = None if self.no_recurrent else states
         return img, states, latent
+
+
+class PostProcessor:
+    """e2vid/image_reconstructor.py:126-140: UnsharpMaskFilter -> IntensityRescaler (-> ImageFilter) on the reconstructed frame,
+    fused into oess_e2vid_postprocess_* (one launch with fixed Imin / Imax, two with auto-HDR, no host synchronisation).  Options
+    are read with the reference's defaults (e2vid/options/inference_options.py:31-46).  The auto-HDR window lives on the device,
+    one per PostProcessor, and persists across calls.  Not implemented: the bilateral filter (cv2.bilateralFilter) and colour."""
+
+    def __init__(self, device, options=None):
+        options = options if options is not None else SimpleNamespace()
+        self.device = torch.device(device)
+        if float(getattr(options, 'bilateral_filter_sigma', 0.0)) > 0:
+            raise NotImplementedError("PostProcessor: the bilateral filter (cv2.bilateralFilter) is not implemented")
+        if getattr(options, 'color', False):
+            raise NotImplementedError("PostProcessor: colour reconstruction is not implemented")
+        self.unsharp_mask_amount = float(getattr(options, 'unsharp_mask_amount', 0.3))
+        self.unsharp_mask_sigma = float(getattr(options, 'unsharp_mask_sigma', 1.0))
+        self.gaussian_kernel = gkern(5, self.unsharp_mask_sigma)            # fp32 [5, 5], kept on the host: the launch reads it there
+        self.auto_hdr = bool(getattr(options, 'auto_hdr', False))
+        self.auto_hdr_median_filter_size = int(getattr(options, 'auto_hdr_median_filter_size', 10))
+        self.Imin = float(getattr(options, 'Imin', 0.0))
+        self.Imax = float(getattr(options, 'Imax', 1.0))
+        if self.auto_hdr:
+            self.hdr_state = hip.E2VIDHdrState(self.auto_hdr_median_filter_size, self.device)
+        else:
+            self.hdr_state = None
+            if not self.Imax > self.Imin:
+                raise ValueError(f"PostProcessor: Imax ({self.Imax}) must exceed Imin ({self.Imin})")
+
+    def _run(self, frame, want_f32):
+        kw = {'hdr_state': self.hdr_state} if self.auto_hdr else {'bounds': (self.Imin, self.Imax)}
+        with torch.no_grad():
+            return hip.e2vid_postprocess(frame, self.gaussian_kernel, self.unsharp_mask_amount, want_f32=want_f32, **kw)
+
+    def process(self, new_predicted_frame):
+        """fp32 [N, 1, H, W] on the device -> fp32 [N, 1, H, W] = uint8 / 255 (the reference contract)."""
+        return self._run(new_predicted_frame, True)[1]
+
+    def process_u8(self, new_predicted_frame):
+        """Same, returning the uint8 [N, H, W] grey levels that the PNG writer stores."""
+        return self._run(new_predicted_frame, False)[0]
+
+    def current_bounds(self):
+        """(Imin, Imax) used by the last call (auto-HDR: the medians on the device, read back -- this synchronises)."""
+        return self.hdr_state.bounds() if self.auto_hdr else (self.Imin, self.Imax)

@@ -6,6 +6,10 @@ executes; `-o/--output_folder` + `--dataset_name` follow e2vid/options/inference
 
     python -m openess_amd.e2vid.run_reconstruction -c E2VID_lightweight.pth.tar -i events.txt -o out/
 
+`--postprocess` runs the reference's PostProcessor (unsharp mask + intensity rescaling, optionally auto-HDR; image_reconstructor.py
+:126-140) on each cropped frame and writes its bytes; its tuning flags (`--unsharp_mask_amount`, `--Imin`, `--auto_hdr`, ...) keep
+the reference's defaults and are refused without it.  Without `--postprocess` a frame is round(clamp(img, 0, 1) * 255).
+
 Checkpoint format: the reference's (`{'arch': 'E2VIDRecurrent', 'model' | 'config.model': {...}, 'state_dict': ...}`,
 e2vid/utils/loading_utils.py:5-16); `-c random` builds E2VID_lightweight with seeded random weights (no checkpoint
 ships with either repository)."""
@@ -15,7 +19,9 @@ import os
 import numpy as np
 import torch
 
-from .image_reconstructor import ImageReconstructor
+from types import SimpleNamespace
+
+from .image_reconstructor import ImageReconstructor, PostProcessor
 from .model.model import E2VID_LIGHTWEIGHT_CONFIG, E2VIDRecurrent
 from .utils.event_readers import FixedDurationEventReader, FixedSizeEventReader
 from .utils.inference_utils import events_to_voxel_grid_pytorch
@@ -35,14 +41,17 @@ def load_model(path_to_model):
 
 
 def reconstruct(path_to_events, model, output_folder=None, window_size=None, fixed_duration=False, window_duration=33.33,
-                num_events_per_pixel=0.35, skipevents=0, suboffset=0, device='cuda', max_windows=None):
-    """Returns the list of reconstructed images (uint8 [H, W]); writes frame_%010d.png + timestamps.txt when a folder is given."""
+                num_events_per_pixel=0.35, skipevents=0, suboffset=0, device='cuda', max_windows=None, postprocessor=None,
+                options=None):
+    """Returns the list of reconstructed images (uint8 [H, W]); writes frame_%010d.png + timestamps.txt when a folder is given.
+    postprocessor: a PostProcessor applied to each cropped frame (its bytes are the image); None = round(clamp(img, 0, 1) * 255).
+    options: passed to ImageReconstructor (no_normalize, no_recurrent)."""
     with open(path_to_events) as f:
         width, height = (int(v) for v in f.readline().split())
     print('Sensor size: {} x {}'.format(width, height))
     device = torch.device(device)
     model = model.to(device).eval()
-    rec = ImageReconstructor(model, height, width, model.num_bins, device)
+    rec = ImageReconstructor(model, height, width, model.num_bins, device, options)
     N = window_size
     if not fixed_duration and N is None:
         N = int(width * height * num_events_per_pixel)
@@ -60,7 +69,10 @@ def reconstruct(path_to_events, model, output_folder=None, window_size=None, fix
         img, _, _ = rec.update_reconstruction(grid.unsqueeze(0), start_index + window.shape[0], window[-1, 0], reconstruct=True)
         if rec.crop.needs_pad:
             img = img[:, :, rec.crop.iy0:rec.crop.iy1, rec.crop.ix0:rec.crop.ix1]
-        frame = (img[0, 0].clamp(0, 1) * 255.0).round().to(torch.uint8).cpu().numpy()
+        if postprocessor is None:
+            frame = (img[0, 0].clamp(0, 1) * 255.0).round().to(torch.uint8).cpu().numpy()
+        else:
+            frame = postprocessor.process_u8(img[:, :1])[0].cpu().numpy()       # the crop view goes in as it is (no copy)
         frames.append(frame)
         stamps.append(float(window[-1, 0]))
         if output_folder:
@@ -72,7 +84,13 @@ def reconstruct(path_to_events, model, output_folder=None, window_size=None, fix
     return frames
 
 
-def main():
+# (flag, reference default, type) of the PostProcessor options (e2vid/options/inference_options.py:31-46)
+POSTPROCESS_FLAGS = (('unsharp_mask_amount', 0.3, float), ('unsharp_mask_sigma', 1.0, float), ('Imin', 0.0, float),
+                     ('Imax', 1.0, float), ('auto_hdr', False, bool), ('auto_hdr_median_filter_size', 10, int),
+                     ('bilateral_filter_sigma', 0.0, float))
+
+
+def main(argv=None):
     p = argparse.ArgumentParser(description='Evaluating a trained network')
     p.add_argument('-c', '--path_to_model', required=True, type=str)
     p.add_argument('-i', '--input_file', required=True, type=str)
@@ -86,10 +104,25 @@ def main():
     p.add_argument('--compute_voxel_grid_on_cpu', action='store_true', help='accepted for compatibility; the grid is always built on the GPU')
     p.add_argument('-o', '--output_folder', default=None, type=str)
     p.add_argument('--dataset_name', default='reconstruction', type=str)
-    a = p.parse_args()
+    p.add_argument('--no-normalize', dest='no_normalize', action='store_true')
+    p.add_argument('--no-recurrent', dest='no_recurrent', action='store_true')
+    g = p.add_argument_group('post-processing (e2vid/options/inference_options.py:31-46; only with --postprocess)')
+    g.add_argument('--postprocess', action='store_true', help="run the reference's PostProcessor (unsharp mask + intensity rescaling)")
+    for name, default, typ in POSTPROCESS_FLAGS:
+        if typ is bool:
+            g.add_argument('--' + name, dest=name, action='store_true', default=None)
+        else:
+            g.add_argument('--' + name, dest=name, default=None, type=typ, help='default: {}'.format(default))
+    a = p.parse_args(argv)
+    given = ['--' + name for name, _, _ in POSTPROCESS_FLAGS if getattr(a, name) is not None]
+    if given and not a.postprocess:
+        p.error('{} need(s) --postprocess'.format(', '.join(given)))
+    opts = SimpleNamespace(no_normalize=a.no_normalize, no_recurrent=a.no_recurrent,
+                           **{name: default if getattr(a, name) is None else getattr(a, name) for name, default, _ in POSTPROCESS_FLAGS})
+    post = PostProcessor(torch.device('cuda'), opts) if a.postprocess else None
     out = os.path.join(a.output_folder, a.dataset_name) if a.output_folder else None
-    reconstruct(a.input_file, load_model(a.path_to_model), out, a.window_size, a.fixed_duration, a.window_duration,
-                a.num_events_per_pixel, a.skipevents, a.suboffset)
+    return reconstruct(a.input_file, load_model(a.path_to_model), out, a.window_size, a.fixed_duration, a.window_duration,
+                       a.num_events_per_pixel, a.skipevents, a.suboffset, postprocessor=post, options=opts)
 
 
 if __name__ == "__main__":

@@ -1,10 +1,23 @@
 """Mirror of the pieces of e2vid/utils/inference_utils.py that are on the training path:
-EventPreprocessor (:49-87) and CropParameters (:284-311)."""
-from math import ceil, floor
+EventPreprocessor (:49-87) and CropParameters (:284-311); and gkern (:38-46) of the offline post-processing."""
+from math import ceil, erfc, floor, sqrt
 
 import torch
 
 from ... import hip
+
+
+def gkern(kernlen=5, nsig=1.0):
+    """e2vid/utils/inference_utils.py:38-46: 2-D Gaussian kernel (fp32 [kernlen x kernlen]) from the differences of the normal CDF
+    at kernlen + 1 points, computed in float64 and cast at the end.  scipy.stats.norm.cdf(x) is restated as
+    0.5 * erfc(-x / sqrt(2)) (the same function; the weights equal the reference's bit for bit, tests/test_e2vid_postprocess.py)."""
+    import numpy as np
+    interval = (2 * nsig + 1.) / kernlen
+    x = np.linspace(-nsig - interval / 2., nsig + interval / 2., kernlen + 1)
+    kern1d = np.diff(np.array([0.5 * erfc(-v / sqrt(2.0)) for v in x], dtype=np.float64))
+    kernel_raw = np.sqrt(np.outer(kern1d, kern1d))
+    kernel = kernel_raw / kernel_raw.sum()
+    return torch.from_numpy(kernel).float()
 
 
 def optimal_crop_size(max_size, max_subsample_factor):

@@ -1795,3 +1795,58 @@ def aspp_pool_branch(x, conv, bn):
                               0.0 if bn.momentum is None else float(bn.momentum), float(bn.eps))
     _engine.bump_bn_counter(bn)
     return y
+
+
+# ------------------------------------------------------------------------------------------ f4: E2VID post-processing
+class E2VIDHdrState:
+    """Device state of the auto-HDR bounds (IntensityRescaler's deque of (Imin, Imax) and its medians): a zero-filled buffer of
+    oess_e2vid_postproc_state_bytes(filter_size) bytes, updated on the device by every e2vid_postprocess call that gets it."""
+
+    def __init__(self, filter_size, device):
+        nbytes = _lib.load().oess_e2vid_postproc_state_bytes(int(filter_size))
+        if nbytes == 0:
+            raise ValueError(f"auto_hdr_median_filter_size must be in [0, 255], got {filter_size}")
+        self.filter_size = int(filter_size)
+        self.buf = torch.zeros(nbytes, dtype=torch.uint8, device=device)
+
+    def bounds(self):
+        """(Imin, Imax) after the last call, as float64 (the header's two doubles at byte 32); synchronises with the device."""
+        v = self.buf[32:48].view(torch.float64).cpu()
+        return float(v[0]), float(v[1])
+
+
+def e2vid_postprocess(img, weights, amount, bounds=None, hdr_state=None, out_u8=None, out_f32=None, want_f32=False):
+    """PostProcessor.process (unsharp mask + intensity rescaling) of fp32 [N, 1, H, W] `img` (any view whose last dimension is
+    contiguous) in one launch (fixed `bounds` = (Imin, Imax)) or two (auto-HDR: `hdr_state`, an E2VIDHdrState).  `weights` is the
+    5 x 5 fp32 gkern, read on the host (ignored when amount <= 0).  Returns (uint8 [N, H, W], fp32 [N, 1, H, W] = byte / 255 or
+    None); the float output is written when `out_f32` is given or `want_f32` is set."""
+    lib = _lib.load()
+    _need_gpu(img, out_u8, out_f32)
+    if img.dtype != torch.float32 or img.dim() != 4 or img.shape[1] != 1 or img.stride(3) != 1:
+        raise ValueError("e2vid_postprocess needs an fp32 [N, 1, H, W] tensor whose last dimension is contiguous")
+    if (bounds is None) == (hdr_state is None):
+        raise ValueError("e2vid_postprocess needs exactly one of bounds=(Imin, Imax) and hdr_state")
+    N, _, H, W = img.shape
+    w = None
+    if amount > 0:
+        w = torch.as_tensor(weights, dtype=torch.float32).reshape(-1)
+        if w.numel() != 25:
+            raise ValueError("e2vid_postprocess needs the 25 weights of a 5 x 5 kernel")
+        w = w.cpu().contiguous()
+    if out_u8 is None:
+        out_u8 = torch.empty((N, H, W), dtype=torch.uint8, device=img.device)
+    elif out_u8.dtype != torch.uint8 or tuple(out_u8.shape) != (N, H, W) or not out_u8.is_contiguous():
+        raise ValueError("out_u8 must be a contiguous uint8 [N, H, W] tensor")
+    if out_f32 is None and want_f32:
+        out_f32 = torch.empty((N, 1, H, W), dtype=torch.float32, device=img.device)
+    elif out_f32 is not None and (out_f32.dtype != torch.float32 or tuple(out_f32.shape) != (N, 1, H, W) or not out_f32.is_contiguous()):
+        raise ValueError("out_f32 must be a contiguous fp32 [N, 1, H, W] tensor")
+    geo = (_ptr(img), img.stride(0), img.stride(2) if H > 1 else W, N, H, W, _ptr(w), float(amount))
+    if hdr_state is None:
+        _lib.check(lib.oess_e2vid_postprocess_f32(*geo, float(bounds[0]), float(bounds[1]), _ptr(out_u8), _ptr(out_f32), _stream()),
+                   "oess_e2vid_postprocess_f32")
+    else:
+        _need_gpu(hdr_state.buf)
+        _lib.check(lib.oess_e2vid_postprocess_auto_hdr_f32(*geo, hdr_state.filter_size, _ptr(hdr_state.buf), hdr_state.buf.numel(),
+                                                           _ptr(out_u8), _ptr(out_f32), _stream()), "oess_e2vid_postprocess_auto_hdr_f32")
+    return out_u8, out_f32
