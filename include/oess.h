@@ -35,7 +35,7 @@ typedef void* oess_stream_t; /* hipStream_t */
 /* Library / device identification.  OESS_ABI_VERSION is bumped whenever a signature of this header changes or an entry point
  * is removed; oess_abi_version() returns the value the library was built with and the ctypes binding (openess_amd/_lib.py,
  * ABI_VERSION) refuses a library whose value differs. */
-#define OESS_ABI_VERSION 11
+#define OESS_ABI_VERSION 12
 int oess_abi_version(void);
 const char* oess_build_info(void);           /* "liboess <ver> gfx950 hipcc <ver>" */
 const char* oess_strerror(int code);
@@ -570,6 +570,47 @@ int oess_e2vid_postprocess_f32(const float* img, long long img_stride, long long
 int oess_e2vid_postprocess_auto_hdr_f32(const float* img, long long img_stride, long long row_stride, int N, int H, int W,
                                         const float* weights_host, double amount, int filter_size, void* state, size_t state_bytes,
                                         uint8_t* out_u8, float* out_f32, oess_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
+ * K14 fp32 E2VID inference (offline reconstruction, run_reconstruction --precision fp32): the layers of UNetRecurrent
+ * (e2vid/model/unet.py:118-170 of the reference) in fp32 on the f32-input MFMA (v_mfma_f32_32x32x2_f32): every output is a
+ * k-ordered fmaf chain, written once (no atomics, bit-repeatable).
+ *
+ * oess_f32_view_t: an fp32 tensor addressed as data[b sb + y sy + x sx + c sc] (strides in ELEMENTS): NHWC, NCHW and channel /
+ *   crop views of either.  An output view's data is written.  Dense, 16-byte aligned channels (sc == 1, the other strides
+ *   multiples of 4) and Cin % 16 == 0 take the vector operand loads; anything else is read element by element.
+ * oess_conv2d_fwd_f32: out = act(conv(in [+ in2]) + bias [+ residual]), act: 0 none, 1 ReLU, 2 sigmoid.  in2 (nullable, same
+ *   shape as in) is summed on load (skip_sum); upsample2x == 1 convolves the bilinear x2 (align_corners=False) of in [+ in2],
+ *   a (2H) x (2W) map (UpsampleConvLayer).  R x S <= 25 taps, stride 1 or 2, pad < R, S.  out: B x Ho x Wo x Cout,
+ *   Ho = (H' + 2 pad - R) / stride + 1 with H' = H or 2H.
+ *   w_packed: oess_conv2d_f32_packed_floats(Cout, Cin, R, S) floats, 16-byte aligned: [ceil16(R S Cin)][ceil32(Cout)], row
+ *   (r S + s) Cin + ci, column co = weight[co][ci][r][s] (Conv2d OIHW), zeros in the padding.  bias: fp32 [Cout] or NULL.
+ * oess_conv_transpose2d_fwd_f32: ConvTranspose2d(kernel 5, stride 2, padding 2, output_padding 1) of in [+ in2] -> out
+ *   B x 2H x 2W x Cout, + bias, act; four stride-1 phase sub-convolutions in ONE launch.  w_packed: four blocks (phase
+ *   p = 2 py + px, py / px = output row / column parity), each [ceil16(ny nx Cin)][ceil32(Cout)] with ny = 3 - py, nx = 3 - px,
+ *   row (ty nx + tx) Cin + ci, column co = weight[ci][co][py + 2 ty][px + 2 tx] (ConvTranspose2d's [Cin][Cout][5][5]).
+ * oess_convlstm_step_f32: ConvLSTM (e2vid/model/submodules.py:175-214): gates = conv(xh, w) + bias (R x S, "same" padding) into
+ *   ws ([B H W][4 C_hidden], i f o g), then c = sigmoid(f) c + sigmoid(i) tanh(g) (prev_cell_is_zero: sigmoid(i) tanh(g)) in
+ *   place in cell (fp32 [B][H][W][C_hidden], dense) and h = sigmoid(o) tanh(c) into the hidden view.  xh has Cin channels
+ *   (cat(x, h) = 2 C_hidden, or x alone with the x-half weights when the previous state is zero); w_packed as for
+ *   oess_conv2d_fwd_f32 with Cout = 4 C_hidden.  Two launches.
+ * ------------------------------------------------------------------------------------------ */
+typedef struct {
+    const float* data;
+    long long sb, sy, sx, sc;
+} oess_f32_view_t;
+size_t oess_conv2d_f32_packed_floats(int Cout, int Cin, int R, int S);       /* 0 for an impossible geometry */
+size_t oess_conv_transpose2d_f32_packed_floats(int Cout, int Cin);
+size_t oess_convlstm_f32_workspace_bytes(long long pixels, int C_hidden);
+int oess_conv2d_fwd_f32(const oess_f32_view_t* in, const oess_f32_view_t* in2, int B, int H, int W, int Cin, int upsample2x,
+                        const float* w_packed, const float* bias, int Cout, int R, int S, int stride, int pad, int act,
+                        const oess_f32_view_t* residual, const oess_f32_view_t* out, oess_stream_t stream);
+int oess_conv_transpose2d_fwd_f32(const oess_f32_view_t* in, const oess_f32_view_t* in2, int B, int H, int W, int Cin,
+                                  const float* w_packed, const float* bias, int Cout, int act, const oess_f32_view_t* out,
+                                  oess_stream_t stream);
+int oess_convlstm_step_f32(const oess_f32_view_t* xh, int B, int H, int W, int Cin, const float* w_packed, const float* bias,
+                           int C_hidden, int R, int S, int pad, int prev_cell_is_zero, float* cell, const oess_f32_view_t* hidden,
+                           void* ws, size_t ws_bytes, oess_stream_t stream);
 
 #ifdef __cplusplus
 }

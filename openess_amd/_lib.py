@@ -10,7 +10,7 @@ import os
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("OESS_LIB_PATH") or os.path.join(_HERE, "liboess.so")      # override: A/B builds of the same ABI
 
-ABI_VERSION = 11         # == OESS_ABI_VERSION of include/oess.h (tests/test_abi.py keeps the two equal)
+ABI_VERSION = 12         # == OESS_ABI_VERSION of include/oess.h (tests/test_abi.py keeps the two equal)
 
 c_i64 = ctypes.c_int64
 c_ll = ctypes.c_longlong
@@ -32,6 +32,14 @@ class ConvS2Desc(ctypes.Structure):
     """oess_conv_s2_desc_t (include/oess.h): one problem of oess_conv5x5s2_group_bf16."""
     _fields_ = [("in_", c_vp), ("in_pix_stride", c_ll), ("B", c_int), ("H", c_int), ("W", c_int), ("Cin", c_int),
                 ("w_packed", c_vp), ("bias", c_vp), ("Cout", c_int), ("relu", c_int), ("out", c_vp), ("out_pix_stride", c_ll)]
+
+
+class F32View(ctypes.Structure):
+    """oess_f32_view_t (include/oess.h): an fp32 tensor addressed as data[b sb + y sy + x sx + c sc] (element strides)."""
+    _fields_ = [("data", c_vp), ("sb", c_ll), ("sy", c_ll), ("sx", c_ll), ("sc", c_ll)]
+
+
+c_view = ctypes.POINTER(F32View)
 
 
 # name -> (restype, argtypes).  Must list EVERY symbol of include/oess.h (tests/test_abi.py checks).
@@ -138,6 +146,14 @@ SIGNATURES = {
     "oess_e2vid_postprocess_f32": (c_int, [c_vp, c_ll, c_ll, c_int, c_int, c_int, c_vp, c_d, c_d, c_d, c_vp, c_vp, c_vp]),
     "oess_e2vid_postprocess_auto_hdr_f32": (c_int, [c_vp, c_ll, c_ll, c_int, c_int, c_int, c_vp, c_d, c_int, c_vp, c_sz, c_vp, c_vp,
                                                     c_vp]),
+    "oess_conv2d_f32_packed_floats": (c_sz, [c_int, c_int, c_int, c_int]),
+    "oess_conv_transpose2d_f32_packed_floats": (c_sz, [c_int, c_int]),
+    "oess_convlstm_f32_workspace_bytes": (c_sz, [c_ll, c_int]),
+    "oess_conv2d_fwd_f32": (c_int, [c_view, c_view, c_int, c_int, c_int, c_int, c_int, c_vp, c_vp, c_int, c_int, c_int, c_int, c_int,
+                                    c_int, c_view, c_view, c_vp]),
+    "oess_conv_transpose2d_fwd_f32": (c_int, [c_view, c_view, c_int, c_int, c_int, c_int, c_vp, c_vp, c_int, c_int, c_view, c_vp]),
+    "oess_convlstm_step_f32": (c_int, [c_view, c_int, c_int, c_int, c_int, c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, c_vp, c_view,
+                                       c_vp, c_sz, c_vp]),
 }
 
 _lib = None

@@ -1,6 +1,8 @@
 """Mirror of e2vid/image_reconstructor.py:ImageReconstructor (:18-123) for the training path:
 preprocess -> pad -> recurrent model step -> keep state.  No CudaTimer syncs in the hot loop.
-PostProcessor (:126-140) of the offline reconstruction: unsharp mask + intensity rescaling in one HIP pass."""
+PostProcessor (:126-140) of the offline reconstruction: unsharp mask + intensity rescaling in one HIP pass.
+options.precision = 'fp32' (offline reconstruction only) runs the whole network in fp32 (UNetRecurrent.forward_fp32), as the
+reference does; the default 'bf16' is the training path's bf16-storage kernels."""
 from types import SimpleNamespace
 
 import torch
@@ -18,6 +20,14 @@ class ImageReconstructor:
         if augmentation or standardization:
             raise NotImplementedError("augmentation / standardization act on the discarded image output")
         self.no_recurrent = bool(getattr(options, 'no_recurrent', False))
+        self.precision = str(getattr(options, 'precision', None) or 'bf16')
+        if self.precision not in ('bf16', 'fp32'):
+            raise ValueError(f"precision must be 'bf16' or 'fp32', got {self.precision!r}")
+        if self.precision == 'fp32':
+            unet = getattr(self.model, 'unetrecurrent', None)
+            if unet is None:
+                raise NotImplementedError("precision='fp32' runs recurrent E2VID models (E2VIDRecurrent)")
+            unet.check_fp32()
         self.crop = CropParameters(self.width, self.height, self.model.num_encoders)
         self.last_states_for_each_channel = {'grayscale': None}
         self.event_preprocessor = EventPreprocessor(options)
@@ -35,6 +45,10 @@ class ImageReconstructor:
         output) is None and is never written to memory (head + encoder-0 conv in one kernel).  With `self.skew` (default) such
         calls also run the recurrent encoder on the skewed schedule: the returned states hold levels 1, 2 one / two sub-windows
         behind until the next call with need_latents=True (or reconstruct=True) drains them -- same results, fewer launches."""
+        from .model.unet import check_states
+        check_states(self.last_states_for_each_channel['grayscale'], self.precision)
+        if self.precision == 'fp32':
+            return self._update_fp32(event_tensor, channel_slice, wavefront, need_latents)
         with torch.no_grad():
             if channel_slice is None:
                 events = event_tensor.to(self.device).float().contiguous()
@@ -60,6 +74,29 @@ class ImageReconstructor:
                     if self.crop.needs_pad:
                         x = self.crop.pad(x.float()).to(torch.bfloat16).contiguous(memory_format=torch.channels_last)
             img, states, latent = self.model(x, self.last_states_for_each_channel['grayscale'], reconstruct=reconstruct, **kw)
+            self.last_states_for_each_channel['grayscale'] = None if self.no_recurrent else states
+        return img, states, latent
+
+    def _update_fp32(self, event_tensor, channel_slice, wavefront, need_latents):
+        """fp32 step: EventPreprocessor (reference contract, fp32 out) -> reflection pad -> UNetRecurrent.forward_fp32.  The image
+        is always computed (the fp32 path is the offline reconstruction); the bf16 schedules have no fp32 form and are refused."""
+        if wavefront is not None:
+            raise ValueError("precision='fp32': the wavefront schedule (one HIP stream per level) is a bf16-path option")
+        if not need_latents:
+            raise ValueError("precision='fp32': need_latents=False (fused head / skewed schedule) is a bf16-path option")
+        with torch.no_grad():
+            if channel_slice is None:
+                events = event_tensor.to(self.device).float().contiguous()
+                x = self.event_preprocessor(events)
+            else:
+                (c0, cs) = channel_slice
+                if self.event_preprocessor.no_normalize:
+                    x = event_tensor[:, c0:c0 + cs]
+                else:
+                    x = hip.masked_normalize_slice(event_tensor, c0, cs)
+            if self.crop.needs_pad:
+                x = self.crop.pad(x)
+            img, states, latent = self.model.forward_fp32(x, self.last_states_for_each_channel['grayscale'])
             self.last_states_for_each_channel['grayscale'] = None if self.no_recurrent else states
         return img, states, latent
 

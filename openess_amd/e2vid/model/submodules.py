@@ -9,6 +9,13 @@ import torch.nn as nn
 from ... import engine, hip
 
 
+def _check_f32_norm(norm, bn):
+    if norm == 'IN':
+        raise NotImplementedError("norm='IN' E2VID variants are not on the fp32 path")
+    if bn is not None and bn.training:
+        raise RuntimeError("E2VID runs in eval mode on the fp32 path")
+
+
 class ConvLayer(nn.Module):
     """e2vid/model/submodules.py:7-31.  conv -> (BN | IN) -> activation.  BN is folded into the packed
     weights (module is in eval mode on this path); ReLU is fused in the conv epilogue."""
@@ -24,6 +31,20 @@ class ConvLayer(nn.Module):
         elif norm == 'IN':
             self.norm_layer = nn.InstanceNorm2d(out_channels, track_running_stats=True)
         self._pw = engine.PackedWeight()
+        self._pw32 = engine.PackedWeightF32()
+
+    def forward_f32(self, x, x2=None, act='layer', out=None):
+        """fp32 inference (K14): act(conv(x [+ x2]) + bias) with eval-mode BatchNorm folded; act='layer' = this layer's own
+        activation (ReLU / none), or None / 'relu' / 'sigmoid' (the prediction layer's sigmoid of unet.py:170)."""
+        _check_f32_norm(self.norm, self.norm_layer if self.norm == 'BN' else None)
+        if act == 'layer':
+            if self.activation_name not in (None, 'relu'):
+                raise NotImplementedError("only relu / None activations are on the fp32 path")
+            act = self.activation_name
+        c = self.conv2d
+        pw = self._pw32.get(c.weight, c.bias, self.norm_layer if self.norm == 'BN' else None)
+        return hip.conv2d_f32(x, pw.packed, pw.bias, c.out_channels, c.kernel_size[0], c.kernel_size[1], c.stride[0], c.padding[0],
+                              act=act, x2=x2, out=out)
 
     def forward(self, x, out=None):
         if self.activation_name not in (None, 'relu'):
@@ -57,6 +78,18 @@ class TransposedConvLayer(nn.Module):
         elif norm == 'IN':
             self.norm_layer = nn.InstanceNorm2d(out_channels, track_running_stats=True)
         self._cache = {}
+        self._pw32 = engine.PackedWeightF32()
+
+    def forward_f32(self, x, skip=None):
+        """fp32 inference (K14): relu(BN(ConvTranspose2d(x + skip))) as four phase sub-convolutions in one launch."""
+        _check_f32_norm(self.norm, self.norm_layer if self.norm == 'BN' else None)
+        if self.activation_name not in (None, 'relu'):
+            raise NotImplementedError("only relu / None activations are on the fp32 path")
+        t = self.transposed_conv2d
+        if t.kernel_size != (5, 5) or t.stride != (2, 2) or t.padding != (2, 2) or t.output_padding != (1, 1):
+            raise NotImplementedError("the fp32 transposed convolution is the 5x5 / stride 2 / padding 2 / output_padding 1 form")
+        pw = self._pw32.get(t.weight, t.bias, self.norm_layer if self.norm == 'BN' else None, transposed=True)
+        return hip.conv_transpose2d_f32(x, pw.packed, pw.bias, t.out_channels, act=self.activation_name, x2=skip)
 
     def forward(self, x):
         if self.norm == 'IN' or self.activation_name not in (None, 'relu'):
@@ -88,17 +121,30 @@ class TransposedConvLayer(nn.Module):
 
 
 class UpsampleConvLayer(nn.Module):
-    """e2vid/model/submodules.py:65-93 -- parameter container only (see TransposedConvLayer)."""
+    """e2vid/model/submodules.py:65-93: bilinear x2 (align_corners=False) -> conv -> BN -> relu.  The bf16 path only holds the
+    parameters; the fp32 path (forward_f32) runs it, the interpolation gathered inside the conv's operand load."""
 
     def __init__(self, in_channels, out_channels, kernel_size, stride=1, padding=0, activation='relu', norm=None):
         super().__init__()
         bias = False if norm == 'BN' else True
         self.conv2d = nn.Conv2d(in_channels, out_channels, kernel_size, stride, padding, bias=bias)
+        self.activation_name = activation
         self.norm = norm
         if norm == 'BN':
             self.norm_layer = nn.BatchNorm2d(out_channels)
         elif norm == 'IN':
             self.norm_layer = nn.InstanceNorm2d(out_channels, track_running_stats=True)
+        self._pw32 = engine.PackedWeightF32()
+
+    def forward_f32(self, x, skip=None):
+        """fp32 inference (K14): act(BN(conv(upsample2x(x + skip)))) in one launch."""
+        _check_f32_norm(self.norm, self.norm_layer if self.norm == 'BN' else None)
+        if self.activation_name not in (None, 'relu'):
+            raise NotImplementedError("only relu / None activations are on the fp32 path")
+        c = self.conv2d
+        pw = self._pw32.get(c.weight, c.bias, self.norm_layer if self.norm == 'BN' else None)
+        return hip.conv2d_f32(x, pw.packed, pw.bias, c.out_channels, c.kernel_size[0], c.kernel_size[1], c.stride[0], c.padding[0],
+                              act=self.activation_name, x2=skip, upsample2x=True)
 
 
 class ResidualBlock(nn.Module):
@@ -118,6 +164,20 @@ class ResidualBlock(nn.Module):
         self.conv2 = nn.Conv2d(out_channels, out_channels, kernel_size=3, stride=1, padding=1, bias=bias)
         self.downsample = downsample
         self._pw1, self._pw2 = engine.PackedWeight(), engine.PackedWeight()
+        self._pw32 = (engine.PackedWeightF32(), engine.PackedWeightF32())
+
+    def forward_f32(self, x):
+        """fp32 inference (K14): relu(bn2(conv2(relu(bn1(conv1(x))))) + x), the residual add and ReLU in the second conv's epilogue."""
+        _check_f32_norm(self.norm, self.bn1 if self.norm == 'BN' else None)
+        if self.downsample is not None:
+            raise NotImplementedError("E2VID residual blocks use no downsample")
+        bn1 = self.bn1 if self.norm == 'BN' else None
+        bn2 = self.bn2 if self.norm == 'BN' else None
+        C = self.conv1.out_channels
+        p1 = self._pw32[0].get(self.conv1.weight, self.conv1.bias, bn1)
+        y = hip.conv2d_f32(x, p1.packed, p1.bias, C, 3, 3, self.conv1.stride[0], 1, act='relu')
+        p2 = self._pw32[1].get(self.conv2.weight, self.conv2.bias, bn2)
+        return hip.conv2d_f32(y, p2.packed, p2.bias, C, 3, 3, 1, 1, act='relu', residual=x)
 
     def forward(self, x):
         """conv-bn-relu-conv-bn + residual + relu (:154-172); eval-mode BatchNorm folded, residual add and ReLU in the conv epilogue."""
@@ -147,6 +207,26 @@ class ConvLSTM(nn.Module):
         self.Gates = nn.Conv2d(input_size + hidden_size, 4 * hidden_size, kernel_size, padding=pad)
         self._pw = engine.PackedWeight()
         self._pw_fused = {}
+        self._pw32, self._pw32_x = engine.PackedWeightF32(), engine.PackedWeightF32()
+
+    def step_f32(self, state):
+        """fp32 step (K14) on a RecurrentConvLayer.new_state_f32 state whose x half was just written: gates conv + cell update;
+        h goes to the h half of the same cat(x, h) buffer (the gates are complete before it is written).  A fresh state (zero h
+        and c, submodules.py:190-198) convolves the x half alone.  Returns the hidden state view [B, C, H, W]."""
+        g = self.Gates
+        C = self.hidden_size
+        xh = state['xh']
+        h_view = engine.from_nhwc(xh[..., C:])
+        k, pad = g.kernel_size[0], g.padding[0]
+        if state['fresh']:
+            pw = self._pw32_x.get(g.weight, g.bias, cin=self.input_size)
+            inp = engine.from_nhwc(xh[..., :self.input_size])
+        else:
+            pw = self._pw32.get(g.weight, g.bias)
+            inp = engine.from_nhwc(xh)
+        hip.convlstm_step_f32(inp, pw.packed, pw.bias, C, k, pad, state['cell'], h_view, prev_cell_is_zero=state['fresh'])
+        state['fresh'] = False
+        return h_view
 
     def fused_args(self, state):
         """Arguments of hip.convlstm_fused (or one problem of hip.convlstm_fused_group) for this state: xh, packed gates, bias,
@@ -266,6 +346,25 @@ class RecurrentConvLayer(nn.Module):
         Co = self.conv.conv2d.out_channels
         self.conv(x, out=state['xh'][state['cur']][:, :Co])         # x -> first half of the current cat(x, h) buffer
         return state
+
+    def new_state_f32(self, x):
+        """State of the fp32 path: one cat(x, h) buffer fp32 [B, Ho, Wo, 2 C] (x half written by the encoder conv, h half by the
+        ConvLSTM step), the cell fp32 [B, Ho, Wo, C], 'fresh' = no previous state; 'precision' tells it from a bf16 state."""
+        B, _, H, W = x.shape
+        c = self.conv.conv2d
+        Ho = (H + 2 * c.padding[0] - c.kernel_size[0]) // c.stride[0] + 1
+        Wo = (W + 2 * c.padding[0] - c.kernel_size[0]) // c.stride[0] + 1
+        Co = c.out_channels
+        return {'precision': 'fp32', 'xh': torch.empty((B, Ho, Wo, 2 * Co), dtype=torch.float32, device=x.device),
+                'cell': torch.empty((B, Ho, Wo, Co), dtype=torch.float32, device=x.device), 'fresh': True}
+
+    def forward_f32(self, x, prev_state):
+        """fp32 inference (K14): encoder conv into the x half of the state's cat(x, h) buffer, then the ConvLSTM step.
+        Returns (h view [B, C, Ho, Wo], state)."""
+        state = prev_state if prev_state is not None else self.new_state_f32(x)
+        Co = self.conv.conv2d.out_channels
+        self.conv.forward_f32(x, out=engine.from_nhwc(state['xh'][..., :Co]))
+        return self.recurrent_block.step_f32(state), state
 
     def forward(self, x, prev_state):
         state = self.run_conv(x, prev_state)

@@ -20,6 +20,22 @@ class _SkewStates(list):
         return any(r is not None for r in self.ready[:-1])
 
 
+def state_precision(state):
+    """'fp32' for a state of the fp32 path (RecurrentConvLayer.new_state_f32), 'bf16' for any other state, None for None."""
+    if state is None:
+        return None
+    return 'fp32' if isinstance(state, dict) and state.get('precision') == 'fp32' else 'bf16'
+
+
+def check_states(prev_states, precision):
+    """ValueError when a state of the other precision is passed to a step of `precision`."""
+    for i, st in enumerate(prev_states if prev_states is not None else []):
+        got = state_precision(st)
+        if got is not None and got != precision:
+            raise ValueError(f"E2VID state of level {i} is {got}, this step runs in {precision}: states do not carry over between "
+                             "precisions (start a new sequence)")
+
+
 class UNetRecurrent(nn.Module):
     group_s2 = True          # skewed schedule: the two deeper encoder convs of a call as one launch (False: one launch each; A/B switch)
 
@@ -177,6 +193,7 @@ class UNetRecurrent(nn.Module):
         pretrain_trainer.py:437-441): latent[1] is None and head + encoder-0 conv run as ONE kernel.
         `skew=True`: the skewed single-stream schedule of _forward_skew (calls with need_head=False return no usable latents and
         leave the deeper levels one / two sub-windows behind; the need_head=True call that ends the sequence drains them)."""
+        check_states(prev_states, 'bf16')
         if skew and not reconstruct and wavefront is None:
             return self._forward_skew(x, prev_states, need_head, raw)
         if isinstance(prev_states, _SkewStates):
@@ -234,4 +251,39 @@ class UNetRecurrent(nn.Module):
             pw = p._pw.get(p.conv2d.weight, p.conv2d.bias, p.norm_layer if p.norm == 'BN' else None, cin_pad=x.shape[1])
             logits = engine.conv2d_infer(x + head, pw, 1, 1, 1, 0, 1, out_f32=True)     # 32 -> 1, fp32 output
             img = torch.sigmoid(logits.float())
+        return img, states, latent
+
+    def check_fp32(self):
+        """The configurations forward_fp32 runs: norm None / 'BN' (eval), skip_type 'sum'; raises otherwise (before any launch)."""
+        if self.norm == 'IN':
+            raise NotImplementedError("norm='IN' E2VID variants are not on the fp32 path")
+        if self.skip_type != 'sum':
+            raise NotImplementedError("E2VID checkpoints use skip_type 'sum'")
+
+    def forward_fp32(self, x, prev_states):
+        """fp32 inference (K14, offline reconstruction): the whole UNetRecurrent forward of the reference (unet.py:146-170) on the
+        f32-input MFMA kernels.  x: fp32 [B, num_bins, H, W] (any strides).  Returns (img fp32 [B, 1, H, W], states, latent) with
+        the meaning of forward(..., reconstruct=True); latents are fp32 logical-NCHW tensors in channels_last storage (the encoder
+        outputs are the hidden-state halves of the states' cat(x, h) buffers: the next step overwrites them), states are fp32."""
+        self.check_fp32()
+        check_states(prev_states, 'fp32')
+        if x.dtype != __import__('torch').float32 or x.ndim != 4 or x.shape[1] != self.num_input_channels:
+            raise ValueError(f"forward_fp32 needs an fp32 [B, {self.num_input_channels}, H, W] tensor")
+        if prev_states is None:
+            prev_states = [None] * self.num_encoders
+        head = self.head.forward_f32(x)
+        x = head
+        blocks, states = [], []
+        for i, encoder in enumerate(self.encoders):
+            x, state = encoder.forward_f32(x, prev_states[i])
+            blocks.append(x)
+            states.append(state)
+        for resblock in self.resblocks:
+            x = resblock.forward_f32(x)
+        for i, decoder in enumerate(self.decoders):
+            x = decoder.forward_f32(x, skip=blocks[self.num_encoders - i - 1])       # decoder(skip_sum(x, block)), summed on load
+        img = self.pred.forward_f32(x, x2=head, act='sigmoid')                      # sigmoid(pred(skip_sum(x, head)))
+        latent = {1: head}
+        for i, b in enumerate(blocks):
+            latent[2 ** (i + 1)] = b
         return img, states, latent

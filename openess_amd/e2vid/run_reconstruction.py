@@ -9,6 +9,8 @@ executes; `-o/--output_folder` + `--dataset_name` follow e2vid/options/inference
 `--postprocess` runs the reference's PostProcessor (unsharp mask + intensity rescaling, optionally auto-HDR; image_reconstructor.py
 :126-140) on each cropped frame and writes its bytes; its tuning flags (`--unsharp_mask_amount`, `--Imin`, `--auto_hdr`, ...) keep
 the reference's defaults and are refused without it.  Without `--postprocess` a frame is round(clamp(img, 0, 1) * 255).
+`--precision fp32` runs the network in fp32 as the reference does (f32-input MFMA kernels); the default `bf16`
+runs it on the training path's bf16-storage kernels.
 
 Checkpoint format: the reference's (`{'arch': 'E2VIDRecurrent', 'model' | 'config.model': {...}, 'state_dict': ...}`,
 e2vid/utils/loading_utils.py:5-16); `-c random` builds E2VID_lightweight with seeded random weights (no checkpoint
@@ -42,16 +44,20 @@ def load_model(path_to_model):
 
 def reconstruct(path_to_events, model, output_folder=None, window_size=None, fixed_duration=False, window_duration=33.33,
                 num_events_per_pixel=0.35, skipevents=0, suboffset=0, device='cuda', max_windows=None, postprocessor=None,
-                options=None):
+                options=None, precision='bf16'):
     """Returns the list of reconstructed images (uint8 [H, W]); writes frame_%010d.png + timestamps.txt when a folder is given.
     postprocessor: a PostProcessor applied to each cropped frame (its bytes are the image); None = round(clamp(img, 0, 1) * 255).
-    options: passed to ImageReconstructor (no_normalize, no_recurrent)."""
+    options: passed to ImageReconstructor (no_normalize, no_recurrent).  precision: 'bf16' (default) or 'fp32' (the whole network
+    in fp32, UNetRecurrent.forward_fp32); it overrides options.precision."""
+    if precision not in ('bf16', 'fp32'):
+        raise ValueError(f"precision must be 'bf16' or 'fp32', got {precision!r}")
     with open(path_to_events) as f:
         width, height = (int(v) for v in f.readline().split())
     print('Sensor size: {} x {}'.format(width, height))
     device = torch.device(device)
     model = model.to(device).eval()
-    rec = ImageReconstructor(model, height, width, model.num_bins, device, options)
+    opts = SimpleNamespace(**dict(vars(options) if options is not None else {}, precision=precision))
+    rec = ImageReconstructor(model, height, width, model.num_bins, device, opts)
     N = window_size
     if not fixed_duration and N is None:
         N = int(width * height * num_events_per_pixel)
@@ -106,6 +112,8 @@ def main(argv=None):
     p.add_argument('--dataset_name', default='reconstruction', type=str)
     p.add_argument('--no-normalize', dest='no_normalize', action='store_true')
     p.add_argument('--no-recurrent', dest='no_recurrent', action='store_true')
+    p.add_argument('--precision', choices=('bf16', 'fp32'), default='bf16',
+                   help="network arithmetic: bf16 (default, the training path's kernels) or fp32 (as the reference)")
     g = p.add_argument_group('post-processing (e2vid/options/inference_options.py:31-46; only with --postprocess)')
     g.add_argument('--postprocess', action='store_true', help="run the reference's PostProcessor (unsharp mask + intensity rescaling)")
     for name, default, typ in POSTPROCESS_FLAGS:
@@ -122,7 +130,7 @@ def main(argv=None):
     post = PostProcessor(torch.device('cuda'), opts) if a.postprocess else None
     out = os.path.join(a.output_folder, a.dataset_name) if a.output_folder else None
     return reconstruct(a.input_file, load_model(a.path_to_model), out, a.window_size, a.fixed_duration, a.window_duration,
-                       a.num_events_per_pixel, a.skipevents, a.suboffset, postprocessor=post, options=opts)
+                       a.num_events_per_pixel, a.skipevents, a.suboffset, postprocessor=post, options=opts, precision=a.precision)
 
 
 if __name__ == "__main__":

@@ -168,6 +168,38 @@ class PackedWeight:
         return self
 
 
+class PackedWeightF32:
+    """fp32 operand of a conv (or, transposed=True, a ConvTranspose2d) weight for the K14 kernels (hip.conv2d_f32,
+    hip.conv_transpose2d_f32), with an eval-mode BatchNorm folded in (in float64, rounded once), cached per parameter versions.
+    cin: keep only the first `cin` input channels (the x half of a ConvLSTM Gates weight, for a step from a zero state)."""
+
+    def __init__(self):
+        self.key = None
+        self.packed = None
+        self.bias = None
+
+    def get(self, weight, bias=None, bn=None, transposed=False, cin=None):
+        key = (weight._version, None if bias is None else bias._version,
+               None if bn is None else (bn.weight._version, bn.bias._version, bn.running_mean._version, bn.running_var._version),
+               transposed, cin)
+        if key != self.key:
+            with torch.no_grad():
+                w = weight.detach().double()
+                b = None if bias is None else bias.detach().double()
+                if bn is not None:     # y = gamma * (conv(x) - mu) / sqrt(var + eps) + beta  (BatchNorm2d in eval mode)
+                    scale = bn.weight.detach().double() / torch.sqrt(bn.running_var.detach().double() + bn.eps)
+                    w = w * (scale[None, :, None, None] if transposed else scale[:, None, None, None])
+                    b0 = torch.zeros_like(scale) if b is None else b
+                    b = (b0 - bn.running_mean.detach().double()) * scale + bn.bias.detach().double()
+                if cin is not None:
+                    w = w[:, :cin]
+                w = w.float()
+                self.packed = hip.pack_conv_transpose_weight_f32(w) if transposed else hip.pack_conv_weight_f32(w)
+                self.bias = None if b is None else b.float().contiguous()
+            self.key = key
+        return self
+
+
 def conv2d_infer(x, pw, Cout, k, stride=1, pad=0, dil=1, relu=False, residual=None, out=None, out_f32=False):
     """Inference conv on logical-NCHW channels_last tensors.  Returns logical NCHW."""
     y = hip.conv2d_nhwc(nhwc(x), pw.packed, pw.bias, Cout, k, k, stride, pad, dil, relu=relu,

@@ -1850,3 +1850,138 @@ def e2vid_postprocess(img, weights, amount, bounds=None, hdr_state=None, out_u8=
         _lib.check(lib.oess_e2vid_postprocess_auto_hdr_f32(*geo, hdr_state.filter_size, _ptr(hdr_state.buf), hdr_state.buf.numel(),
                                                            _ptr(out_u8), _ptr(out_f32), _stream()), "oess_e2vid_postprocess_auto_hdr_f32")
     return out_u8, out_f32
+
+
+# ------------------------------------------------------------------------------------------ K14: fp32 E2VID inference
+_F32_ACT = {None: 0, 'relu': 1, 'sigmoid': 2}
+
+
+def _f32_view(t, what):
+    """Logical [B, C, H, W] fp32 tensor with any strides (NCHW, channels_last, channel / crop views) -> oess_f32_view_t."""
+    if t.dtype != torch.float32 or t.ndim != 4:
+        raise ValueError(f"{what} must be a 4-D float32 tensor [B, C, H, W]")
+    return _lib.F32View(t.data_ptr(), t.stride(0), t.stride(2), t.stride(3), t.stride(1))
+
+
+def _f32_ref(v):
+    return None if v is None else ctypes.byref(v)
+
+
+def _f32_operands(x, x2, packed, bias, Cout, need):
+    _need_gpu(x, x2, packed, bias)
+    vx = _f32_view(x, "x")
+    v2 = None
+    if x2 is not None:
+        if tuple(x2.shape) != tuple(x.shape):
+            raise ValueError(f"x2 {tuple(x2.shape)} must have the shape of x {tuple(x.shape)}")
+        v2 = _f32_view(x2, "x2")
+    if packed.dtype != torch.float32 or not packed.is_contiguous() or need == 0 or packed.numel() < need:
+        raise ValueError(f"packed weight must be a contiguous fp32 tensor of at least {need} floats")
+    if bias is not None and (bias.dtype != torch.float32 or not bias.is_contiguous() or bias.numel() != Cout):
+        raise ValueError(f"bias must be a contiguous fp32 tensor of {Cout} elements")
+    return vx, v2
+
+
+def _f32_out(out, B, Cout, Ho, Wo, device):
+    if out is None:
+        return torch.empty((B, Ho, Wo, Cout), dtype=torch.float32, device=device).permute(0, 3, 1, 2)
+    _need_gpu(out)
+    if tuple(out.shape) != (B, Cout, Ho, Wo):
+        raise ValueError(f"bad output shape {tuple(out.shape)} != {(B, Cout, Ho, Wo)}")
+    return out
+
+
+def pack_conv_weight_f32(w):
+    """Conv2d weight [Cout, Cin, R, S] -> the fp32 operand of oess_conv2d_fwd_f32: [ceil16(R S Cin)][ceil32(Cout)], row
+    (r S + s) Cin + ci (include/oess.h).  Parameter preparation, once per weight version (engine.PackedWeightF32)."""
+    Co, Ci, R, S = w.shape
+    n = _lib.load().oess_conv2d_f32_packed_floats(Co, Ci, R, S)
+    if n == 0:
+        raise ValueError(f"no fp32 packing for a {tuple(w.shape)} weight")
+    Kp, Cp = (R * S * Ci + 15) // 16 * 16, (Co + 31) // 32 * 32
+    out = torch.zeros((Kp, Cp), dtype=torch.float32, device=w.device)
+    out[:R * S * Ci, :Co] = w.detach().float().permute(2, 3, 1, 0).reshape(R * S * Ci, Co)
+    return out
+
+
+def pack_conv_transpose_weight_f32(w):
+    """ConvTranspose2d weight [Cin, Cout, 5, 5] -> the four phase blocks of oess_conv_transpose2d_fwd_f32 (include/oess.h)."""
+    Ci, Co, R, S = w.shape
+    if (R, S) != (5, 5):
+        raise ValueError("oess_conv_transpose2d_fwd_f32 takes 5 x 5 kernels")
+    Cp = (Co + 31) // 32 * 32
+    blocks = []
+    for p in range(4):
+        py, px = p >> 1, p & 1
+        sub = w.detach().float()[:, :, py::2, px::2]                  # [Cin, Cout, ny, nx]: taps ky = py + 2 ty
+        ny, nx = sub.shape[2], sub.shape[3]
+        blk = torch.zeros(((ny * nx * Ci + 15) // 16 * 16, Cp), dtype=torch.float32, device=w.device)
+        blk[:ny * nx * Ci, :Co] = sub.permute(2, 3, 0, 1).reshape(ny * nx * Ci, Co)
+        blocks.append(blk)
+    out = torch.cat(blocks, 0).reshape(-1)
+    assert out.numel() == _lib.load().oess_conv_transpose2d_f32_packed_floats(Co, Ci)
+    return out
+
+
+def conv2d_f32(x, packed, bias, Cout, R, S, stride=1, pad=0, act=None, x2=None, upsample2x=False, residual=None, out=None):
+    """out = act(conv(x [+ x2]) + bias [+ residual]) in fp32 on the f32-input MFMA (oess_conv2d_fwd_f32).  x, x2, residual, out:
+    logical [B, C, H, W] fp32 tensors with any strides (channels_last and channel slices take the vector loads); act: None, 'relu'
+    or 'sigmoid'; upsample2x: convolve the bilinear x2 (align_corners=False) of x [+ x2].  Returns out (channels_last if new)."""
+    lib = _lib.load()
+    B, Cin, H, W = x.shape
+    vx, v2 = _f32_operands(x, x2, packed, bias, Cout, lib.oess_conv2d_f32_packed_floats(Cout, Cin, R, S))
+    if act not in _F32_ACT:
+        raise ValueError(f"act must be one of {list(_F32_ACT)}")
+    Hl, Wl = (2 * H, 2 * W) if upsample2x else (H, W)
+    Ho, Wo = (Hl + 2 * pad - R) // stride + 1, (Wl + 2 * pad - S) // stride + 1
+    out = _f32_out(out, B, Cout, Ho, Wo, x.device)
+    vr = None
+    if residual is not None:
+        _need_gpu(residual)
+        if tuple(residual.shape) != (B, Cout, Ho, Wo):
+            raise ValueError(f"residual shape {tuple(residual.shape)} != {(B, Cout, Ho, Wo)}")
+        vr = _f32_view(residual, "residual")
+    vo = _f32_view(out, "out")
+    _lib.check(lib.oess_conv2d_fwd_f32(ctypes.byref(vx), _f32_ref(v2), B, H, W, Cin, int(bool(upsample2x)), _ptr(packed), _ptr(bias),
+                                       Cout, R, S, stride, pad, _F32_ACT[act], _f32_ref(vr), ctypes.byref(vo), _stream()),
+               "oess_conv2d_fwd_f32")
+    _bump(out)
+    return out
+
+
+def conv_transpose2d_f32(x, packed, bias, Cout, act=None, x2=None, out=None):
+    """ConvTranspose2d(k 5, stride 2, padding 2, output_padding 1) of x [+ x2] + bias, act, in fp32: four phase sub-convolutions in
+    one launch (oess_conv_transpose2d_fwd_f32).  `packed` from pack_conv_transpose_weight_f32.  out: [B, Cout, 2H, 2W]."""
+    lib = _lib.load()
+    B, Cin, H, W = x.shape
+    vx, v2 = _f32_operands(x, x2, packed, bias, Cout, lib.oess_conv_transpose2d_f32_packed_floats(Cout, Cin))
+    if act not in _F32_ACT:
+        raise ValueError(f"act must be one of {list(_F32_ACT)}")
+    out = _f32_out(out, B, Cout, 2 * H, 2 * W, x.device)
+    vo = _f32_view(out, "out")
+    _lib.check(lib.oess_conv_transpose2d_fwd_f32(ctypes.byref(vx), _f32_ref(v2), B, H, W, Cin, _ptr(packed), _ptr(bias), Cout,
+                                                 _F32_ACT[act], ctypes.byref(vo), _stream()), "oess_conv_transpose2d_fwd_f32")
+    _bump(out)
+    return out
+
+
+def convlstm_step_f32(xh, packed, bias, C, k, pad, cell, hidden_out, prev_cell_is_zero=False):
+    """One fp32 ConvLSTM step (oess_convlstm_step_f32): gates = conv(xh) + bias (k x k, `pad`), then the cell update in place in
+    `cell` (contiguous fp32 [B, H, W, C]) and the new hidden state into `hidden_out` (a [B, C, H, W] fp32 view, e.g. the h half of
+    the cat(x, h) buffer that xh belongs to: the gates are complete before it is written).  xh: [B, Cin, H, W] fp32 view."""
+    lib = _lib.load()
+    B, Cin, H, W = xh.shape
+    vx, _ = _f32_operands(xh, None, packed, bias, 4 * C, lib.oess_conv2d_f32_packed_floats(4 * C, Cin, k, k))
+    _need_gpu(cell, hidden_out)
+    if cell.dtype != torch.float32 or not cell.is_contiguous() or tuple(cell.shape) != (B, H, W, C):
+        raise ValueError(f"cell must be a contiguous fp32 [B, H, W, C] = {(B, H, W, C)} tensor")
+    if tuple(hidden_out.shape) != (B, C, H, W):
+        raise ValueError(f"hidden_out shape {tuple(hidden_out.shape)} != {(B, C, H, W)}")
+    vh = _f32_view(hidden_out, "hidden_out")
+    need = lib.oess_convlstm_f32_workspace_bytes(B * H * W, C)
+    ws = _workspace(need, xh.device, tag="convlstm_f32")
+    _lib.check(lib.oess_convlstm_step_f32(ctypes.byref(vx), B, H, W, Cin, _ptr(packed), _ptr(bias), C, k, k, pad, int(bool(prev_cell_is_zero)),
+                                          _ptr(cell), ctypes.byref(vh), _ptr(ws), ws.numel(), _stream()), "oess_convlstm_step_f32")
+    _bump(cell)
+    _bump(hidden_out)
+    return hidden_out
