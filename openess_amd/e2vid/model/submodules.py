@@ -9,21 +9,30 @@ import torch.nn as nn
 from ... import engine, hip
 
 
-def _check_f32_norm(norm, bn):
+def check_runs(norm, bn, activation=None):
+    """The layer configurations the HIP paths (bf16 and fp32) run: no InstanceNorm, BatchNorm in eval mode (it is folded into
+    the packed weights: the E2VID front end is frozen, pretrain_trainer.py:370-373), relu / no activation.  Raises otherwise."""
     if norm == 'IN':
-        raise NotImplementedError("norm='IN' E2VID variants are not on the fp32 path")
+        raise NotImplementedError("norm='IN' E2VID variants are not on the HIP paths")
     if bn is not None and bn.training:
-        raise RuntimeError("E2VID runs in eval mode on the fp32 path")
+        raise RuntimeError("E2VID runs in eval mode on the HIP paths (BatchNorm is folded into the packed weights)")
+    if activation not in (None, 'relu'):
+        raise NotImplementedError("only relu / None activations are on the HIP paths")
 
 
-class ConvLayer(nn.Module):
-    """e2vid/model/submodules.py:7-31.  conv -> (BN | IN) -> activation.  BN is folded into the packed
-    weights (module is in eval mode on this path); ReLU is fused in the conv epilogue."""
+class _ConvNormAct(nn.Module):
+    """conv -> (BN | IN) -> activation: the constructor ConvLayer, TransposedConvLayer and UpsampleConvLayer share, under the
+    reference's parameter names (conv2d / transposed_conv2d, norm_layer)."""
+    transposed = False
 
     def __init__(self, in_channels, out_channels, kernel_size, stride=1, padding=0, activation='relu', norm=None):
         super().__init__()
         bias = False if norm == 'BN' else True
-        self.conv2d = nn.Conv2d(in_channels, out_channels, kernel_size, stride, padding, bias=bias)
+        if self.transposed:
+            self.transposed_conv2d = nn.ConvTranspose2d(in_channels, out_channels, kernel_size, stride=2, padding=padding,
+                                                        output_padding=1, bias=bias)
+        else:
+            self.conv2d = nn.Conv2d(in_channels, out_channels, kernel_size, stride, padding, bias=bias)
         self.activation_name = activation
         self.norm = norm
         if norm == 'BN':
@@ -33,116 +42,77 @@ class ConvLayer(nn.Module):
         self._pw = engine.PackedWeight()
         self._pw32 = engine.PackedWeightF32()
 
+    @property
+    def bn(self):
+        """The BatchNorm2d to fold into the packed weights, or None."""
+        return self.norm_layer if self.norm == 'BN' else None
+
+
+class ConvLayer(_ConvNormAct):
+    """e2vid/model/submodules.py:7-31.  conv -> (BN | IN) -> activation.  BN is folded into the packed
+    weights (module is in eval mode on this path); ReLU is fused in the conv epilogue."""
+
     def forward_f32(self, x, x2=None, act='layer', out=None):
         """fp32 inference (K14): act(conv(x [+ x2]) + bias) with eval-mode BatchNorm folded; act='layer' = this layer's own
         activation (ReLU / none), or None / 'relu' / 'sigmoid' (the prediction layer's sigmoid of unet.py:170)."""
-        _check_f32_norm(self.norm, self.norm_layer if self.norm == 'BN' else None)
+        check_runs(self.norm, self.bn, self.activation_name if act == 'layer' else None)
         if act == 'layer':
-            if self.activation_name not in (None, 'relu'):
-                raise NotImplementedError("only relu / None activations are on the fp32 path")
             act = self.activation_name
         c = self.conv2d
-        pw = self._pw32.get(c.weight, c.bias, self.norm_layer if self.norm == 'BN' else None)
+        pw = self._pw32.get(c.weight, c.bias, self.bn)
         return hip.conv2d_f32(x, pw.packed, pw.bias, c.out_channels, c.kernel_size[0], c.kernel_size[1], c.stride[0], c.padding[0],
                               act=act, x2=x2, out=out)
 
+    def _packed(self, cin_pad):
+        """The bf16 operand (engine.PackedWeight) for an input of `cin_pad` (zero-padded) channels."""
+        return self._pw.get(self.conv2d.weight, self.conv2d.bias, self.bn, cin_pad=cin_pad)
+
     def forward(self, x, out=None):
-        if self.activation_name not in (None, 'relu'):
-            raise NotImplementedError("only relu / None activations are on the hot path")
-        if self.norm == 'IN':
-            raise NotImplementedError("norm='IN' E2VID variants are not on the hot path")
-        if self.norm == 'BN' and self.norm_layer.training:
-            raise RuntimeError("E2VID front end is frozen/eval on this path (pretrain_trainer.py:370-373)")
+        check_runs(self.norm, self.bn, self.activation_name)
         c = self.conv2d
-        pw = self._pw.get(c.weight, c.bias, self.norm_layer if self.norm == 'BN' else None, cin_pad=x.shape[1])
-        return engine.conv2d_infer(x, pw, c.out_channels, c.kernel_size[0], c.stride[0], c.padding[0], 1,
+        return engine.conv2d_infer(x, self._packed(x.shape[1]), c.out_channels, c.kernel_size[0], c.stride[0], c.padding[0], 1,
                                    relu=self.activation_name == 'relu', out=out)
 
 
-class TransposedConvLayer(nn.Module):
+class TransposedConvLayer(_ConvNormAct):
     """e2vid/model/submodules.py:34-62: ConvTranspose2d(k, stride 2, padding, output_padding 1) -> BN -> relu.  Only the offline
     reconstruction path runs it (unet.py:165-166; the training path stops at the latents).  A transposed convolution IS the
     data gradient of the strided convolution with the same weight tensor, so it runs on the same two kernels as autograd's
-    dgrad: zero insertion (oess_zero_insert_nhwc_bf16) + the MFMA conv on the rotated / transposed packing; the eval-mode
-    BatchNorm is folded into that packing and ReLU is fused in the epilogue."""
-
-    def __init__(self, in_channels, out_channels, kernel_size, stride=1, padding=0, activation='relu', norm=None):
-        super().__init__()
-        bias = False if norm == 'BN' else True
-        self.transposed_conv2d = nn.ConvTranspose2d(in_channels, out_channels, kernel_size, stride=2, padding=padding,
-                                                    output_padding=1, bias=bias)
-        self.activation_name = activation
-        self.norm = norm
-        if norm == 'BN':
-            self.norm_layer = nn.BatchNorm2d(out_channels)
-        elif norm == 'IN':
-            self.norm_layer = nn.InstanceNorm2d(out_channels, track_running_stats=True)
-        self._cache = {}
-        self._pw32 = engine.PackedWeightF32()
+    dgrad: zero insertion (oess_zero_insert_nhwc_bf16) + the MFMA conv on the rotated / transposed packing
+    (engine.PackedWeight, layout='transposed'); the eval-mode BatchNorm is folded into that packing and ReLU is fused in the
+    epilogue."""
+    transposed = True
 
     def forward_f32(self, x, skip=None):
         """fp32 inference (K14): relu(BN(ConvTranspose2d(x + skip))) as four phase sub-convolutions in one launch."""
-        _check_f32_norm(self.norm, self.norm_layer if self.norm == 'BN' else None)
-        if self.activation_name not in (None, 'relu'):
-            raise NotImplementedError("only relu / None activations are on the fp32 path")
+        check_runs(self.norm, self.bn, self.activation_name)
         t = self.transposed_conv2d
         if t.kernel_size != (5, 5) or t.stride != (2, 2) or t.padding != (2, 2) or t.output_padding != (1, 1):
             raise NotImplementedError("the fp32 transposed convolution is the 5x5 / stride 2 / padding 2 / output_padding 1 form")
-        pw = self._pw32.get(t.weight, t.bias, self.norm_layer if self.norm == 'BN' else None, transposed=True)
+        pw = self._pw32.get(t.weight, t.bias, self.bn, transposed=True)
         return hip.conv_transpose2d_f32(x, pw.packed, pw.bias, t.out_channels, act=self.activation_name, x2=skip)
 
     def forward(self, x):
-        if self.norm == 'IN' or self.activation_name not in (None, 'relu'):
-            raise NotImplementedError("only BN / no norm with relu / None are used by the shipped E2VID configurations")
+        check_runs(self.norm, self.bn, self.activation_name)
         t = self.transposed_conv2d
-        if self.norm == 'BN' and self.norm_layer.training:
-            raise RuntimeError("E2VID runs in eval mode on this path")
         k, pad = t.kernel_size[0], t.padding[0]
-        bn = self.norm_layer if self.norm == 'BN' else None
-        key = (t.weight._version, None if t.bias is None else t.bias._version,
-               None if bn is None else (bn.weight._version, bn.bias._version, bn.running_mean._version, bn.running_var._version))
-        if self._cache.get('key') != key:
-            with torch.no_grad():
-                w = t.weight.detach().float()                        # [Cin, Cout, k, k] == Conv2d weight of the strided conv it transposes
-                b = None if t.bias is None else t.bias.detach().float()
-                if bn is not None:
-                    scale = bn.weight.detach().float() / torch.sqrt(bn.running_var.detach().float() + bn.eps)
-                    w = w * scale[None, :, None, None]
-                    b0 = torch.zeros_like(scale) if b is None else b
-                    b = (b0 - bn.running_mean.detach().float()) * scale + bn.bias.detach().float()
-                self._cache = {'key': key, 'packed': hip.pack_conv_weight(w.contiguous(), flip=True),
-                               'bias': None if b is None else b.contiguous()}
+        pw = self._pw.get(t.weight, t.bias, self.bn, layout='transposed')
         B, Cin, H, W = x.shape
         Ho, Wo = (H - 1) * 2 - 2 * pad + k + 1, (W - 1) * 2 - 2 * pad + k + 1
         z = hip.zero_insert(engine.nhwc(x), 2, Ho - (k - 1) + 2 * pad, Wo - (k - 1) + 2 * pad)
-        y = hip.conv2d_nhwc(z, self._cache['packed'], self._cache['bias'], t.out_channels, k, k, 1, (k - 1) - pad, 1,
-                            relu=self.activation_name == 'relu')
+        y = hip.conv2d_nhwc(z, pw.packed, pw.bias, t.out_channels, k, k, 1, (k - 1) - pad, 1, relu=self.activation_name == 'relu')
         return engine.from_nhwc(y)
 
 
-class UpsampleConvLayer(nn.Module):
+class UpsampleConvLayer(_ConvNormAct):
     """e2vid/model/submodules.py:65-93: bilinear x2 (align_corners=False) -> conv -> BN -> relu.  The bf16 path only holds the
     parameters; the fp32 path (forward_f32) runs it, the interpolation gathered inside the conv's operand load."""
 
-    def __init__(self, in_channels, out_channels, kernel_size, stride=1, padding=0, activation='relu', norm=None):
-        super().__init__()
-        bias = False if norm == 'BN' else True
-        self.conv2d = nn.Conv2d(in_channels, out_channels, kernel_size, stride, padding, bias=bias)
-        self.activation_name = activation
-        self.norm = norm
-        if norm == 'BN':
-            self.norm_layer = nn.BatchNorm2d(out_channels)
-        elif norm == 'IN':
-            self.norm_layer = nn.InstanceNorm2d(out_channels, track_running_stats=True)
-        self._pw32 = engine.PackedWeightF32()
-
     def forward_f32(self, x, skip=None):
         """fp32 inference (K14): act(BN(conv(upsample2x(x + skip)))) in one launch."""
-        _check_f32_norm(self.norm, self.norm_layer if self.norm == 'BN' else None)
-        if self.activation_name not in (None, 'relu'):
-            raise NotImplementedError("only relu / None activations are on the fp32 path")
+        check_runs(self.norm, self.bn, self.activation_name)
         c = self.conv2d
-        pw = self._pw32.get(c.weight, c.bias, self.norm_layer if self.norm == 'BN' else None)
+        pw = self._pw32.get(c.weight, c.bias, self.bn)
         return hip.conv2d_f32(x, pw.packed, pw.bias, c.out_channels, c.kernel_size[0], c.kernel_size[1], c.stride[0], c.padding[0],
                               act=self.activation_name, x2=skip, upsample2x=True)
 
@@ -166,13 +136,17 @@ class ResidualBlock(nn.Module):
         self._pw1, self._pw2 = engine.PackedWeight(), engine.PackedWeight()
         self._pw32 = (engine.PackedWeightF32(), engine.PackedWeightF32())
 
-    def forward_f32(self, x):
-        """fp32 inference (K14): relu(bn2(conv2(relu(bn1(conv1(x))))) + x), the residual add and ReLU in the second conv's epilogue."""
-        _check_f32_norm(self.norm, self.bn1 if self.norm == 'BN' else None)
+    def _checked_bns(self):
+        """(bn1, bn2) to fold into the two convs, or (None, None); raises for the configurations the HIP paths do not run."""
+        bn1, bn2 = (self.bn1, self.bn2) if self.norm == 'BN' else (None, None)
+        check_runs(self.norm, bn1)
         if self.downsample is not None:
             raise NotImplementedError("E2VID residual blocks use no downsample")
-        bn1 = self.bn1 if self.norm == 'BN' else None
-        bn2 = self.bn2 if self.norm == 'BN' else None
+        return bn1, bn2
+
+    def forward_f32(self, x):
+        """fp32 inference (K14): relu(bn2(conv2(relu(bn1(conv1(x))))) + x), the residual add and ReLU in the second conv's epilogue."""
+        bn1, bn2 = self._checked_bns()
         C = self.conv1.out_channels
         p1 = self._pw32[0].get(self.conv1.weight, self.conv1.bias, bn1)
         y = hip.conv2d_f32(x, p1.packed, p1.bias, C, 3, 3, self.conv1.stride[0], 1, act='relu')
@@ -181,12 +155,7 @@ class ResidualBlock(nn.Module):
 
     def forward(self, x):
         """conv-bn-relu-conv-bn + residual + relu (:154-172); eval-mode BatchNorm folded, residual add and ReLU in the conv epilogue."""
-        if self.norm == 'IN' or self.downsample is not None:
-            raise NotImplementedError("E2VID residual blocks use BN / no norm and no downsample")
-        bn1 = self.bn1 if self.norm == 'BN' else None
-        bn2 = self.bn2 if self.norm == 'BN' else None
-        if bn1 is not None and bn1.training:
-            raise RuntimeError("E2VID runs in eval mode on this path")
+        bn1, bn2 = self._checked_bns()
         C = self.conv1.out_channels
         p1 = self._pw1.get(self.conv1.weight, self.conv1.bias, bn1, cin_pad=x.shape[1])
         y = engine.conv2d_infer(x, p1, C, 3, 1, 1, 1, relu=True)
@@ -206,7 +175,7 @@ class ConvLSTM(nn.Module):
         pad = kernel_size // 2
         self.Gates = nn.Conv2d(input_size + hidden_size, 4 * hidden_size, kernel_size, padding=pad)
         self._pw = engine.PackedWeight()
-        self._pw_fused = {}
+        self._pw_gates, self._pw_gates_x = engine.PackedWeight(), engine.PackedWeight()
         self._pw32, self._pw32_x = engine.PackedWeightF32(), engine.PackedWeightF32()
 
     def step_f32(self, state):
@@ -235,23 +204,14 @@ class ConvLSTM(nn.Module):
         cur = state['cur']
         xh = state['xh'][cur]
         k, pad = g.kernel_size[0], g.padding[0]
-        pw = self._pw_fused
-        key = (g.weight._version, g.bias._version)
-        if pw.get('key') != key:
-            with torch.no_grad():
-                pw['packed'] = hip.pack_conv_weight(g.weight, flip=2)
-                pw['bias'] = g.bias.detach().float().contiguous()
-            pw['key'] = key
-        h_view = state['xh'][1 - cur][:, self.input_size:]
+        pw = self._pw_gates.get(g.weight, g.bias, layout='gates')
+        h_view = engine.nhwc(state['xh'][1 - cur][:, self.input_size:])
         if state['fresh']:
             # first sub-window: h_prev = 0 and c_prev = 0 (submodules.py:190-198), so the h half of the Gates
             # reduction contributes nothing -> convolve the x half only (half the K loop), same cell update
-            if pw.get('packed_x') is None or pw.get('key_x') != key:
-                with torch.no_grad():
-                    pw['packed_x'] = hip.pack_conv_weight(g.weight[:, :self.input_size], flip=2)
-                pw['key_x'] = key
-            return (engine.nhwc(xh[:, :self.input_size]), pw['packed_x'], pw['bias'], state['cell'], engine.nhwc(h_view), k, pad, True)
-        return (engine.nhwc(xh), pw['packed'], pw['bias'], state['cell'], engine.nhwc(h_view), k, pad, False)
+            pwx = self._pw_gates_x.get(g.weight, g.bias, layout='gates', cin=self.input_size)
+            return (engine.nhwc(xh[:, :self.input_size]), pwx.packed, pw.bias, state['cell'], h_view, k, pad, True)
+        return (engine.nhwc(xh), pw.packed, pw.bias, state['cell'], h_view, k, pad, False)
 
     def w128_ok(self, B, H, W):
         """Geometry rule of oess_convlstm_w128_group_bf16 (include/oess.h): 3 x 3 / pad 1 Gates, 64-channel multiples, a 256-pixel tile
@@ -309,12 +269,16 @@ class RecurrentConvLayer(nn.Module):
         self.conv = ConvLayer(in_channels, out_channels, kernel_size, stride, padding, activation, norm)
         self.recurrent_block = ConvLSTM(input_size=out_channels, hidden_size=out_channels, kernel_size=3)
 
-    def new_state(self, x):
+    def _state_shape(self, x):
+        """(B, Ho, Wo, Co) of the encoder conv's output for the input x."""
         B, _, H, W = x.shape
         c = self.conv.conv2d
         Ho = (H + 2 * c.padding[0] - c.kernel_size[0]) // c.stride[0] + 1
         Wo = (W + 2 * c.padding[0] - c.kernel_size[0]) // c.stride[0] + 1
-        Co = c.out_channels
+        return B, Ho, Wo, c.out_channels
+
+    def new_state(self, x):
+        B, Ho, Wo, Co = self._state_shape(x)
         # fused ConvLSTM path: the first step convolves the x half only (zero state) and every later read of a cat(x, h) buffer
         # follows the encoder conv's write of its x half and the previous step's write of its h half -> no zero fill needed
         # (6 fills of up to 157 MB per pre-training step); the conv + gate-kernel path reads h_prev = 0 from the buffer itself
@@ -337,7 +301,7 @@ class RecurrentConvLayer(nn.Module):
                 and m.norm != 'IN' and not (m.norm == 'BN' and m.norm_layer.training) and x.shape[1] % 32 == 0
                 and c.out_channels % 64 == 0 and x.dtype == torch.bfloat16 and x.stride(1) == 1):
             return None
-        pw = m._pw.get(c.weight, c.bias, m.norm_layer if m.norm == 'BN' else None, cin_pad=x.shape[1])
+        pw = m._packed(x.shape[1])
         out = state['xh'][state['cur']][:, :c.out_channels]
         return (engine.nhwc(x), pw.packed, pw.bias, c.out_channels, m.activation_name == 'relu', engine.nhwc(out))
 
@@ -350,11 +314,7 @@ class RecurrentConvLayer(nn.Module):
     def new_state_f32(self, x):
         """State of the fp32 path: one cat(x, h) buffer fp32 [B, Ho, Wo, 2 C] (x half written by the encoder conv, h half by the
         ConvLSTM step), the cell fp32 [B, Ho, Wo, C], 'fresh' = no previous state; 'precision' tells it from a bf16 state."""
-        B, _, H, W = x.shape
-        c = self.conv.conv2d
-        Ho = (H + 2 * c.padding[0] - c.kernel_size[0]) // c.stride[0] + 1
-        Wo = (W + 2 * c.padding[0] - c.kernel_size[0]) // c.stride[0] + 1
-        Co = c.out_channels
+        B, Ho, Wo, Co = self._state_shape(x)
         return {'precision': 'fp32', 'xh': torch.empty((B, Ho, Wo, 2 * Co), dtype=torch.float32, device=x.device),
                 'cell': torch.empty((B, Ho, Wo, Co), dtype=torch.float32, device=x.device), 'fresh': True}
 

@@ -2,9 +2,13 @@
 The residual blocks, decoders and prediction layer are constructed (identical state_dict) but not
 executed: the hot path only consumes `latent` (unet.py:163), exactly as the reference's callers do
 (`_, _, latent = update_reconstruction(...)`, pretrain_trainer.py:441)."""
+import contextlib
+
+import torch
 import torch.nn as nn
 
-from .submodules import ConvLayer, RecurrentConvLayer, ResidualBlock, TransposedConvLayer, UpsampleConvLayer
+from ... import engine, hip
+from .submodules import ConvLayer, RecurrentConvLayer, ResidualBlock, TransposedConvLayer, UpsampleConvLayer, check_runs
 
 
 class _SkewStates(list):
@@ -34,6 +38,11 @@ def check_states(prev_states, precision):
         if got is not None and got != precision:
             raise ValueError(f"E2VID state of level {i} is {got}, this step runs in {precision}: states do not carry over between "
                              "precisions (start a new sequence)")
+
+
+def _latents(head, blocks):
+    """The latents by downsampling factor (unet.py:163): {1: head output, 2: encoder 0's hidden state, 4: encoder 1's, ...}."""
+    return {1: head, **{2 ** (i + 1): b for i, b in enumerate(blocks)}}
 
 
 class UNetRecurrent(nn.Module):
@@ -69,7 +78,7 @@ class UNetRecurrent(nn.Module):
         """The head + encoder-0 conv pair that oess_e2vid_head_enc0_bf16 takes: 8 padded input channels, 5x5 stride-1 head to 32
         channels, 5x5 stride-2 encoder conv 32 -> 64, ReLU / no activation, no InstanceNorm (BatchNorm is folded when in eval)."""
         h, e = self.head, self.encoders[0].conv
-        ok = x.is_cuda and x.shape[1] == 8 and x.dtype == __import__('torch').bfloat16
+        ok = x.is_cuda and x.shape[1] == 8 and x.dtype == torch.bfloat16
         for m, cin, cout, st in ((h, None, 32, 1), (e, 32, 64, 2)):
             c = m.conv2d
             ok = ok and c.kernel_size == (5, 5) and c.stride == (st, st) and c.padding == (2, 2) and c.out_channels == cout \
@@ -77,16 +86,19 @@ class UNetRecurrent(nn.Module):
                 and not (m.norm == 'BN' and m.norm_layer.training)
         return ok and h.conv2d.in_channels <= 8
 
+    def _fuses_head_enc0(self, x, need_head, raw, reconstruct=False):
+        """True when this call runs head + encoder-0 conv as ONE kernel (_head_enc0): the caller hands raw events, or nobody reads
+        the head output (no latents wanted, no prediction layer to skip-connect it to) and the pair fits the kernel."""
+        return raw is not None or (not need_head and not reconstruct and self._head_enc0_fusable(x))
+
     def _head_enc0(self, x, prev_state, raw=None):
         """Encoder 0's conv output straight from the voxel slice (the 32-channel head output is never written): fills the x half
         of the level-0 cat(x, h) buffer and returns the state.  raw = (events fp32 [B, Ctot, H, W], c0, cs, normalize): the slice is
         normalised and packed inside the kernel as well (x is not needed)."""
-        from ... import engine, hip
         h, e = self.head, self.encoders[0]
         state = prev_state if prev_state is not None else e.new_state(raw[0] if raw is not None else x)
-        pwh = h._pw.get(h.conv2d.weight, h.conv2d.bias, h.norm_layer if h.norm == 'BN' else None, cin_pad=8)
         ec = e.conv
-        pwe = ec._pw.get(ec.conv2d.weight, ec.conv2d.bias, ec.norm_layer if ec.norm == 'BN' else None, cin_pad=32)
+        pwh, pwe = h._packed(8), ec._packed(32)
         out = engine.nhwc(state['xh'][state['cur']][:, :64])
         if raw is not None:
             ev, c0, cs, normalize = raw
@@ -100,7 +112,6 @@ class UNetRecurrent(nn.Module):
     def events_fusable(self, events, cs):
         """True when `forward(None, ..., need_head=False, raw=(events, c0, cs, normalize))` may replace EventPreprocessor + NHWC8
         re-layout + head + encoder-0 conv by one kernel."""
-        import torch
         if not (events.is_cuda and events.dtype == torch.float32 and events.is_contiguous() and events.ndim == 4 and 0 < cs <= 5):
             return False
         probe = torch.empty((1, 8, 1, 1), dtype=torch.bfloat16, device=events.device)
@@ -109,7 +120,6 @@ class UNetRecurrent(nn.Module):
     def _lstm_stage(self, st, levels):
         """The ConvLSTM steps of `levels` (independent of each other on the skewed schedule) as ONE launch when they all take the
         fused kernel, else one by one; st.out[l] = the new hidden state, st.ready[l] = the same view as level l + 1's next input."""
-        from ... import hip
         if len(levels) > 3:                                  # the grouped launch takes three problems (num_encoders = 4 variants)
             self._lstm_stage(st, levels[:3])
             self._lstm_stage(st, levels[3:])
@@ -143,7 +153,7 @@ class UNetRecurrent(nn.Module):
         deeper levels trail by l sub-windows until a call with need_head=True (the caller wants latents) drains them."""
         n = self.num_encoders
         st = prev_states if isinstance(prev_states, _SkewStates) else _SkewStates(prev_states, n)
-        fuse = raw is not None or (not need_head and self._head_enc0_fusable(x))
+        fuse = self._fuses_head_enc0(x, need_head, raw)
 
         levels = self._deeper_convs(st)
         head = None
@@ -153,17 +163,13 @@ class UNetRecurrent(nn.Module):
             head = self.head(x)
             st[0] = self.encoders[0].run_conv(head, st[0])
         self._lstm_stage(st, levels + [0])
-        latent = {1: head}
         if need_head:
             self._drain(st)
-            for i in range(n):
-                latent[2 ** (i + 1)] = st.out[i]
-        return None, st, latent
+        return None, st, _latents(head, st.out if need_head else [])
 
     def _deeper_convs(self, st):
         """Encoder convs of the levels whose input arrived from the level above in the last call (independent of each other: level
         l reads h_{l-1}, writes the x half of its own cat buffer); two stride-2 convs go out as ONE launch.  Returns the levels."""
-        from ... import hip
         n = self.num_encoders
         levels = [l for l in range(n - 1, 0, -1) if st.ready[l - 1] is not None]
         for l in levels:
@@ -201,42 +207,29 @@ class UNetRecurrent(nn.Module):
             prev_states = list(prev_states)
         if prev_states is None:
             prev_states = [None] * self.num_encoders
-        blocks, states = [], []
-        if wavefront is not None and not reconstruct:
-            import torch
-            fuse = raw is not None or (not need_head and self._head_enc0_fusable(x))
-            head = None
-            if not fuse:
-                with torch.cuda.stream(wavefront.streams[0]):
-                    x = self.head(x)
-                head = x
-            for i, encoder in enumerate(self.encoders):
-                with torch.cuda.stream(wavefront.streams[i]):
-                    wavefront.before_conv(i)
-                    state = self._head_enc0(x, prev_states[0], raw) if (fuse and i == 0) else encoder.run_conv(x, prev_states[i])
-                    wavefront.after_conv(i)
-                    wavefront.before_lstm(i)
-                    x = encoder.recurrent_block.step(state)
-                    wavefront.after_lstm(i)
-                blocks.append(x)
-                states.append(state)
-        else:
-            fuse = raw is not None or (not need_head and not reconstruct and self._head_enc0_fusable(x))
-            head = None
-            if not fuse:
+        # wavefront (training path only): level i runs on its own stream between the schedule's event hooks (wavefront.py)
+        wf = None if reconstruct else wavefront
+        on_level = (lambda i: contextlib.nullcontext()) if wf is None else (lambda i: torch.cuda.stream(wf.streams[i]))
+        fuse = self._fuses_head_enc0(x, need_head, raw, reconstruct)
+        head = None
+        if not fuse:
+            with on_level(0):
                 x = self.head(x)
-                head = x
-            for i, encoder in enumerate(self.encoders):
-                if fuse and i == 0:
-                    state = self._head_enc0(x, prev_states[0], raw)
-                    x = encoder.recurrent_block.step(state)
-                else:
-                    x, state = encoder(x, prev_states[i])
-                blocks.append(x)
-                states.append(state)
-        latent = {1: head}
-        for i, b in enumerate(blocks):
-            latent[2 ** (i + 1)] = b
+            head = x
+        blocks, states = [], []
+        for i, encoder in enumerate(self.encoders):
+            with on_level(i):
+                if wf is not None:
+                    wf.before_conv(i)
+                state = self._head_enc0(x, prev_states[0], raw) if (fuse and i == 0) else encoder.run_conv(x, prev_states[i])
+                if wf is not None:
+                    wf.after_conv(i)
+                    wf.before_lstm(i)
+                x = encoder.recurrent_block.step(state)
+                if wf is not None:
+                    wf.after_lstm(i)
+            blocks.append(x)
+            states.append(state)
         img = None
         if reconstruct:
             if self.skip_type != 'sum':
@@ -245,18 +238,13 @@ class UNetRecurrent(nn.Module):
                 x = resblock(x)
             for i, decoder in enumerate(self.decoders):
                 x = decoder(x + blocks[self.num_encoders - i - 1])           # apply_skip_connection = skip_sum
-            import torch
-            from ... import engine
-            p = self.pred
-            pw = p._pw.get(p.conv2d.weight, p.conv2d.bias, p.norm_layer if p.norm == 'BN' else None, cin_pad=x.shape[1])
-            logits = engine.conv2d_infer(x + head, pw, 1, 1, 1, 0, 1, out_f32=True)     # 32 -> 1, fp32 output
+            logits = engine.conv2d_infer(x + head, self.pred._packed(x.shape[1]), 1, 1, 1, 0, 1, out_f32=True)     # 32 -> 1, fp32 output
             img = torch.sigmoid(logits.float())
-        return img, states, latent
+        return img, states, _latents(head, blocks)
 
     def check_fp32(self):
         """The configurations forward_fp32 runs: norm None / 'BN' (eval), skip_type 'sum'; raises otherwise (before any launch)."""
-        if self.norm == 'IN':
-            raise NotImplementedError("norm='IN' E2VID variants are not on the fp32 path")
+        check_runs(self.norm, None)
         if self.skip_type != 'sum':
             raise NotImplementedError("E2VID checkpoints use skip_type 'sum'")
 
@@ -267,7 +255,7 @@ class UNetRecurrent(nn.Module):
         outputs are the hidden-state halves of the states' cat(x, h) buffers: the next step overwrites them), states are fp32."""
         self.check_fp32()
         check_states(prev_states, 'fp32')
-        if x.dtype != __import__('torch').float32 or x.ndim != 4 or x.shape[1] != self.num_input_channels:
+        if x.dtype != torch.float32 or x.ndim != 4 or x.shape[1] != self.num_input_channels:
             raise ValueError(f"forward_fp32 needs an fp32 [B, {self.num_input_channels}, H, W] tensor")
         if prev_states is None:
             prev_states = [None] * self.num_encoders
@@ -283,7 +271,4 @@ class UNetRecurrent(nn.Module):
         for i, decoder in enumerate(self.decoders):
             x = decoder.forward_f32(x, skip=blocks[self.num_encoders - i - 1])       # decoder(skip_sum(x, block)), summed on load
         img = self.pred.forward_f32(x, x2=head, act='sigmoid')                      # sigmoid(pred(skip_sum(x, head)))
-        latent = {1: head}
-        for i, b in enumerate(blocks):
-            latent[2 ** (i + 1)] = b
-        return img, states, latent
+        return img, states, _latents(head, blocks)

@@ -48,9 +48,33 @@ def zeros_cl(B, C, H, W, device, dtype=torch.bfloat16):
     return from_nhwc(torch.zeros((B, H, W, C), dtype=dtype, device=device))
 
 
+def fold_bn(w, b, bn, cout_dim=0):
+    """Fold an eval-mode BatchNorm2d, y = gamma * (conv(x) - mu) / sqrt(var + eps) + beta, into (weight, bias) in w's dtype.
+    cout_dim: the weight's output-channel dimension (0: Conv2d, 1: ConvTranspose2d).  bn None: (w, b) unchanged."""
+    if bn is None:
+        return w, b
+    scale = bn.weight.detach().to(w.dtype) / torch.sqrt(bn.running_var.detach().to(w.dtype) + bn.eps)
+    w = w * (scale[None, :, None, None] if cout_dim == 1 else scale[:, None, None, None])
+    b0 = torch.zeros_like(scale) if b is None else b
+    return w, (b0 - bn.running_mean.detach().to(w.dtype)) * scale + bn.bias.detach().to(w.dtype)
+
+
+def param_versions(weight, bias=None, bn=None):
+    """Cache key of everything a folded operand is computed from: the parameters' (and BatchNorm buffers') version counters."""
+    return (weight._version, None if bias is None else bias._version,
+            None if bn is None else (bn.weight._version, bn.bias._version, bn.running_mean._version, bn.running_var._version))
+
+
+_PACK_FLIP = {'forward': False, 'transposed': True, 'gates': 2}      # PackedWeight layout -> hip.pack_conv_weight(flip=...)
+
+
 class PackedWeight:
     """bf16 packed operand of a conv weight (optionally with an eval-mode BatchNorm folded in),
-    cached per (parameter versions).
+    cached per (parameter versions, layout, channel slice / padding).
+
+    layout: 'forward' (Conv2d weight), 'transposed' (ConvTranspose2d weight [Cin, Cout, k, k] as the data-gradient operator of
+    the strided conv it transposes; BatchNorm scale over dim 1) or 'gates' (ConvLSTM gate-interleaved rows, hip.convlstm_fused).
+    cin: keep only the first `cin` input channels (the x half of a ConvLSTM Gates weight, for a step from a zero state).
 
     Group refresh: after an optimiser step EVERY trainable conv weight of a model is stale at once, and packing them one by one
     is ~125 launches of ~6 us per frame2recon step (53 forward operands, 53 data-gradient operands, ...).  Plain weights
@@ -123,14 +147,14 @@ class PackedWeight:
                                                                  torch.cuda.current_stream(dev).cuda_stream), "oess_conv2d_pack_weight_multi")
         for pw, w in members:
             b = pw._bref() if pw._bref is not None else None
-            pw.key = (w._version, None if b is None else b._version, None, pw.key[3])
+            pw.key = param_versions(w, b) + pw.key[3:]
             pw._w_for_flip = w.detach()
         return len(rows[0]) + len(rows[1])
 
-    def get(self, weight, bias=None, bn=None, need_flip=False, cin_pad=None, ver=None):
-        key = (weight._version if ver is None else ver, None if bias is None else bias._version,
-               None if bn is None else (bn.weight._version, bn.bias._version, bn.running_mean._version,
-                                        bn.running_var._version), cin_pad)
+    def get(self, weight, bias=None, bn=None, need_flip=False, cin_pad=None, ver=None, layout='forward', cin=None):
+        key = param_versions(weight, bias, bn) + (cin_pad, layout, cin)
+        if ver is not None:
+            key = (ver,) + key[1:]
         if PackedWeight.group_enabled and key != self.key and self.packed is not None and self._wref is not None and self._wref() is weight and \
                 self.key is not None and self.key[2:] == key[2:]:
             PackedWeight.refresh_stale(weight.device)   # this operand and every other stale registered one of its device, in one launch
@@ -138,21 +162,20 @@ class PackedWeight:
                 self.key = key                      # (bias version: the fp32 bias tensor shares the parameter's storage)
         if key != self.key:
             with torch.no_grad():
-                w = weight.detach().float()
-                b = None if bias is None else bias.detach().float()
-                if bn is not None:     # y = gamma*(conv(x)-mu)/sqrt(var+eps)+beta  (BatchNorm2d in eval mode)
-                    scale = bn.weight.detach().float() / torch.sqrt(bn.running_var.detach().float() + bn.eps)
-                    w = w * scale[:, None, None, None]
-                    b0 = torch.zeros_like(scale) if b is None else b
-                    b = (b0 - bn.running_mean.detach().float()) * scale + bn.bias.detach().float()
+                w, b = fold_bn(weight.detach().float(), None if bias is None else bias.detach().float(), bn,
+                               1 if layout == 'transposed' else 0)
+                if cin is not None:
+                    w = w[:, :cin]
                 if cin_pad is not None and cin_pad != w.shape[1]:
                     w = F.pad(w, (0, 0, 0, 0, 0, cin_pad - w.shape[1]))
-                self.packed = hip.pack_conv_weight(w)
+                self.packed = hip.pack_conv_weight(w, flip=_PACK_FLIP[layout])
                 self.packed_flip = None
                 self._w_for_flip = w
                 self.bias = None if b is None else b.contiguous()
-                # plain weights join the group refresh: the operand is a pure function of the parameter's own storage
-                plain = (ver is None and bn is None and weight.dtype == torch.float32 and weight.is_contiguous() and weight.is_cuda
+                # plain weights join the group refresh (which packs the forward layout only): the operand is a pure function
+                # of the parameter's own storage
+                plain = (ver is None and bn is None and layout == 'forward' and cin is None
+                         and weight.dtype == torch.float32 and weight.is_contiguous() and weight.is_cuda
                          and w.data_ptr() == weight.data_ptr() and weight.requires_grad
                          and weight.shape[0] % 8 == 0 and weight.shape[1] % 8 == 0
                          and (bias is None or (bias.dtype == torch.float32 and bias.is_contiguous())))
@@ -179,18 +202,10 @@ class PackedWeightF32:
         self.bias = None
 
     def get(self, weight, bias=None, bn=None, transposed=False, cin=None):
-        key = (weight._version, None if bias is None else bias._version,
-               None if bn is None else (bn.weight._version, bn.bias._version, bn.running_mean._version, bn.running_var._version),
-               transposed, cin)
+        key = param_versions(weight, bias, bn) + (transposed, cin)
         if key != self.key:
             with torch.no_grad():
-                w = weight.detach().double()
-                b = None if bias is None else bias.detach().double()
-                if bn is not None:     # y = gamma * (conv(x) - mu) / sqrt(var + eps) + beta  (BatchNorm2d in eval mode)
-                    scale = bn.weight.detach().double() / torch.sqrt(bn.running_var.detach().double() + bn.eps)
-                    w = w * (scale[None, :, None, None] if transposed else scale[:, None, None, None])
-                    b0 = torch.zeros_like(scale) if b is None else b
-                    b = (b0 - bn.running_mean.detach().double()) * scale + bn.bias.detach().double()
+                w, b = fold_bn(weight.detach().double(), None if bias is None else bias.detach().double(), bn, 1 if transposed else 0)
                 if cin is not None:
                     w = w[:, :cin]
                 w = w.float()
