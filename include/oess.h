@@ -35,7 +35,7 @@ typedef void* oess_stream_t; /* hipStream_t */
 /* Library / device identification.  OESS_ABI_VERSION is bumped whenever a signature of this header changes or an entry point
  * is removed; oess_abi_version() returns the value the library was built with and the ctypes binding (openess_amd/_lib.py,
  * ABI_VERSION) refuses a library whose value differs. */
-#define OESS_ABI_VERSION 12
+#define OESS_ABI_VERSION 13
 int oess_abi_version(void);
 const char* oess_build_info(void);           /* "liboess <ver> gfx950 hipcc <ver>" */
 const char* oess_strerror(int code);
@@ -236,8 +236,52 @@ int oess_conv2d_fwd_bf16(const void* in, long long in_pix_stride, int B, int H, 
  * summation order of the fp32 accumulators). */
 size_t oess_conv2d_fwd_workspace_bytes(int B, int H, int W, int Cin, int Cout, int R, int S, int stride, int pad, int dil,
                                        int with_tile_stats, int out_is_f32);
+/* Which kernel a call takes.  oess_conv2d_fwd_bf16 is one entry point over the kernels below; the choice depends on the geometry,
+ * the epilogue flags, the pixel strides, the output pointer's 16-byte alignment and the workspace on offer.
+ * oess_conv2d_fwd_route runs the launch's own walk of the dispatch rules up to the launch site and returns the OESS_ROUTE_*
+ * value found there instead of launching.  Host only: no launch, no attribute call, no allocation; the one runtime call is the
+ * rules' query of the device's CU count, which falls back to 256 without a GPU (so the query runs on any machine, and the
+ * w128 rules answer for the current device).  The OESS_W128_* environment knobs of the launch apply to the query as well.  Negative = OESS_E*, as the launch would return.  Split-K routes carry the slice count:
+ * route = OESS_ROUTE_SPLITK_* | ks << 8; OESS_ROUTE_KERNEL(route) strips it.  oess_convlstm_fused_route is the same query for
+ * oess_convlstm_fused_bf16.  Values are stable: new kernels append, OESS_ROUTE_COUNT grows. */
+#define OESS_ROUTE_SMALLCIN 1          /* conv_smallcin_kernel<5, 5>: Cin = 8 stencil (E2VID head)                         */
+#define OESS_ROUTE_FALLBACK_128 2      /* conv_fwd_kernel<128>: register-staged, no LDS-DMA (input >= 2 GiB, K >= 32768)   */
+#define OESS_ROUTE_FALLBACK_64 3       /* conv_fwd_kernel<64>                                                              */
+#define OESS_ROUTE_FALLBACK_32 4       /* conv_fwd_kernel<32>                                                              */
+#define OESS_ROUTE_S2_HALO 5           /* conv5x5s2_halo_kernel<false>: 5x5 stride-2 pad-2                                 */
+#define OESS_ROUTE_SMALLMAP_RING 6     /* conv_fwd_dma_kernel<128, 128, 4, true, 0, 512>: small maps, 4-deep ring          */
+#define OESS_ROUTE_CONV3X3_W128 7      /* conv3x3_w128_kernel: persistent 3x3 in front of a BatchNorm                      */
+#define OESS_ROUTE_HALO3X3 8           /* conv3x3_halo_kernel<0>: 3x3 'same' row-halo                                      */
+#define OESS_ROUTE_HALO3X3_LSTM 9      /* conv3x3_halo_kernel<1>: the same with the fused ConvLSTM epilogue                */
+#define OESS_ROUTE_LSTM_FASTK 10       /* conv_fwd_dma_kernel<128, 128, 2, true, 1>: fused ConvLSTM, other geometries      */
+#define OESS_ROUTE_LSTM_SLOWK 11       /* conv_fwd_dma_kernel<128, 128, 2, false, 1>                                       */
+#define OESS_ROUTE_SPLITK_FASTK 12     /* conv_fwd_dma_kernel<128, 128, 2, true> over ks slices + splitk_reduce_kernel     */
+#define OESS_ROUTE_SPLITK_SLOWK 13     /* conv_fwd_dma_kernel<128, 128, 2, false> over ks slices + splitk_reduce_kernel    */
+#define OESS_ROUTE_CONV1X1_W128 14     /* conv1x1_w128_kernel: persistent 1x1                                              */
+#define OESS_ROUTE_TILE256 15          /* conv_fwd_dma_kernel<256, 256, 2, true>                                           */
+#define OESS_ROUTE_RING32 16           /* conv_fwd_dma32_kernel<128, true, 0, 3>: K <= 256, BK = 32 ring                   */
+#define OESS_ROUTE_TILE64_FASTK 17     /* conv_fwd_dma_kernel<64, 128, 2, true>: 64-row tiles                              */
+#define OESS_ROUTE_TILE64_SLOWK 18     /* conv_fwd_dma_kernel<64, 128, 2, false>                                           */
+#define OESS_ROUTE_DMA128_FASTK 19     /* conv_fwd_dma_kernel<128, 128, 2, true>: the general kernel                       */
+#define OESS_ROUTE_DMA128_SLOWK 20     /* conv_fwd_dma_kernel<128, 128, 2, false>                                          */
+#define OESS_ROUTE_DMA64_FASTK 21      /* conv_fwd_dma_kernel<128, 64, 2, true>                                            */
+#define OESS_ROUTE_DMA64_SLOWK 22      /* conv_fwd_dma_kernel<128, 64, 2, false>                                           */
+#define OESS_ROUTE_DMA32_FASTK 23      /* conv_fwd_dma_kernel<128, 32, 2, true>                                            */
+#define OESS_ROUTE_DMA32_SLOWK 24      /* conv_fwd_dma_kernel<128, 32, 2, false>                                           */
+#define OESS_ROUTE_COUNT 24            /* kernels are 1 .. OESS_ROUTE_COUNT                                                */
+#define OESS_ROUTE_KERNEL(route) ((route) & 0xff)
+#define OESS_ROUTE_KSPLIT(route) ((route) >> 8)
+int oess_conv2d_fwd_route(int B, int H, int W, int Cin, int Cout, int R, int S, int stride, int pad, int dil, int has_bias,
+                          int relu, int has_residual, int out_is_f32, int with_tile_stats, long long in_pix_stride,
+                          long long out_pix_stride, long long res_pix_stride, int out_aligned16, size_t workspace_bytes);
+int oess_convlstm_fused_route(int B, int H, int W, int Cin, long long in_pix_stride, int C_hidden, int R, int S, int pad,
+                              long long hidden_pix_stride);
+int oess_conv2d_route_count(void);             /* == OESS_ROUTE_COUNT of the header the library was built from */
+const char* oess_conv2d_route_name(int route); /* kernel name of a route value (static string; "?" for anything else) */
 /* tile_stats (nullable): [ceil(M/128)][2][Cout] fp32, per-128-row-tile column sums and sums of squares of the fp32
- * result (BatchNorm batch statistics straight from the accumulators; bias-free, no activation/residual).
+ * result (BatchNorm batch statistics straight from the accumulators; bias-free, no activation/residual).  Every row is written.
+ * One kernel differs: OESS_ROUTE_TILE256 (256 x 256 tiles) puts the sums of its 256 rows into row 2t and zeroes row 2t + 1
+ * (where the table has it), so only the sum over rows is kernel-independent; all other routes fill genuine 128-row rows.
  * oess_norm_reduce_finalize_tile_stats turns them into mean / rstd / scale / shift. */
 
 /* Reduce + finalize (G = 1), sums and E[x^2] - E[x]^2 in double, slices added in a FIXED order (bit-repeatable):

@@ -2066,7 +2066,12 @@ int conv_fwd_impl(const void* in, long long in_pix_stride, int B, int H, int W, 
                   const void* residual, long long res_pix_stride, void* out_bf16, float* out_f32,
                   long long out_pix_stride, float* tile_stats, const LstmOut* lstm, oess_stream_t stream,
                   void* workspace = nullptr, size_t workspace_bytes = 0, size_t* want_workspace = nullptr,
-                  ConvArgs* capture = nullptr) {
+                  ConvArgs* capture = nullptr, int* route = nullptr) {
+    // route != null (oess_conv2d_fwd_route): the walk stops at the launch site it reaches and stores that site's OESS_ROUTE_*
+    // value instead of launching.  The query passes dummy host pointers, so EVERY hipLaunchKernelGGL of this function must have
+    // an OESS_ROUTE(...) in front of it (one value per template instantiation, declared in include/oess.h and pinned by a row of
+    // tests/conv_route_cases.py); the guard at the end of the function turns a forgotten one on the last path into an error.
+#define OESS_ROUTE(r) do { if (route) { *route = (r); return OESS_OK; } } while (0)
     // capture != null (ConvLSTM only): fill *capture with the launch arguments of the row-halo kernel instead of launching it;
     // OESS_EINVAL when the geometry takes another kernel (the caller then launches the problems one by one)
     if (want_workspace) *want_workspace = 0;
@@ -2107,7 +2112,7 @@ int conv_fwd_impl(const void* in, long long in_pix_stride, int B, int H, int W, 
     a.mg_w = (W >= 2 && 256ll * W < 0x100000000ll) ? (unsigned)(0x100000000ull / (unsigned)W) + 1u : 0u;
     a.mg_wd = (256ll * (W + dil) < 0x100000000ll) ? (unsigned)(0x100000000ull / (unsigned)(W + dil)) + 1u : 0u;
     hipStream_t st = (hipStream_t)stream;
-    conv_set_attrs();
+    if (!route) conv_set_attrs();           // the route query does no device work
     // The LDS-DMA kernels address the input with 32-bit buffer offsets and decode filter taps with exact small-range
     // reciprocals (verified here over the whole range); anything outside takes the register-staged generic kernel.
     const long long in_extent = (((long long)B * H * W - 1) * in_pix_stride + Cin) * 2;
@@ -2141,6 +2146,7 @@ int conv_fwd_impl(const void* in, long long in_pix_stride, int B, int H, int W, 
         !tile_stats && (out_pix_stride & 3) == 0 && a.Kpad == 256 && dma_ok) {
         if (want_workspace) return OESS_OK;
         const int tiles = B * ((a.Ho + 7) / 8) * ((a.Wo + 63) / 64);
+        OESS_ROUTE(OESS_ROUTE_SMALLCIN);
         hipLaunchKernelGGL((conv_smallcin_kernel<5, 5>), dim3(tiles < 512 ? tiles : 512), dim3(256), 0, st, a);   // persistent: 2 workgroups per CU
         OESS_HIP(hipGetLastError());
         return OESS_OK;
@@ -2151,6 +2157,7 @@ int conv_fwd_impl(const void* in, long long in_pix_stride, int B, int H, int W, 
         const size_t tab = (size_t)(a.Kpad / 8) * 8;
         size_t lds = (size_t)2 * (BM + bn) * 8 * 16 + tab;
         if (lds < epi) lds = epi;
+        OESS_ROUTE(bn == 128 ? OESS_ROUTE_FALLBACK_128 : (bn == 64 ? OESS_ROUTE_FALLBACK_64 : OESS_ROUTE_FALLBACK_32));
         if (bn == 128) hipLaunchKernelGGL(conv_fwd_kernel<128>, grid, block, lds, st, a);
         else if (bn == 64) hipLaunchKernelGGL(conv_fwd_kernel<64>, grid, block, lds, st, a);
         else hipLaunchKernelGGL(conv_fwd_kernel<32>, grid, block, lds, st, a);
@@ -2164,6 +2171,7 @@ int conv_fwd_impl(const void* in, long long in_pix_stride, int B, int H, int W, 
         a.tiles_n = Cout / 64;
         a.tiles_m = B * ((a.Ho + S2_PH - 1) / S2_PH) * ((a.Wo + S2_PW - 1) / S2_PW);
         if (capture) { *capture = a; return OESS_OK; }
+        OESS_ROUTE(OESS_ROUTE_S2_HALO);
         hipLaunchKernelGGL((conv5x5s2_halo_kernel<false>), dim3(a.tiles_m * a.tiles_n), dim3(256), S2_LDS, st, a, S2Head{});
         OESS_HIP(hipGetLastError());
         return OESS_OK;
@@ -2183,6 +2191,7 @@ int conv_fwd_impl(const void* in, long long in_pix_stride, int B, int H, int W, 
             if (want_workspace) return OESS_OK;
             size_t lds = (size_t)4 * (BM + 128) * 8 * 16;
             if (lds < epi) lds = epi;
+            OESS_ROUTE(OESS_ROUTE_SMALLMAP_RING);
             hipLaunchKernelGGL((conv_fwd_dma_kernel<128, 128, 4, true, 0, 512>), grid, dim3(512), lds, st, a);
             OESS_HIP(hipGetLastError());
             return OESS_OK;
@@ -2201,6 +2210,7 @@ int conv_fwd_impl(const void* in, long long in_pix_stride, int B, int H, int W, 
             out_extent < 0x7ffffff0ll && (long long)Cout * a.Kpad * 2 < 0x7ffffff0ll && (long long)H * W * W < 0x100000000ll) {
             if (want_workspace) return OESS_OK;
             a.tiles_m = (a.M + 255) / 256; a.tiles_n = Cout / 256;
+            OESS_ROUTE(OESS_ROUTE_CONV3X3_W128);
             hipLaunchKernelGGL(conv3x3_w128_kernel, dim3(num_cus() / 8 * 8), dim3(256), (size_t)W128_OPER, st, a);
             OESS_HIP(hipGetLastError());
             return OESS_OK;
@@ -2213,6 +2223,7 @@ int conv_fwd_impl(const void* in, long long in_pix_stride, int B, int H, int W, 
         if (want_workspace) return OESS_OK;
         if (capture) { *capture = a; return OESS_OK; }
         const size_t lds = (size_t)2 * HALO_ROWS * 128 + (size_t)2 * 128 * 128;
+        OESS_ROUTE(lstm ? OESS_ROUTE_HALO3X3_LSTM : OESS_ROUTE_HALO3X3);
         if (lstm) hipLaunchKernelGGL((conv3x3_halo_kernel<1>), grid, block, lds, st, a);
         else hipLaunchKernelGGL((conv3x3_halo_kernel<0>), grid, block, lds, st, a);
         OESS_HIP(hipGetLastError());
@@ -2222,6 +2233,7 @@ int conv_fwd_impl(const void* in, long long in_pix_stride, int B, int H, int W, 
     if (capture) return OESS_EINVAL;
     if (lstm) {
         const size_t lds = (size_t)2 * (BM + 128) * 8 * 16;
+        OESS_ROUTE(fastk ? OESS_ROUTE_LSTM_FASTK : OESS_ROUTE_LSTM_SLOWK);
         if (fastk) hipLaunchKernelGGL((conv_fwd_dma_kernel<128, 128, 2, true, 1>), grid, block, lds, st, a);
         else hipLaunchKernelGGL((conv_fwd_dma_kernel<128, 128, 2, false, 1>), grid, block, lds, st, a);
         OESS_HIP(hipGetLastError());
@@ -2251,6 +2263,7 @@ int conv_fwd_impl(const void* in, long long in_pix_stride, int B, int H, int W, 
                 a.partial = (float*)workspace; a.ksplit = best; a.kt_per = (KTall + best - 1) / best;
                 const size_t lds = (size_t)2 * (BM + 128) * 8 * 16;
                 const dim3 gridk(a.tiles_m * a.tiles_n, best);
+                OESS_ROUTE((fastk ? OESS_ROUTE_SPLITK_FASTK : OESS_ROUTE_SPLITK_SLOWK) | best << 8);
                 if (fastk) hipLaunchKernelGGL((conv_fwd_dma_kernel<128, 128, 2, true>), gridk, block, lds, st, a);
                 else hipLaunchKernelGGL((conv_fwd_dma_kernel<128, 128, 2, false>), gridk, block, lds, st, a);
                 hipLaunchKernelGGL(splitk_reduce_kernel, dim3(a.tiles_m, (Cout + 63) / 64), dim3(256), 0, st, a);
@@ -2284,6 +2297,7 @@ int conv_fwd_impl(const void* in, long long in_pix_stride, int B, int H, int W, 
             // 2 x and reducing layers lose 2-10 % with them: EXPERIMENTS R6-8).  OESS_W128_NT = 0 / 1 forces (A/B).
             static const int nt_env = [] { const char* e = getenv("OESS_W128_NT"); return e ? atoi(e) : -1; }();
             a.ksplit = nt_env >= 0 ? nt_env : (Cout >= 4 * Cin);
+            OESS_ROUTE(OESS_ROUTE_CONV1X1_W128);
             hipLaunchKernelGGL(conv1x1_w128_kernel, dim3(num_cus() / 8 * 8), dim3(256), (size_t)G128_LDS, st, a);
             OESS_HIP(hipGetLastError());
             return OESS_OK;
@@ -2296,6 +2310,7 @@ int conv_fwd_impl(const void* in, long long in_pix_stride, int B, int H, int W, 
             size_t lds = (size_t)2 * 512 * 128;                                          // 2 stages x (256 + 256) rows x 128 B
             const size_t epi256 = (size_t)256 * (256 + 8) * 2 + (size_t)4 * 256 * 2 * 4 + 256;   // output image + BatchNorm partials
             if (lds < epi256) lds = epi256;
+            OESS_ROUTE(OESS_ROUTE_TILE256);
             hipLaunchKernelGGL((conv_fwd_dma_kernel<256, 256, 2, true>), dim3(a.tiles_m * a.tiles_n), dim3(512), lds, st, a);
             OESS_HIP(hipGetLastError());
             return OESS_OK;
@@ -2307,6 +2322,7 @@ int conv_fwd_impl(const void* in, long long in_pix_stride, int B, int H, int W, 
     if (bn == 128 && fastk32 && a.Kpad <= 256) {
         size_t lds3 = (size_t)3 * (BM + 128) * 64;
         if (lds3 < epi) lds3 = epi;
+        OESS_ROUTE(OESS_ROUTE_RING32);
         hipLaunchKernelGGL((conv_fwd_dma32_kernel<128, true, 0, 3>), grid, block, lds3, st, a);
         OESS_HIP(hipGetLastError());
         return OESS_OK;
@@ -2319,6 +2335,7 @@ int conv_fwd_impl(const void* in, long long in_pix_stride, int B, int H, int W, 
         size_t lds = (size_t)2 * (64 + 128) * 8 * 16;
         const size_t epi64 = (size_t)64 * (128 + 8) * 2 + 4096;
         if (lds < epi64) lds = epi64;
+        OESS_ROUTE(fastk ? OESS_ROUTE_TILE64_FASTK : OESS_ROUTE_TILE64_SLOWK);
         if (fastk) hipLaunchKernelGGL((conv_fwd_dma_kernel<64, 128, 2, true>), grid64, block, lds, st, a);
         else hipLaunchKernelGGL((conv_fwd_dma_kernel<64, 128, 2, false>), grid64, block, lds, st, a);
         OESS_HIP(hipGetLastError());
@@ -2331,13 +2348,16 @@ int conv_fwd_impl(const void* in, long long in_pix_stride, int B, int H, int W, 
 #define OESS_LAUNCH_DMA(BN_)                                                                                  \
         if (fastk) hipLaunchKernelGGL((conv_fwd_dma_kernel<128, BN_, 2, true>), grid, block, lds, st, a);        \
         else hipLaunchKernelGGL((conv_fwd_dma_kernel<128, BN_, 2, false>), grid, block, lds, st, a);
+        OESS_ROUTE((bn == 128 ? OESS_ROUTE_DMA128_FASTK : (bn == 64 ? OESS_ROUTE_DMA64_FASTK : OESS_ROUTE_DMA32_FASTK)) + (fastk ? 0 : 1));
         if (bn == 128) { OESS_LAUNCH_DMA(128) }
         else if (bn == 64) { OESS_LAUNCH_DMA(64) }
         else { OESS_LAUNCH_DMA(32) }
 #undef OESS_LAUNCH_DMA
     }
+    if (route) return OESS_EINVAL;          // not reached: a query must have returned at an OESS_ROUTE above
     OESS_HIP(hipGetLastError());
     return OESS_OK;
+#undef OESS_ROUTE
 }
 }  // namespace
 
@@ -2361,6 +2381,48 @@ size_t oess_conv2d_fwd_workspace_bytes(int B, int H, int W, int Cin, int Cout, i
                                  out_is_f32 ? nullptr : (void*)dummy, out_is_f32 ? (float*)dummy : nullptr, (Cout + 7) / 8 * 8,
                                  with_tile_stats ? (float*)dummy : nullptr, nullptr, nullptr, nullptr, 0, &need);
     return rc == OESS_OK ? need : 0;
+}
+
+int oess_conv2d_fwd_route(int B, int H, int W, int Cin, int Cout, int R, int S, int stride, int pad, int dil, int has_bias,
+                          int relu, int has_residual, int out_is_f32, int with_tile_stats, long long in_pix_stride,
+                          long long out_pix_stride, long long res_pix_stride, int out_aligned16, size_t workspace_bytes) {
+    // the launch's own walk on dummy (never dereferenced) pointers: only their nullness and the output's alignment matter
+    alignas(16) static char dummy[32] = {0};
+    char* out = dummy + (out_aligned16 ? 0 : 8);
+    int route = 0;
+    const int rc = conv_fwd_impl(dummy, in_pix_stride, B, H, W, Cin, dummy, has_bias ? (const float*)dummy : nullptr, Cout, R, S,
+                                 stride, pad, dil, relu, has_residual ? (const void*)dummy : nullptr, res_pix_stride,
+                                 out_is_f32 ? nullptr : (void*)out, out_is_f32 ? (float*)out : nullptr, out_pix_stride,
+                                 with_tile_stats ? (float*)dummy : nullptr, nullptr, nullptr, workspace_bytes ? (void*)dummy : nullptr,
+                                 workspace_bytes, nullptr, nullptr, &route);
+    return rc == OESS_OK ? route : rc;
+}
+
+int oess_convlstm_fused_route(int B, int H, int W, int Cin, long long in_pix_stride, int C_hidden, int R, int S, int pad,
+                              long long hidden_pix_stride) {
+    alignas(16) static char dummy[32] = {0};
+    LstmOut l{nullptr, (float*)dummy, dummy, hidden_pix_stride, C_hidden};
+    int route = 0;
+    const int rc = conv_fwd_impl(dummy, in_pix_stride, B, H, W, Cin, dummy, nullptr, 4 * C_hidden, R, S, 1, pad, 1, 0, nullptr, 0,
+                                 nullptr, nullptr, 0, nullptr, &l, nullptr, nullptr, 0, nullptr, nullptr, &route);
+    return rc == OESS_OK ? route : rc;
+}
+
+int oess_conv2d_route_count(void) { return OESS_ROUTE_COUNT; }
+
+const char* oess_conv2d_route_name(int route) {
+    static const char* const names[OESS_ROUTE_COUNT + 1] = {
+        "?", "conv_smallcin_kernel<5, 5>", "conv_fwd_kernel<128>", "conv_fwd_kernel<64>", "conv_fwd_kernel<32>",
+        "conv5x5s2_halo_kernel<false>", "conv_fwd_dma_kernel<128, 128, 4, true, 0, 512>", "conv3x3_w128_kernel",
+        "conv3x3_halo_kernel<0>", "conv3x3_halo_kernel<1>", "conv_fwd_dma_kernel<128, 128, 2, true, 1>",
+        "conv_fwd_dma_kernel<128, 128, 2, false, 1>", "split-K conv_fwd_dma_kernel<128, 128, 2, true> + splitk_reduce_kernel",
+        "split-K conv_fwd_dma_kernel<128, 128, 2, false> + splitk_reduce_kernel", "conv1x1_w128_kernel",
+        "conv_fwd_dma_kernel<256, 256, 2, true>", "conv_fwd_dma32_kernel<128, true, 0, 3>", "conv_fwd_dma_kernel<64, 128, 2, true>",
+        "conv_fwd_dma_kernel<64, 128, 2, false>", "conv_fwd_dma_kernel<128, 128, 2, true>", "conv_fwd_dma_kernel<128, 128, 2, false>",
+        "conv_fwd_dma_kernel<128, 64, 2, true>", "conv_fwd_dma_kernel<128, 64, 2, false>", "conv_fwd_dma_kernel<128, 32, 2, true>",
+        "conv_fwd_dma_kernel<128, 32, 2, false>"};
+    const int k = OESS_ROUTE_KERNEL(route);        // a split-K slice count in the upper bits does not change the name
+    return route > 0 && k >= 1 && k <= OESS_ROUTE_COUNT ? names[k] : names[0];
 }
 
 int oess_convlstm_fused_bf16(const void* in, long long in_pix_stride, int B, int H, int W, int Cin, const void* w_packed_gates,

@@ -560,6 +560,37 @@ def pack_conv_weight(w, flip=False):
     return packed
 
 
+def _conv_marshal(x, Cout, R, S, stride, pad, dil, residual, out, out_f32, tile_stats, allow_splitk, alloc):
+    """The arguments of oess_conv2d_fwd_bf16 that conv2d_nhwc derives from its tensors, shared with conv2d_route so that the
+    query describes the call exactly: (B, H, W, Cin, ps_in, out, is_f32, ps_out, ps_res, workspace bytes to offer).
+    alloc=False (the query) leaves a missing output unallocated: it would be dense and 16-byte aligned."""
+    B, H, W, Cin, ps_in = _nhwc_geom(x)
+    Ho = (H + 2 * pad - dil * (R - 1) - 1) // stride + 1
+    Wo = (W + 2 * pad - dil * (S - 1) - 1) // stride + 1
+    if out is None and alloc:
+        out = torch.empty((B, Ho, Wo, Cout), dtype=torch.float32 if out_f32 else torch.bfloat16, device=x.device)
+    if out is None:
+        is_f32, ps_out = bool(out_f32), Cout
+    else:
+        is_f32 = out.dtype == torch.float32
+        if is_f32:
+            if out.stride(3) != 1:
+                raise ValueError("fp32 output must have dense channels")
+            ps_out = out.stride(2)
+        else:
+            ps_out = _nhwc_geom(out)[4]
+        if tuple(out.shape) != (B, Ho, Wo, Cout):
+            raise ValueError(f"bad output shape {tuple(out.shape)} != {(B, Ho, Wo, Cout)}")
+    ps_res = 0
+    if residual is not None:
+        ps_res = _nhwc_geom(residual)[4]
+    key = (B, H, W, Cin, Cout, R, S, stride, pad, dil, tile_stats is not None, is_f32)
+    need = _CONV_WS_NEED.get(key)
+    if need is None:       # host-only query of the dispatch rules (split-K layers want fp32 slice scratch), cached per geometry
+        need = _CONV_WS_NEED[key] = _lib.load().oess_conv2d_fwd_workspace_bytes(*key[:10], int(key[10]), int(key[11]))
+    return B, H, W, Cin, ps_in, out, is_f32, ps_out, ps_res, (need if allow_splitk else 0)
+
+
 def conv2d_nhwc(x, packed, bias, Cout, R, S, stride=1, pad=0, dil=1, relu=False, residual=None, out=None,
                 out_f32=False, tile_stats=None, allow_splitk=True):
     """out = act(conv(x, w) + bias [+ residual]) on NHWC bf16 views (channel slices of wider buffers are fine).
@@ -567,31 +598,13 @@ def conv2d_nhwc(x, packed, bias, Cout, R, S, stride=1, pad=0, dil=1, relu=False,
     allow_splitk=False withholds the scratch of the split-K form (small-M / long-K layers): one pass, for A/B tests."""
     lib = _lib.load()
     _need_gpu(x, packed)
-    B, H, W, Cin, ps_in = _nhwc_geom(x)
-    Ho = (H + 2 * pad - dil * (R - 1) - 1) // stride + 1
-    Wo = (W + 2 * pad - dil * (S - 1) - 1) // stride + 1
-    if out is None:
-        out = torch.empty((B, Ho, Wo, Cout), dtype=torch.float32 if out_f32 else torch.bfloat16, device=x.device)
-    if out.dtype == torch.float32:
-        if out.stride(3) != 1:
-            raise ValueError("fp32 output must have dense channels")
-        ps_out, o_bf16, o_f32 = out.stride(2), None, _ptr(out)
-    else:
-        _, _, _, _, ps_out = _nhwc_geom(out)
-        o_bf16, o_f32 = _ptr(out), None
-    if tuple(out.shape) != (B, Ho, Wo, Cout):
-        raise ValueError(f"bad output shape {tuple(out.shape)} != {(B, Ho, Wo, Cout)}")
-    ps_res = 0
-    if residual is not None:
-        _, _, _, _, ps_res = _nhwc_geom(residual)
+    B, H, W, Cin, ps_in, out, is_f32, ps_out, ps_res, need = _conv_marshal(x, Cout, R, S, stride, pad, dil, residual, out, out_f32,
+                                                                           tile_stats, allow_splitk, True)
+    o_bf16, o_f32 = (None, _ptr(out)) if is_f32 else (_ptr(out), None)
     if bias is not None and (bias.dtype != torch.float32 or not bias.is_contiguous()):
         bias = bias.float().contiguous()
     ws, wsn = None, 0
-    key = (B, H, W, Cin, Cout, R, S, stride, pad, dil, tile_stats is not None, o_f32 is not None)
-    need = _CONV_WS_NEED.get(key)
-    if need is None:       # host-only query of the dispatch rules (split-K layers want fp32 slice scratch), cached per geometry
-        need = _CONV_WS_NEED[key] = lib.oess_conv2d_fwd_workspace_bytes(*key[:10], int(key[10]), int(key[11]))
-    if need and allow_splitk:
+    if need:
         ws = _workspace(need, x.device, tag=("conv_splitk", torch.cuda.current_stream(x.device).cuda_stream))
         wsn = ws.numel()
     _lib.check(lib.oess_conv2d_fwd_bf16(_ptr(x), ps_in, B, H, W, Cin, _ptr(packed), _ptr(bias), Cout, R, S, stride, pad,
@@ -599,6 +612,54 @@ def conv2d_nhwc(x, packed, bias, Cout, R, S, stride=1, pad=0, dil=1, relu=False,
                                         _ptr(ws), wsn, _stream()),
                "oess_conv2d_fwd_bf16")
     return out
+
+
+def conv2d_route(x, packed, bias, Cout, R, S, stride=1, pad=0, dil=1, relu=False, residual=None, out=None,
+                 out_f32=False, tile_stats=None, allow_splitk=True, in_pix_stride=None, out_pix_stride=None,
+                 res_pix_stride=None, out_aligned16=True):
+    """The kernel conv2d_nhwc would launch for these arguments: an OESS_ROUTE_* value of include/oess.h (split-K carries its
+    slice count: route & 0xff is the kernel, route >> 8 is ks); raises where the call would.  Host only, needs no GPU.
+    With x a tensor the arguments are conv2d_nhwc's own and go through the same marshalling (_conv_marshal): strides, output
+    type, alignment and workspace are those of the call.  With x a (B, H, W, Cin) shape, bias / residual / tile_stats are
+    booleans and the *_pix_stride / out_aligned16 keywords stand in for the views (default: dense, aligned).
+    `packed` is not looked at."""
+    lib = _lib.load()
+    if torch.is_tensor(x):
+        B, H, W, Cin, ps_in, out, f32, ps_out, ps_res, need = _conv_marshal(x, Cout, R, S, stride, pad, dil, residual, out, out_f32,
+                                                                            tile_stats, allow_splitk, False)
+        has_bias, has_res, stats = bias is not None, residual is not None, tile_stats is not None
+        if out is not None:
+            out_aligned16 = out.data_ptr() % 16 == 0
+    else:
+        B, H, W, Cin = x
+        has_bias, has_res, stats, f32 = bool(bias), bool(residual), bool(tile_stats), bool(out_f32)
+        ps_in = Cin if in_pix_stride is None else in_pix_stride
+        ps_out = Cout if out_pix_stride is None else out_pix_stride
+        ps_res = (Cout if res_pix_stride is None else res_pix_stride) if has_res else 0
+        need = lib.oess_conv2d_fwd_workspace_bytes(B, H, W, Cin, Cout, R, S, stride, pad, dil, int(stats), int(f32)) if allow_splitk else 0
+    r = lib.oess_conv2d_fwd_route(B, H, W, Cin, Cout, R, S, stride, pad, dil, int(has_bias), int(relu), int(has_res), int(f32),
+                                  int(stats), ps_in, ps_out, ps_res, int(bool(out_aligned16)), need)
+    if r < 0:
+        _lib.check(r, "oess_conv2d_fwd_route")
+    return r
+
+
+def convlstm_route(xh, C, k, pad, hidden_pix_stride=None, in_pix_stride=None):
+    """conv2d_route for convlstm_fused: xh is the cat(x, h) tensor of the call or its (B, H, W, Cin) shape."""
+    lib = _lib.load()
+    if torch.is_tensor(xh):
+        B, H, W, Cin, ps = _nhwc_geom(xh)
+    else:
+        B, H, W, Cin = xh
+        ps = Cin if in_pix_stride is None else in_pix_stride
+    r = lib.oess_convlstm_fused_route(B, H, W, Cin, ps, C, k, k, pad, C if hidden_pix_stride is None else hidden_pix_stride)
+    if r < 0:
+        _lib.check(r, "oess_convlstm_fused_route")
+    return r
+
+
+def conv2d_route_name(route):
+    return _lib.load().oess_conv2d_route_name(int(route)).decode()
 
 
 def e2vid_head_enc0(x8, head_packed, head_bias, head_relu, enc_packed, enc_bias, enc_relu, out=None):

@@ -120,3 +120,44 @@ def test_product_path_refuses_cpu_tensors():
     from openess_amd import hip
     with pytest.raises(RuntimeError):
         hip.masked_normalize(torch.zeros(4, 4))
+
+
+def test_route_queries_run_on_the_host():
+    """ABI 13: oess_conv2d_fwd_route / oess_convlstm_fused_route walk the launch's dispatch rules without a device; one known
+    geometry per kernel family, and bad arguments come back as OESS_EINVAL like the launch's."""
+    from openess_amd import _lib
+    from tests.conv_route_cases import header_routes
+    lib = _lib.load()
+    R = header_routes()
+    assert lib.oess_abi_version() == 13 and lib.oess_conv2d_route_count() == len(R) == 24
+
+    def q(B, H, W, Cin, Cout, k, stride, pad, dil, bias=1, relu=0, res=0, f32=0, stats=0, ws=0, aligned=1):
+        return lib.oess_conv2d_fwd_route(B, H, W, Cin, Cout, k, k, stride, pad, dil, bias, relu, res, f32, stats, Cin, (Cout + 7) // 8 * 8,
+                                         (Cout + 7) // 8 * 8 if res else 0, aligned, ws)
+    assert q(1, 33, 47, 8, 32, 5, 1, 2, 1) == R["SMALLCIN"]                                   # E2VID head
+    assert q(2, 30, 42, 32, 64, 5, 2, 2, 1) == R["S2_HALO"]                                   # E2VID encoder
+    assert q(1, 5, 7, 4096, 136, 3, 1, 1, 1) == R["FALLBACK_128"]                             # K >= 32768
+    assert q(8, 28, 40, 1024, 256, 1, 1, 0, 1) == R["SMALLMAP_RING"]                          # DeepLabv3 OS16 1x1
+    assert q(1, 9, 20, 64, 72, 3, 1, 1, 1) == R["HALO3X3"]
+    assert q(8, 110, 160, 64, 256, 3, 1, 1, 1, bias=0, stats=1) == R["CONV3X3_W128"]
+    assert q(8, 110, 160, 256, 1024, 1, 1, 0, 1, bias=0, stats=1) == R["CONV1X1_W128"]
+    assert q(8, 110, 160, 256, 1024, 1, 1, 0, 1, res=1) == R["TILE256"]
+    assert q(8, 110, 160, 64, 256, 1, 1, 0, 1) == R["RING32"]
+    assert q(1, 9, 20, 64, 12, 3, 1, 1, 1, f32=1) == R["DMA32_FASTK"]
+    # the ASPP geometry of test_round3_...: split-K with the workspace it asks for, one pass without
+    need = lib.oess_conv2d_fwd_workspace_bytes(8, 28, 40, 2048, 256, 3, 3, 1, 12, 12, 1, 0)
+    r = q(8, 28, 40, 2048, 256, 3, 1, 12, 12, bias=0, stats=1, ws=need)
+    assert r & 0xff == R["SPLITK_FASTK"] and 2 <= r >> 8 <= 8 and need == (r >> 8) * 8960 * 256 * 4
+    assert q(8, 28, 40, 2048, 256, 3, 1, 12, 12, bias=0, stats=1, ws=need - 1) == R["DMA128_FASTK"]
+    assert lib.oess_convlstm_fused_route(1, 45, 60, 128, 128, 64, 3, 3, 1, 128) == R["HALO3X3_LSTM"]
+    assert lib.oess_convlstm_fused_route(1, 45, 60, 128, 128, 64, 5, 5, 2, 128) == R["LSTM_FASTK"]
+    assert lib.oess_conv2d_route_name(R["HALO3X3"]) == b"conv3x3_halo_kernel<0>"
+    assert lib.oess_conv2d_route_name(r).startswith(b"split-K") and lib.oess_conv2d_route_name(0) == b"?"
+    assert lib.oess_conv2d_route_name(-22) == b"?" and lib.oess_conv2d_route_name(25) == b"?"
+    # bad arguments: Cin % 8, no pixels, a residual with an fp32 output, statistics with a bias, hidden size % 32, hidden stride < C
+    assert q(1, 9, 20, 12, 72, 3, 1, 1, 1) == -22
+    assert q(0, 9, 20, 64, 72, 3, 1, 1, 1) == -22
+    assert q(1, 9, 20, 64, 72, 3, 1, 1, 1, res=1, f32=1) == -22
+    assert q(1, 9, 20, 64, 72, 3, 1, 1, 1, bias=1, stats=1) == -22
+    assert lib.oess_convlstm_fused_route(1, 45, 60, 128, 128, 48, 3, 3, 1, 128) == -22
+    assert lib.oess_convlstm_fused_route(1, 45, 60, 128, 128, 64, 3, 3, 1, 32) == -22

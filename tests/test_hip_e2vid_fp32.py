@@ -334,3 +334,162 @@ def test_fp32_repeatable_and_sync_free(g):
     finally:
         torch.cuda.set_sync_debug_mode(prev)
     torch.cuda.synchronize()
+
+
+# ------------------------------------------------------------------------------------------------ exact view / geometry surface
+# Integer operands (activations in [-2, 2], weights in {-1, 0, 1}, integer bias and residual) make every product and partial sum
+# of a v_mfma_f32_32x32x2_f32 chain an integer far below 2^24: the fp32 result is exact in any order and is compared with the
+# float64 CPU reference by torch.equal.  The bilinear x2 weights are 0, 1/4, 3/4 and 1, so upsampled integers stay exact too.
+
+def _iv(g, shape, lo=-2, hi=2):
+    return torch.randint(lo, hi + 1, shape, generator=g).float()
+
+
+def _nonzero_floors(pre, want):
+    """conditions on the reference alone, so that equality is not vacuous: at least half of the pre-activation reference is
+    non-zero, and (a ReLU zeroes the negative half of a symmetric result) at least a quarter of what is compared"""
+    assert float(want.abs().max()) < 2 ** 24
+    assert float((pre != 0).double().mean()) >= 0.5 and float((want != 0).double().mean()) >= 0.25
+
+
+def _place(t, layout):
+    """logical [B, C, H, W] CPU tensor -> CUDA tensor of the same logical shape stored as `layout`"""
+    B, C, H, W = t.shape
+    nhwc = t.permute(0, 2, 3, 1).cuda()
+    if layout == 'cl':
+        return _cl(t)
+    if layout == 'nchw':
+        return t.cuda().contiguous()
+    if layout == 'crop':            # a window of a larger NHWC map
+        big = torch.full((B, H + 5, W + 4, C), 9.0, device="cuda")
+        big[:, 2:2 + H, 3:3 + W] = nhwc
+        return big[:, 2:2 + H, 3:3 + W].permute(0, 3, 1, 2)
+    if layout == 'off4':            # dense NHWC whose base is 4 bytes off 16-byte alignment
+        v = torch.zeros(t.numel() + 1, device="cuda")[1:].view(B, H, W, C)
+        v.copy_(nhwc)
+        assert v.data_ptr() % 16 == 4
+        return v.permute(0, 3, 1, 2)
+    if layout == 'slice':           # a channel slice of a wider NHWC buffer
+        big = torch.full((B, H, W, C + 8), 9.0, device="cuda")
+        big[..., 4:4 + C] = nhwc
+        return big[..., 4:4 + C].permute(0, 3, 1, 2)
+    raise ValueError(layout)
+
+
+def _out_view(layout, B, C, H, W):
+    """(out argument, buffer to check for untouched neighbours)"""
+    if layout is None:
+        return None, None
+    if layout == 'nchw':
+        return torch.full((B, C, H, W), float("nan"), device="cuda"), None
+    big = torch.full((B, H, W, C + 8), -7.0, device="cuda")
+    return big[..., 4:4 + C].permute(0, 3, 1, 2), big
+
+
+def _neighbours_untouched(big, C):
+    return big is None or (bool((big[..., :4] == -7.0).all()) and bool((big[..., 4 + C:] == -7.0).all()))
+
+
+# (B, Cin, H, W, Cout, R, S, stride, pad, act, x layout, x2 layout, residual layout, output layout)
+EXACT_CONV_CASES = {
+    "k3x5_pad0_cin12_cout33": (2, 12, 9, 11, 33, 3, 5, 1, 0, 'relu', 'cl', None, None, None),
+    "k1x5_pad0_cin24_cout65_nchw_out": (1, 24, 7, 12, 65, 1, 5, 1, 0, None, 'cl', None, None, 'nchw'),
+    "k3x3_pad2_cin1_cout3_nchw": (2, 1, 6, 7, 3, 3, 3, 1, 2, 'relu', 'nchw', None, 'nchw', None),
+    "k5x5_pad4_cin12": (1, 12, 5, 6, 33, 5, 5, 1, 4, None, 'cl', None, None, None),
+    "s2_pad0_even": (1, 12, 10, 12, 33, 3, 3, 2, 0, None, 'cl', None, None, None),
+    "s2_pad0_odd_3x5_res_nchw_out_slice": (2, 24, 9, 13, 65, 3, 5, 2, 0, 'relu', 'cl', None, 'nchw', 'slice'),
+    "crop_window_cin16_out_slice": (2, 16, 8, 9, 32, 3, 3, 1, 1, 'relu', 'crop', None, None, 'slice'),
+    "crop_window_cin12_cout3": (1, 12, 8, 9, 3, 3, 3, 1, 1, None, 'crop', None, None, None),
+    "x2_base_off_alignment": (2, 16, 7, 9, 65, 3, 3, 1, 1, 'relu', 'cl', 'off4', 'cl', 'nchw'),
+    "nchw_in_cin24": (1, 24, 6, 8, 33, 3, 3, 1, 1, None, 'nchw', 'nchw', None, 'nchw'),
+    "slice_in_cin16_s2": (1, 16, 7, 7, 65, 3, 3, 2, 0, 'relu', 'slice', 'cl', None, None),
+}
+
+
+@pytest.mark.parametrize("case", sorted(EXACT_CONV_CASES))
+def test_conv2d_f32_views_and_geometry_exact(case):
+    from openess_amd import hip
+    B, Cin, H, W, Cout, R, S, st, pad, act, xl, x2l, rl, ol = EXACT_CONV_CASES[case]
+    g = torch.Generator().manual_seed(sum(map(ord, case)))
+    x = _iv(g, (B, Cin, H, W))
+    x2 = _iv(g, (B, Cin, H, W)) if x2l else None
+    w = _iv(g, (Cout, Cin, R, S), -1, 1)
+    b = _iv(g, (Cout,))
+    Ho, Wo = (H + 2 * pad - R) // st + 1, (W + 2 * pad - S) // st + 1
+    r = _iv(g, (B, Cout, Ho, Wo)) if rl else None
+    pre = F.conv2d(x.double() + (x2.double() if x2l else 0), w.double(), b.double(), st, pad) + (r.double() if rl else 0)
+    want = _act64(pre, act)
+    assert want.shape == (B, Cout, Ho, Wo)
+    _nonzero_floors(pre, want)
+    out, big = _out_view(ol, B, Cout, Ho, Wo)
+    y = hip.conv2d_f32(_place(x, xl), hip.pack_conv_weight_f32(w.cuda()), b.cuda(), Cout, R, S, st, pad, act=act,
+                       x2=_place(x2, x2l) if x2l else None, residual=_place(r, rl) if rl else None, out=out)
+    assert y.shape == want.shape
+    assert torch.equal(y.cpu().double(), want), f"{int((y.cpu().double() != want).sum())} of {want.numel()} outputs differ"
+    assert _neighbours_untouched(big, Cout)
+
+
+def test_conv2d_f32_unaligned_x2_equals_aligned_x2():
+    """an in2 that is dense but 4 bytes off 16-byte alignment falls to the element loader and gives the vector path's answer"""
+    from openess_amd import hip
+    g = torch.Generator().manual_seed(41)
+    x, x2 = _iv(g, (2, 32, 6, 9)), _iv(g, (2, 32, 6, 9))
+    packed, b = hip.pack_conv_weight_f32(_iv(g, (33, 32, 3, 3), -1, 1).cuda()), _iv(g, (33,)).cuda()
+    ya = hip.conv2d_f32(_cl(x), packed, b, 33, 3, 3, 1, 1, act='relu', x2=_cl(x2))
+    yb = hip.conv2d_f32(_cl(x), packed, b, 33, 3, 3, 1, 1, act='relu', x2=_place(x2, 'off4'))
+    assert torch.equal(ya, yb)
+
+
+@pytest.mark.parametrize("B,Cin,H,W,Cout,xl", [(2, 16, 5, 7, 33, 'cl'), (1, 12, 1, 6, 3, 'cl'), (1, 16, 3, 1, 32, 'nchw')])
+def test_upsample_conv_f32_odd_extents_exact(B, Cin, H, W, Cout, xl):
+    from openess_amd import hip
+    g = torch.Generator().manual_seed(B * 11 + Cin + H)
+    x, skip = _iv(g, (B, Cin, H, W)), _iv(g, (B, Cin, H, W))
+    w, b = _iv(g, (Cout, Cin, 3, 3), -1, 1), _iv(g, (Cout,))
+    y = hip.conv2d_f32(_place(x, xl), hip.pack_conv_weight_f32(w.cuda()), b.cuda(), Cout, 3, 3, 1, 1, act='relu', x2=_place(skip, xl),
+                       upsample2x=True)
+    up = F.interpolate(x.double() + skip.double(), scale_factor=2, mode='bilinear', align_corners=False)
+    pre = F.conv2d(up, w.double(), b.double(), 1, 1)
+    want = torch.relu(pre)
+    assert y.shape == want.shape == (B, Cout, 2 * H, 2 * W)
+    _nonzero_floors(pre, want)
+    assert torch.equal(y.cpu().double(), want), f"{int((y.cpu().double() != want).sum())} of {want.numel()} outputs differ"
+
+
+@pytest.mark.parametrize("B,Cin,H,W,Cout,two", [(2, 8, 3, 5, 40, False), (1, 24, 1, 1, 1, False), (2, 24, 4, 3, 40, True),
+                                                (1, 8, 1, 1, 1, True)])
+def test_conv_transpose2d_f32_ragged_channels_exact(B, Cin, H, W, Cout, two):
+    from openess_amd import hip
+    g = torch.Generator().manual_seed(B * 100 + Cin + Cout)
+    x = _iv(g, (B, Cin, H, W))
+    skip = _iv(g, (B, Cin, H, W)) if two else None
+    w, b = _iv(g, (Cin, Cout, 5, 5), -1, 1), _iv(g, (Cout,))
+    out = torch.full((B, Cout, 2 * H, 2 * W), float("nan"), device="cuda")          # an NCHW output view
+    y = hip.conv_transpose2d_f32(_cl(x), hip.pack_conv_transpose_weight_f32(w.cuda()), b.cuda(), Cout, act='relu',
+                                 x2=_cl(skip) if two else None, out=out)
+    pre = F.conv_transpose2d(x.double() + (skip.double() if two else 0), w.double(), b.double(), 2, 2, 1)
+    want = torch.relu(pre)
+    assert y.shape == want.shape == (B, Cout, 2 * H, 2 * W)
+    _nonzero_floors(pre, want)
+    assert torch.equal(y.cpu().double(), want), f"{int((y.cpu().double() != want).sum())} of {want.numel()} outputs differ"
+
+
+def test_convlstm_step_f32_hidden_channel_slice_odd_extents():
+    """B > 1, odd H and W, xh the whole cat(x, h) buffer and the hidden output a channel slice of a second one (neighbours
+    asserted untouched), from a non-zero cell; sigmoid / tanh are not exact, so the existing 1e-5 bound applies."""
+    from openess_amd import hip
+    g = torch.Generator().manual_seed(19)
+    B, H, W, Cx, C, k = 3, 7, 9, 16, 32, 3
+    xh = torch.randn(B, Cx + C, H, W, generator=g)
+    wt = torch.randn(4 * C, Cx + C, k, k, generator=g) / ((Cx + C) * k * k) ** 0.5
+    b = torch.randn(4 * C, generator=g)
+    c0 = torch.randn(B, H, W, C, generator=g)
+    cell = c0.cuda().contiguous()
+    nxt = torch.full((B, H, W, Cx + C), -7.0, device="cuda")
+    h = hip.convlstm_step_f32(_cl(xh), hip.pack_conv_weight_f32(wt.cuda()), b.cuda(), C, k, 1, cell, nxt[..., Cx:].permute(0, 3, 1, 2))
+    i_, f_, o_, g_ = F.conv2d(xh.double(), wt.double(), b.double(), padding=1).chunk(4, 1)
+    c64 = torch.sigmoid(f_) * c0.double().permute(0, 3, 1, 2) + torch.sigmoid(i_) * torch.tanh(g_)
+    h64 = torch.sigmoid(o_) * torch.tanh(c64)
+    assert relerr(h.cpu().numpy(), h64.numpy()) <= 1e-5
+    assert relerr(cell.permute(0, 3, 1, 2).cpu().numpy(), c64.numpy()) <= 1e-5
+    assert bool((nxt[..., :Cx] == -7.0).all())
