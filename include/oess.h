@@ -656,6 +656,27 @@ int oess_convlstm_step_f32(const oess_f32_view_t* xh, int B, int H, int W, int C
                            int C_hidden, int R, int S, int pad, int prev_cell_is_zero, float* cell, const oess_f32_view_t* hidden,
                            void* ws, size_t ws_bytes, oess_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------
+ * K15 fp32 SemSegE2VID inference (models/style_networks.py:9-198 of the reference, validation with eval_precision: fp32): the
+ * decoder's convolutions are oess_conv2d_fwd_f32; these are the two layers it lacked.  Additions only: the ABI version stays.
+ *
+ * oess_instance_norm_fwd_f32: nn.InstanceNorm2d(affine=False): out = (in - mean) / sqrt(var + eps) [+ residual] [ReLU if relu],
+ *   mean and biased variance per (sample, channel) over H x W.  in, residual (nullable) and out are B x H x W x C views; out may
+ *   be in itself.  Two launches, no host synchronisation: per-workgroup (mean, M2) partials of shifted sums merged pairwise
+ *   (Chan) in a fixed order -- no raw E[x^2] - E[x]^2, no atomics, bit-repeatable.  Dense 16-byte aligned channels (as above) with
+ *   C % 4 == 0 in every view take 16-byte loads and stores.  ws: oess_instance_norm_f32_workspace_bytes(B, H, W, C) bytes,
+ *   16-byte aligned (0 for an impossible geometry; B <= 65535).
+ * oess_upsample_nearest2x_concat_f32: out[:, :, :, :C] = nearest x2 of in (B x H x W x C), out[:, :, :, C:] = skip
+ *   (B x 2H x 2W x C_skip; NULL with C_skip == 0: upsample only); out: B x 2H x 2W x (C + C_skip).  Values are moved, not
+ *   computed.  H, W <= 16384.
+ * ------------------------------------------------------------------------------------------ */
+size_t oess_instance_norm_f32_workspace_bytes(int B, int H, int W, int C);
+int oess_instance_norm_fwd_f32(const oess_f32_view_t* in, int B, int H, int W, int C, float eps, int relu,
+                               const oess_f32_view_t* residual, const oess_f32_view_t* out, void* ws, size_t ws_bytes,
+                               oess_stream_t stream);
+int oess_upsample_nearest2x_concat_f32(const oess_f32_view_t* in, int B, int H, int W, int C, const oess_f32_view_t* skip,
+                                       int C_skip, const oess_f32_view_t* out, oess_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

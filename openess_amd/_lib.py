@@ -159,6 +159,9 @@ SIGNATURES = {
     "oess_conv_transpose2d_fwd_f32": (c_int, [c_view, c_view, c_int, c_int, c_int, c_int, c_vp, c_vp, c_int, c_int, c_view, c_vp]),
     "oess_convlstm_step_f32": (c_int, [c_view, c_int, c_int, c_int, c_int, c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, c_vp, c_view,
                                        c_vp, c_sz, c_vp]),
+    "oess_instance_norm_f32_workspace_bytes": (c_sz, [c_int, c_int, c_int, c_int]),
+    "oess_instance_norm_fwd_f32": (c_int, [c_view, c_int, c_int, c_int, c_int, c_f, c_int, c_view, c_view, c_vp, c_sz, c_vp]),
+    "oess_upsample_nearest2x_concat_f32": (c_int, [c_view, c_int, c_int, c_int, c_int, c_view, c_int, c_view, c_vp]),
 }
 
 _lib = None

@@ -4,6 +4,7 @@ that every file under the reference's config/ tree loads unchanged and the train
 Differences, all opt-in: `dataset_path: 'synthetic'` (or a missing directory together with
 OPENESS_ALLOW_MISSING_DATA=1) selects the synthetic provider instead of failing the isdir assertion
 (settings.py:117); `generate_log=False` creates nothing on disk, exactly like the reference.
+`eval_precision: fp32` in the `clip:` block (next to `use_amp`) validates the stage-2/3 event networks in fp32.
 Quirk reproduced on purpose: `if_linear_probing` is read from the `clip:` block only (settings.py:258), so the
 reference's config/linear_probe/** files, which put it at top level, dispatch to OpenESSModel.
 """
@@ -159,3 +160,7 @@ class Settings:
         self.frozen_backbone = c.get('frozen_backbone', False)
         self.if_linear_probing = c.get('if_linear_probing', False)
         self.use_amp = c.get('use_amp', False)
+        # arithmetic of the stage-2/3 validation loop: 'bf16' (the training kernels) or 'fp32' (the reference's)
+        self.eval_precision = c.get('eval_precision', 'bf16')
+        if self.eval_precision not in ('bf16', 'fp32'):
+            raise ValueError(f"clip.eval_precision must be 'bf16' or 'fp32', got {self.eval_precision!r}")

@@ -214,6 +214,19 @@ class PackedWeightF32:
             self.key = key
         return self
 
+    def get_composed(self, params, make):
+        """Operand of a weight that is a function of several parameters (SemSegE2VID's composed head): `make()` returns the
+        float64 (weight [Cout, Cin, R, S], bias | None); it runs, and the result is rounded once and packed, only when the
+        version counter of one of `params` has moved."""
+        key = (tuple(p._version for p in params), 'composed')
+        if key != self.key:
+            with torch.no_grad():
+                w, b = make()
+                self.packed = hip.pack_conv_weight_f32(w.float())
+                self.bias = None if b is None else b.float().contiguous()
+            self.key = key
+        return self
+
 
 def conv2d_infer(x, pw, Cout, k, stride=1, pad=0, dil=1, relu=False, residual=None, out=None, out_f32=False):
     """Inference conv on logical-NCHW channels_last tensors.  Returns logical NCHW."""

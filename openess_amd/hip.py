@@ -2046,3 +2046,52 @@ def convlstm_step_f32(xh, packed, bias, C, k, pad, cell, hidden_out, prev_cell_i
     _bump(cell)
     _bump(hidden_out)
     return hidden_out
+
+
+# ------------------------------------------------------------------------------------------ K15: fp32 SemSegE2VID inference
+def instance_norm_f32(x, relu=False, residual=None, eps=1e-5, out=None):
+    """nn.InstanceNorm2d(affine=False, eps) [+ residual] [+ ReLU] in fp32 (oess_instance_norm_fwd_f32): x, residual, out logical
+    [B, C, H, W] fp32 tensors with any strides (channels_last and channel slices of it take the vector path); out may be x
+    itself.  Statistics are merged from shifted per-thread sums in a fixed order: stable and bit-repeatable.  Returns out."""
+    lib = _lib.load()
+    _need_gpu(x, residual, out)
+    if relu and residual is not None:
+        raise NotImplementedError("ReLU after the residual add is not a pattern of the reference")
+    vx = _f32_view(x, "x")
+    B, C, H, W = x.shape
+    vr = None
+    if residual is not None:
+        if tuple(residual.shape) != (B, C, H, W):
+            raise ValueError(f"residual shape {tuple(residual.shape)} != {(B, C, H, W)}")
+        vr = _f32_view(residual, "residual")
+    out = _f32_out(out, B, C, H, W, x.device)
+    vo = _f32_view(out, "out")
+    need = lib.oess_instance_norm_f32_workspace_bytes(B, H, W, C)
+    if need == 0:
+        raise ValueError(f"instance_norm_f32: no kernel for a {(B, C, H, W)} map")
+    ws = _workspace(need, x.device, tag="instnorm_f32")
+    _lib.check(lib.oess_instance_norm_fwd_f32(ctypes.byref(vx), B, H, W, C, float(eps), int(bool(relu)), _f32_ref(vr), ctypes.byref(vo),
+                                              _ptr(ws), ws.numel(), _stream()), "oess_instance_norm_fwd_f32")
+    _bump(out)
+    return out
+
+
+def upsample2x_concat_f32(x, skip=None, out=None):
+    """cat([F.interpolate(x, scale_factor=2, mode='nearest'), skip], 1) in fp32 written by one gather kernel
+    (oess_upsample_nearest2x_concat_f32).  x [B, C, H, W], skip [B, Cs, 2H, 2W] or None: fp32 tensors with any strides (the E2VID
+    latents are read where they are).  Returns out [B, C + Cs, 2H, 2W] (channels_last if new)."""
+    lib = _lib.load()
+    _need_gpu(x, skip, out)
+    vx = _f32_view(x, "x")
+    B, C, H, W = x.shape
+    Cs, vs = 0, None
+    if skip is not None:
+        if skip.ndim != 4 or (skip.shape[0], skip.shape[2], skip.shape[3]) != (B, 2 * H, 2 * W):
+            raise ValueError(f"skip {tuple(skip.shape)} must be [B, Cs, 2H, 2W] = {(B, '*', 2 * H, 2 * W)}")
+        Cs, vs = skip.shape[1], _f32_view(skip, "skip")
+    out = _f32_out(out, B, C + Cs, 2 * H, 2 * W, x.device)
+    vo = _f32_view(out, "out")
+    _lib.check(lib.oess_upsample_nearest2x_concat_f32(ctypes.byref(vx), B, H, W, C, _f32_ref(vs), Cs, ctypes.byref(vo), _stream()),
+               "oess_upsample_nearest2x_concat_f32")
+    _bump(out)
+    return out

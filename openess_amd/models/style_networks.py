@@ -28,6 +28,13 @@ class _HipConv2d(nn.Conv2d):
     def __init__(self, *a, **k):
         super().__init__(*a, **k)
         self._pw = engine.PackedWeight()
+        self._pw32 = engine.PackedWeightF32()
+
+    def forward_f32(self, x, act=None, out=None):
+        """fp32 inference (K15): act(conv(x) + bias) on the f32-input MFMA kernel, operand cached per parameter versions."""
+        pw = self._pw32.get(self.weight, self.bias)
+        return hip.conv2d_f32(x, pw.packed, pw.bias, self.out_channels, self.kernel_size[0], self.kernel_size[1], self.stride[0],
+                              self.padding[0], act=act, out=out)
 
     def forward(self, x, out_f32=False):
         return engine.conv2d_train(x, self.weight, self.bias, self._pw, self.kernel_size[0], self.stride[0],
@@ -54,6 +61,10 @@ class ReLUINSConv2d(nn.Module):
     def forward(self, x):
         return _instance_norm(self.model[0](x), relu=True)
 
+    def forward_f32(self, x):
+        y = self.model[0].forward_f32(x)
+        return hip.instance_norm_f32(y, relu=True, eps=self.model[1].eps, out=y)
+
 
 class INSResBlock(nn.Module):
     def __init__(self, inplanes, planes, stride=1, dropout=0.0):
@@ -69,6 +80,20 @@ class INSResBlock(nn.Module):
         if len(self.model) > 5:
             return self.model[5](_instance_norm(self.model[3](out), relu=False)) + x
         return _instance_norm(self.model[3](out), relu=False, residual=x)      # out += residual (:287)
+
+    def forward_f32(self, x):
+        y = self.model[0].forward_f32(x)
+        y = hip.instance_norm_f32(y, relu=True, eps=self.model[1].eps, out=y)
+        z = self.model[3].forward_f32(y)
+        return hip.instance_norm_f32(z, residual=x, eps=self.model[4].eps, out=z)
+
+
+def compose_head_f64(w256, b256, w512, b512, text):
+    """decoder_ch256 -> decoder_ch512 -> conv2d(text_embeddings) as one 1x1 operator, composed in float64:
+    (T W512 W256 [K, C, 1, 1], T b512 + T W512 b256 [K])."""
+    w1, w2, t = w256.detach().double().flatten(1), w512.detach().double().flatten(1), text.detach().double()
+    tw2 = t @ w2
+    return (tw2 @ w1)[:, :, None, None], t @ b512.detach().double() + tw2 @ b256.detach().double()
 
 
 def skip_concat(x1, x2):
@@ -122,6 +147,7 @@ class SemSegE2VID(nn.Module):
                     p.requires_grad = False
             self.linear_probe = nn.Conv2d(text_categories, text_categories, 1)
         self._pw_head = engine.PackedWeight()
+        self._pw32_head, self._pw32_probe = engine.PackedWeightF32(), engine.PackedWeightF32()
 
     def update_skip_dict(self, skips, x, sz_in):
         rem, scale = sz_in % x.shape[3], sz_in // x.shape[3]
@@ -165,4 +191,54 @@ class SemSegE2VID(nn.Module):
         if self.if_linear_probing:
             logits = hip.linear_probe(logits, self.linear_probe)
         self.update_skip_dict(out, logits, sz_in)
+        return out, x_ch256
+
+    def check_fp32(self):
+        """The configurations forward_fp32 runs: skip_type 'concat' (with 'sum' the reference's own channel counts do not fit:
+        ReLUINSConv2d(256, ...) would receive 128 channels), no dropout in an INSResBlock; raises otherwise, before any launch."""
+        if self.skip_type != 'concat':
+            raise NotImplementedError(f"forward_fp32 runs skip_type='concat' (every shipped config), not {self.skip_type!r}")
+        for m in self.modules():
+            if isinstance(m, nn.Dropout) and m.p > 0:
+                raise NotImplementedError("forward_fp32 has no dropout (INSResBlock(dropout > 0))")
+        if self.materialize_ch256 == 'pooled':
+            raise NotImplementedError("forward_fp32 has no 'pooled' form of x_ch256 (a pre-training option of the bf16 path)")
+
+    def _head_f32(self):
+        c256, c512 = self.decoder_ch256[0], self.decoder_ch512[0]
+        params = (c256.weight, c256.bias, c512.weight, c512.bias, self.text_embeddings)
+        return self._pw32_head.get_composed(params, lambda: compose_head_f64(*params))
+
+    def forward_fp32(self, input_dict):
+        """fp32 inference (K15): forward() in the reference's arithmetic.  input_dict: the fp32 latents {1, 2, 4, 8} of
+        UNetRecurrent.forward_fp32 (logical NCHW, any strides; read where they are).  Returns (out, x_ch256) as forward():
+        out[1] the fp32 logits at input size, out[2], out[4] the decoder features, x_ch256 fp32 or None."""
+        self.check_fp32()
+        for k in (1, 2, 4, 8):
+            if input_dict[k].dtype != torch.float32:
+                raise ValueError("forward_fp32 takes the fp32 latents of the fp32 E2VID path")
+        with torch.no_grad():
+            sz_in = input_dict[1].shape[3]
+            x = input_dict[8]
+            out = {8: x}
+            for layer in self.decoder_scale_1:
+                x = layer.forward_f32(x)
+            x = hip.upsample2x_concat_f32(x, input_dict[4])
+            for layer in self.decoder_scale_2:
+                x = layer.forward_f32(x)
+            self.update_skip_dict(out, x, sz_in)
+            x = hip.upsample2x_concat_f32(x, input_dict[2])
+            for layer in self.decoder_scale_3:
+                x = layer.forward_f32(x)
+            self.update_skip_dict(out, x, sz_in)
+            x = hip.upsample2x_concat_f32(x)
+            x = self.decoder_scale_4[0].forward_f32(x)
+            x_ch256 = self.decoder_ch256[0].forward_f32(x) if self.materialize_ch256 else None
+            pw = self._head_f32()
+            K = self.text_embeddings.shape[0]
+            logits = hip.conv2d_f32(x, pw.packed, pw.bias, K, 1, 1)
+            if self.if_linear_probing:
+                pp = self._pw32_probe.get(self.linear_probe.weight, self.linear_probe.bias)
+                logits = hip.conv2d_f32(logits, pp.packed, pp.bias, K, 1, 1)
+            self.update_skip_dict(out, logits, sz_in)
         return out, x_ch256

@@ -2,6 +2,7 @@
 training/finetune_trainer.py:81-492, training/linear_probe_trainer.py:79-491, training/sup_only_trainer.py:80-511 are three
 near-copies in the reference; what differs between them lives in the three modules of the same names next to this file."""
 import math
+from types import SimpleNamespace
 
 import torch
 import torch.nn.functional as f
@@ -19,6 +20,16 @@ class SupervisedTrainer(BaseTrainer):
     """What the three stage-2/3 trainers share.  A subclass states its differences through three hooks:
     `backend_kwargs()` (extra SemSegE2VID constructor arguments), `deeplab_kwargs()` (extra deeplabv3_resnet50 constructor
     arguments) and `amp_requested()` (whether the reference would build a GradScaler for this trainer)."""
+
+    def __init__(self, settings, train=True):
+        # `eval_precision` (optional YAML key, clip block): arithmetic of val_step; refused here, before anything is built
+        self.eval_precision = getattr(settings, 'eval_precision', 'bf16')
+        if self.eval_precision not in ('bf16', 'fp32'):
+            raise ValueError(f"eval_precision must be 'bf16' or 'fp32', got {self.eval_precision!r}")
+        if self.eval_precision == 'fp32' and settings.config_option == 'frame2recon':
+            raise NotImplementedError("eval_precision: fp32 with frame2recon needs DeepLabv3 (ResNet-50 + ASPP) in fp32, which is "
+                                      "not built; the fp32 validation path covers frame2voxel / recon2voxel")
+        super().__init__(settings, train)
 
     def backend_kwargs(self):
         return {}
@@ -75,6 +86,13 @@ class SupervisedTrainer(BaseTrainer):
         if 'front_sensor_b' in self.models_dict:
             self.reconstructor = ImageReconstructor(self.front_end_sensor_b, self.input_height, self.input_width,
                                                     s.nr_temporal_bins_b, self.device, s.e2vid_config)
+            if self.eval_precision == 'fp32':
+                # validation in the reference's arithmetic: a second reconstructor over the SAME model with states and packed
+                # operands of its own, so nothing the training step reads is shared
+                self.task_backend.check_fp32()
+                opts = SimpleNamespace(**dict(vars(s.e2vid_config), precision='fp32'))
+                self.reconstructor_fp32 = ImageReconstructor(self.front_end_sensor_b, self.input_height, self.input_width,
+                                                             s.nr_temporal_bins_b, self.device, opts)
 
     def createOptimizerDict(self):
         """finetune_trainer.py:198-238: one AdamW over the trainable parameters of the student (optimizer_voxel / optimizer_recon)."""
@@ -95,6 +113,15 @@ class SupervisedTrainer(BaseTrainer):
         for i in range(s.nr_events_data_b):
             _, _, latent = self.reconstructor.update_reconstruction(event, channel_slice=(i * s.input_channels_b, s.input_channels_b),
                                                                     need_latents=(i == s.nr_events_data_b - 1))
+        return latent
+
+    def _latents_fp32(self, event):
+        s = self.settings
+        rec = self.reconstructor_fp32
+        rec.last_states_for_each_channel = {'grayscale': None}
+        for i in range(s.nr_events_data_b):
+            _, _, latent = rec.update_reconstruction(event, channel_slice=(i * s.input_channels_b, s.input_channels_b))
+        rec.last_states_for_each_channel = {'grayscale': None}
         return latent
 
     def _set_modes(self):
@@ -160,14 +187,27 @@ class SupervisedTrainer(BaseTrainer):
             opt.step()
         return losses, outputs, t_loss.detach()
 
-    def val_step(self, batch, sensor, i_batch, vis_reconstr_idx, file_path):
+    def val_logits(self, batch, precision=None):
+        """Class logits of one validation batch in `precision` (default: the trainer's eval_precision).  'fp32' runs the E2VID
+        encoder through the fp32 reconstructor and the decoder through SemSegE2VID.forward_fp32 (trainers built with
+        eval_precision: fp32 only); it shares no state with the bf16 path or the training step."""
         s = self.settings
+        precision = self.eval_precision if precision is None else precision
+        if s.config_option not in ('recon2voxel', 'frame2voxel'):
+            if precision != 'bf16':
+                raise NotImplementedError("fp32 validation covers frame2voxel / recon2voxel (no fp32 DeepLabv3)")
+            return self.models_dict['model_recon'](batch[2])[0]
+        if precision == 'fp32':
+            if getattr(self, 'reconstructor_fp32', None) is None:
+                raise RuntimeError("this trainer was built without eval_precision: fp32")
+            return self.models_dict['back_end'].forward_fp32(self._latents_fp32(batch[0]))[0][1]
+        if precision != 'bf16':
+            raise ValueError(f"precision must be 'bf16' or 'fp32', got {precision!r}")
+        return self.models_dict['back_end'](self._latents(batch[0]))[0][1]
+
+    def val_step(self, batch, sensor, i_batch, vis_reconstr_idx, file_path):
         gt = batch[1]
-        if s.config_option in ('recon2voxel', 'frame2voxel'):
-            pred, _ = self.models_dict['back_end'](self._latents(batch[0]))
-            pred = pred[1]
-        else:
-            pred, _ = self.models_dict['model_recon'](batch[2])
+        pred = self.val_logits(batch)
         losses = {'semseg_' + sensor + '_loss': self.task_loss(pred, gt).detach()}
         self.metrics_semseg_b.update_batch(pred.argmax(dim=1), gt)
         return losses, None
