@@ -238,8 +238,8 @@ size_t oess_conv2d_fwd_workspace_bytes(int B, int H, int W, int Cin, int Cout, i
                                        int with_tile_stats, int out_is_f32);
 /* Which kernel a call takes.  oess_conv2d_fwd_bf16 is one entry point over the kernels below; the choice depends on the geometry,
  * the epilogue flags, the pixel strides, the output pointer's 16-byte alignment and the workspace on offer.
- * oess_conv2d_fwd_route runs the launch's own walk of the dispatch rules up to the launch site and returns the OESS_ROUTE_*
- * value found there instead of launching.  Host only: no launch, no attribute call, no allocation; the one runtime call is the
+ * oess_conv2d_fwd_route makes the plan the launch itself executes (conv_plan: the dispatch rules) and returns its OESS_ROUTE_*
+ * value instead of launching.  Host only: no launch, no attribute call, no allocation; the one runtime call is the
  * rules' query of the device's CU count, which falls back to 256 without a GPU (so the query runs on any machine, and the
  * w128 rules answer for the current device).  The OESS_W128_* environment knobs of the launch apply to the query as well.  Negative = OESS_E*, as the launch would return.  Split-K routes carry the slice count:
  * route = OESS_ROUTE_SPLITK_* | ks << 8; OESS_ROUTE_KERNEL(route) strips it.  oess_convlstm_fused_route is the same query for

@@ -2037,8 +2037,6 @@ size_t oess_conv2d_packed_bytes(int Cout, int Cin, int R, int S, int flip_for_dg
 }  // extern "C"
 
 namespace {
-struct LstmOut { const float* prev; float* cell; void* h; long long h_stride; int C; };
-
 void conv_set_attrs() {
     static bool set_on[64] = {false};     // the attribute is per device
     int dev = 0;
@@ -2061,38 +2059,50 @@ void conv_set_attrs() {
     }
 }
 
-int conv_fwd_impl(const void* in, long long in_pix_stride, int B, int H, int W, int Cin, const void* w_packed,
-                  const float* bias, int Cout, int R, int S, int stride, int pad, int dil, int relu,
-                  const void* residual, long long res_pix_stride, void* out_bf16, float* out_f32,
-                  long long out_pix_stride, float* tile_stats, const LstmOut* lstm, oess_stream_t stream,
-                  void* workspace = nullptr, size_t workspace_bytes = 0, size_t* want_workspace = nullptr,
-                  ConvArgs* capture = nullptr, int* route = nullptr) {
-    // route != null (oess_conv2d_fwd_route): the walk stops at the launch site it reaches and stores that site's OESS_ROUTE_*
-    // value instead of launching.  The query passes dummy host pointers, so EVERY hipLaunchKernelGGL of this function must have
-    // an OESS_ROUTE(...) in front of it (one value per template instantiation, declared in include/oess.h and pinned by a row of
-    // tests/conv_route_cases.py); the guard at the end of the function turns a forgotten one on the last path into an error.
-#define OESS_ROUTE(r) do { if (route) { *route = (r); return OESS_OK; } } while (0)
-    // capture != null (ConvLSTM only): fill *capture with the launch arguments of the row-halo kernel instead of launching it;
-    // OESS_EINVAL when the geometry takes another kernel (the caller then launches the problems one by one)
-    if (want_workspace) *want_workspace = 0;
+// One bf16 convolution (or fused ConvLSTM step) without its pointers: everything the dispatch rules look at.
+struct ConvCall {
+    int B, H, W, Cin, Cout, R, S, stride, pad, dil, relu;
+    bool has_bias, has_residual, out_is_f32, with_tile_stats, out_aligned16;    // (the bf16 output pointer's 16-byte alignment)
+    long long in_pix_stride, out_pix_stride, res_pix_stride;
+    int C_hidden; long long hidden_pix_stride;      // C_hidden != 0: fused ConvLSTM step (Cout = 4 * C_hidden; the out_* / res_* fields are unused)
+    size_t workspace_bytes;                 // split-K workspace on offer (0 = none)
+};
+// What conv_plan decides: the kernel (OESS_ROUTE_*, split-K with its slice count), its launch shape and the ConvArgs it gets,
+// pointers left null.  want_workspace = the split-K workspace the call takes if offered that much (0: no split-K for it).
+struct ConvPlan {
+    int route;
+    ConvArgs args;                          // (conv_bind puts the pointers in)
+    dim3 grid, block;
+    size_t lds, want_workspace;
+};
+struct ConvPtrs {                           // ConvLSTM calls: lstm_prev / lstm_cell / lstm_h = previous cell (or null), new cell, hidden output
+    const void *in, *w; const float* bias; const void* residual; void* out_bf16; float *out_f32, *tile_stats;
+    const float* lstm_prev; float* lstm_cell; void* lstm_h; void* workspace;
+};
+
+inline int s2_tiles_m(int B, int Ho, int Wo) { return B * ((Ho + S2_PH - 1) / S2_PH) * ((Wo + S2_PW - 1) / S2_PW); }
+
+// The dispatch rules as a pure host function: validates the call, walks the rules in order and fills *p for the first one that
+// takes it.  No launch, no attribute call, no allocation; the one runtime call is num_cus() behind the w128 rules.  One value
+// of OESS_ROUTE_* per template instantiation (include/oess.h), each pinned by a row of tests/conv_route_cases.py.
+int conv_plan(const ConvCall& c, ConvPlan* p) {
+    const int B = c.B, H = c.H, W = c.W, Cin = c.Cin, Cout = c.Cout, R = c.R, S = c.S, stride = c.stride, pad = c.pad, dil = c.dil, relu = c.relu;
+    const bool bias = c.has_bias, residual = c.has_residual, out_f32 = c.out_is_f32, tile_stats = c.with_tile_stats, lstm = c.C_hidden != 0;
+    // (a ConvLSTM call's output stride satisfies the generic output checks below; the conv epilogue is not used)
+    const long long in_pix_stride = c.in_pix_stride, res_pix_stride = c.res_pix_stride, out_pix_stride = lstm ? Cout : c.out_pix_stride;
+    p->want_workspace = 0;
     if (lstm) {
-        if (!lstm->cell || !lstm->h || lstm->C <= 0 || (lstm->C & 31) || Cout != 4 * lstm->C || (lstm->h_stride & 1) ||
-            lstm->h_stride < lstm->C || residual || relu || tile_stats || out_f32 || stride != 1)
+        if (c.C_hidden <= 0 || (c.C_hidden & 31) || Cout != 4 * c.C_hidden || (c.hidden_pix_stride & 1) ||
+            c.hidden_pix_stride < c.C_hidden || residual || relu || tile_stats || out_f32 || stride != 1)
             return OESS_EINVAL;
-        out_bf16 = lstm->h;             // satisfies the generic output checks below; the conv epilogue is not used
-        out_pix_stride = Cout;
     }
-    if (!in || !w_packed || (!out_bf16 && !out_f32) || B <= 0 || H <= 0 || W <= 0 || Cin <= 0 || (Cin & 7) || Cout <= 0 ||
-        R <= 0 || S <= 0 || stride <= 0 || pad < 0 || dil <= 0)
+    if (B <= 0 || H <= 0 || W <= 0 || Cin <= 0 || (Cin & 7) || Cout <= 0 || R <= 0 || S <= 0 || stride <= 0 || pad < 0 || dil <= 0)
         return OESS_EINVAL;
     if ((in_pix_stride & 7) || in_pix_stride < Cin || out_pix_stride < Cout) return OESS_EINVAL;
-    if (out_bf16 && !out_f32 && (out_pix_stride & 7) && (Cout & 7) == 0) return OESS_EINVAL;
+    if (!out_f32 && (out_pix_stride & 7) && (Cout & 7) == 0) return OESS_EINVAL;
     if (residual && ((res_pix_stride & 7) || out_f32)) return OESS_EINVAL;
-    ConvArgs a;
-    a.in = (const uint16_t*)in; a.w = (const uint16_t*)w_packed; a.bias = bias;
-    a.out = out_f32 ? nullptr : (uint16_t*)out_bf16; a.out_f32 = out_f32;
-    a.residual = (const uint16_t*)residual;
-    a.stats = tile_stats;
+    ConvArgs& a = p->args;
+    a = ConvArgs{};                         // (all pointers null)
     if (tile_stats && (bias || out_f32 || residual || relu)) return OESS_EINVAL;
     a.in_pix_stride = in_pix_stride; a.out_pix_stride = out_pix_stride; a.res_pix_stride = res_pix_stride;
     a.B = B; a.H = H; a.W = W; a.Cin = Cin; a.Cout = Cout;
@@ -2105,14 +2115,11 @@ int conv_fwd_impl(const void* in, long long in_pix_stride, int B, int H, int W, 
     if (M > 0x7fffffffll) return OESS_EINVAL;
     a.M = (int)M;
     a.relu = relu;
-    a.lstm_prev = lstm ? lstm->prev : nullptr; a.lstm_cell = lstm ? lstm->cell : nullptr;
-    a.lstm_h = lstm ? (uint16_t*)lstm->h : nullptr; a.lstm_h_stride = lstm ? lstm->h_stride : 0; a.lstm_C = lstm ? lstm->C : 0;
+    a.lstm_h_stride = lstm ? c.hidden_pix_stride : 0; a.lstm_C = c.C_hidden;
     a.tiles_m = (a.M + BM - 1) / BM;
-    a.partial = nullptr; a.ksplit = 1; a.kt_per = 0;
+    a.ksplit = 1; a.kt_per = 0;
     a.mg_w = (W >= 2 && 256ll * W < 0x100000000ll) ? (unsigned)(0x100000000ull / (unsigned)W) + 1u : 0u;
     a.mg_wd = (256ll * (W + dil) < 0x100000000ll) ? (unsigned)(0x100000000ull / (unsigned)(W + dil)) + 1u : 0u;
-    hipStream_t st = (hipStream_t)stream;
-    if (!route) conv_set_attrs();           // the route query does no device work
     // The LDS-DMA kernels address the input with 32-bit buffer offsets and decode filter taps with exact small-range
     // reciprocals (verified here over the whole range); anything outside takes the register-staged generic kernel.
     const long long in_extent = (((long long)B * H * W - 1) * in_pix_stride + Cin) * 2;
@@ -2140,43 +2147,28 @@ int conv_fwd_impl(const void* in, long long in_pix_stride, int B, int H, int W, 
     const double e128 = (double)t128 / (double)(((t128 + 511) / 512) * 512);
     const double e64 = 0.88 * (double)t64 / (double)(((t64 + 767) / 768) * 768);
     const bool want64 = bn == 128 && !tile_stats && !lstm && e64 > e128 * 1.04;
+    auto take = [p](int route, dim3 g, dim3 b, size_t lds) { p->route = route; p->grid = g; p->block = b; p->lds = lds; return OESS_OK; };
 
     // (1) Cin == 8 stencil layers (E2VID head): LDS halo tile instead of the im2col gather
-    if (!capture && !lstm && Cin == 8 && stride == 1 && dil == 1 && R == 5 && S == 5 && Cout <= 32 && (Cout & 3) == 0 && !residual && !out_f32 &&
+    if (!lstm && Cin == 8 && stride == 1 && dil == 1 && R == 5 && S == 5 && Cout <= 32 && (Cout & 3) == 0 && !residual && !out_f32 &&
         !tile_stats && (out_pix_stride & 3) == 0 && a.Kpad == 256 && dma_ok) {
-        if (want_workspace) return OESS_OK;
         const int tiles = B * ((a.Ho + 7) / 8) * ((a.Wo + 63) / 64);
-        OESS_ROUTE(OESS_ROUTE_SMALLCIN);
-        hipLaunchKernelGGL((conv_smallcin_kernel<5, 5>), dim3(tiles < 512 ? tiles : 512), dim3(256), 0, st, a);   // persistent: 2 workgroups per CU
-        OESS_HIP(hipGetLastError());
-        return OESS_OK;
+        return take(OESS_ROUTE_SMALLCIN, dim3(tiles < 512 ? tiles : 512), dim3(256), 0);   // persistent: 2 workgroups per CU
     }
     if (!dma_ok) {
-        if (want_workspace) return OESS_OK;
-        if (lstm || capture) return OESS_EINVAL;       // the fused ConvLSTM epilogue exists only in the LDS-DMA kernels
+        if (lstm) return OESS_EINVAL;       // the fused ConvLSTM epilogue exists only in the LDS-DMA kernels
         const size_t tab = (size_t)(a.Kpad / 8) * 8;
         size_t lds = (size_t)2 * (BM + bn) * 8 * 16 + tab;
         if (lds < epi) lds = epi;
-        OESS_ROUTE(bn == 128 ? OESS_ROUTE_FALLBACK_128 : (bn == 64 ? OESS_ROUTE_FALLBACK_64 : OESS_ROUTE_FALLBACK_32));
-        if (bn == 128) hipLaunchKernelGGL(conv_fwd_kernel<128>, grid, block, lds, st, a);
-        else if (bn == 64) hipLaunchKernelGGL(conv_fwd_kernel<64>, grid, block, lds, st, a);
-        else hipLaunchKernelGGL(conv_fwd_kernel<32>, grid, block, lds, st, a);
-        OESS_HIP(hipGetLastError());
-        return OESS_OK;
+        return take(bn == 128 ? OESS_ROUTE_FALLBACK_128 : (bn == 64 ? OESS_ROUTE_FALLBACK_64 : OESS_ROUTE_FALLBACK_32), grid, block, lds);
     }
     // (1b) 5x5 stride-2 pad-2 layers (E2VID's encoder ConvLayers): 2-D input halo in LDS, 8 x 16-pixel x 64-channel tiles
     if (!lstm && R == 5 && S == 5 && stride == 2 && pad == 2 && dil == 1 && (Cin & 31) == 0 && (Cout & 63) == 0 && !tile_stats &&
-        !residual && !out_f32 && relu != 2 && (out_pix_stride & 7) == 0 && (((uintptr_t)out_bf16) & 15) == 0 && a.Kpad >= 25 * Cin) {
-        if (want_workspace) return OESS_OK;
+        !residual && !out_f32 && relu != 2 && (out_pix_stride & 7) == 0 && c.out_aligned16 && a.Kpad >= 25 * Cin) {
         a.tiles_n = Cout / 64;
-        a.tiles_m = B * ((a.Ho + S2_PH - 1) / S2_PH) * ((a.Wo + S2_PW - 1) / S2_PW);
-        if (capture) { *capture = a; return OESS_OK; }
-        OESS_ROUTE(OESS_ROUTE_S2_HALO);
-        hipLaunchKernelGGL((conv5x5s2_halo_kernel<false>), dim3(a.tiles_m * a.tiles_n), dim3(256), S2_LDS, st, a, S2Head{});
-        OESS_HIP(hipGetLastError());
-        return OESS_OK;
+        a.tiles_m = s2_tiles_m(B, a.Ho, a.Wo);
+        return take(OESS_ROUTE_S2_HALO, dim3(a.tiles_m * a.tiles_n), dim3(256), S2_LDS);
     }
-    if (capture && !lstm) return OESS_EINVAL;          // (non-ConvLSTM captures are for the stride-2 group launch only)
     // (1c) SMALL MAPS (at most one 128 x 128 tile per CU: DeepLabv3's OS16 half, M = 8 960), K >= 16 slabs, not a row-halo 3x3:
     //      with a single workgroup on a CU nothing is lost by giving it the whole LDS, so the ring is 4 deep (three slabs in
     //      flight).  Measured on the DeepLabv3 forward (round 5, same box, ring 2 / 3 / 4): 1024->256 36.1 / 31.6 / 31.4 us,
@@ -2187,63 +2179,39 @@ int conv_fwd_impl(const void* in, long long in_pix_stride, int B, int H, int W, 
     //      32.3 -> 29.4 us, 2048->256 36.0 -> 30.1, 1280->256 28.7 -> 23.1, 256->1024 22.5 -> 20.4 (same box, alternating).
     {
         const bool is3x3halo = R == 3 && S == 3 && stride == 1 && pad == dil;
-        if (!capture && !lstm && bn == 128 && fastk && t128 <= 256 && a.Kpad / BK >= 16 && a.Kpad / BK < 200 && !is3x3halo) {
-            if (want_workspace) return OESS_OK;
+        if (!lstm && bn == 128 && fastk && t128 <= 256 && a.Kpad / BK >= 16 && a.Kpad / BK < 200 && !is3x3halo) {
             size_t lds = (size_t)4 * (BM + 128) * 8 * 16;
             if (lds < epi) lds = epi;
-            OESS_ROUTE(OESS_ROUTE_SMALLMAP_RING);
-            hipLaunchKernelGGL((conv_fwd_dma_kernel<128, 128, 4, true, 0, 512>), grid, dim3(512), lds, st, a);
-            OESS_HIP(hipGetLastError());
-            return OESS_OK;
+            return take(OESS_ROUTE_SMALLMAP_RING, grid, dim3(512), lds);
         }
     }
     // (2a) the same layers in front of a BatchNorm (raw bf16 result + tile statistics: conv2 of the frozen teacher's dilated
     //      bottlenecks), Cout % 256 == 0, >= 2 tiles of 256 x 256 per CU: persistent workgroups on 128 x 128 wave tiles
     //      (conv3x3_w128.h).  OESS_W128_CONV3=0 keeps rule (2) (A/B).
-    if (!capture && !lstm && R == 3 && S == 3 && stride == 1 && pad == dil && fastk && (Cout % 256) == 0 && a.Kpad == 9 * Cin && a.Ho == H && a.Wo == W &&
-        !bias && !relu && !residual && !out_f32 && (out_pix_stride & 7) == 0 && (((uintptr_t)out_bf16) & 15) == 0 && a.mg_w && a.mg_wd) {
+    if (!lstm && R == 3 && S == 3 && stride == 1 && pad == dil && fastk && (Cout % 256) == 0 && a.Kpad == 9 * Cin && a.Ho == H && a.Wo == W &&
+        !bias && !relu && !residual && !out_f32 && (out_pix_stride & 7) == 0 && c.out_aligned16 && a.mg_w && a.mg_wd) {
         const int use3 = [] { const char* e = getenv("OESS_W128_CONV3"); return e ? atoi(e) : 1; }();
         const long long t256 = (long long)((a.M + 255) / 256) * (Cout / 256);
         const long long out_extent = ((long long)a.M - 1) * out_pix_stride * 2 + (long long)Cout * 2;
         const int breaks = (256 + W - 2) / W;
         if (use3 && t256 >= 2ll * num_cus() && dil + 255 + dil * breaks + dil + 1 <= W128_HROWS && breaks + 1 + 2 * dil <= H &&
             out_extent < 0x7ffffff0ll && (long long)Cout * a.Kpad * 2 < 0x7ffffff0ll && (long long)H * W * W < 0x100000000ll) {
-            if (want_workspace) return OESS_OK;
             a.tiles_m = (a.M + 255) / 256; a.tiles_n = Cout / 256;
-            OESS_ROUTE(OESS_ROUTE_CONV3X3_W128);
-            hipLaunchKernelGGL(conv3x3_w128_kernel, dim3(num_cus() / 8 * 8), dim3(256), (size_t)W128_OPER, st, a);
-            OESS_HIP(hipGetLastError());
-            return OESS_OK;
+            return take(OESS_ROUTE_CONV3X3_W128, dim3(num_cus() / 8 * 8), dim3(256), (size_t)W128_OPER);
         }
     }
     // (2) 3x3 stride-1 'same' convolutions with Cin % 64 == 0: row-halo reuse of the pixel operand, unless the 64-row tiling
     //     is what the layer wants (tile quantisation of small maps)
     if (R == 3 && S == 3 && stride == 1 && pad == dil && fastk && bn == 128 && a.Kpad == 9 * Cin && a.Ho == H && a.Wo == W &&
-        (dil + 127 + dil * ((BM + W - 2) / W) + dil + 1) <= HALO_ROWS && !want64) {
-        if (want_workspace) return OESS_OK;
-        if (capture) { *capture = a; return OESS_OK; }
-        const size_t lds = (size_t)2 * HALO_ROWS * 128 + (size_t)2 * 128 * 128;
-        OESS_ROUTE(lstm ? OESS_ROUTE_HALO3X3_LSTM : OESS_ROUTE_HALO3X3);
-        if (lstm) hipLaunchKernelGGL((conv3x3_halo_kernel<1>), grid, block, lds, st, a);
-        else hipLaunchKernelGGL((conv3x3_halo_kernel<0>), grid, block, lds, st, a);
-        OESS_HIP(hipGetLastError());
-        return OESS_OK;
-    }
+        (dil + 127 + dil * ((BM + W - 2) / W) + dil + 1) <= HALO_ROWS && !want64)
+        return take(lstm ? OESS_ROUTE_HALO3X3_LSTM : OESS_ROUTE_HALO3X3, grid, block, (size_t)2 * HALO_ROWS * 128 + (size_t)2 * 128 * 128);
     // (3) fused ConvLSTM cell update on geometries the halo kernel does not take
-    if (capture) return OESS_EINVAL;
-    if (lstm) {
-        const size_t lds = (size_t)2 * (BM + 128) * 8 * 16;
-        OESS_ROUTE(fastk ? OESS_ROUTE_LSTM_FASTK : OESS_ROUTE_LSTM_SLOWK);
-        if (fastk) hipLaunchKernelGGL((conv_fwd_dma_kernel<128, 128, 2, true, 1>), grid, block, lds, st, a);
-        else hipLaunchKernelGGL((conv_fwd_dma_kernel<128, 128, 2, false, 1>), grid, block, lds, st, a);
-        OESS_HIP(hipGetLastError());
-        return OESS_OK;
-    }
+    if (lstm) return take(fastk ? OESS_ROUTE_LSTM_FASTK : OESS_ROUTE_LSTM_SLOWK, grid, block, (size_t)2 * (BM + 128) * 8 * 16);
     // (3a) split-K for small-M / long-K layers (DeepLabv3's ASPP at output stride 16: M = 8 960 = 70 row tiles x 2 column
     //      tiles = 140 workgroups for 512 slots, K = 18 432 = 288 slabs each: 272 us at 311 TFLOP/s).  Model (us): a workgroup
     //      spends 1.1 per slab + 6 fixed; the fp32 slices cost a write and a read of ks * M * Cout * 4 bytes at ~3 TB/s plus
     //      one launch.  Taken when it beats both the one-pass 128-row tiling and the 64-row tiling by 15 %.
-    if (!lstm && bn == 128 && (Cout & 3) == 0 && a.Kpad / BK >= 32 && t128 <= 384 && (!out_f32 || (out_pix_stride & 3) == 0)) {
+    if (bn == 128 && (Cout & 3) == 0 && a.Kpad / BK >= 32 && t128 <= 384 && (!out_f32 || (out_pix_stride & 3) == 0)) {
         const int KTall = a.Kpad / BK;
         auto rounds = [](long long wg, long long slots) { return (double)((wg + slots - 1) / slots); };
         const double t_one = rounds(t128, 512) * (KTall * 1.1 + 6.0);
@@ -2257,22 +2225,14 @@ int conv_fwd_impl(const void* in, long long in_pix_stride, int B, int H, int W, 
             if (tk < tbest) { tbest = tk; best = ks; }
         }
         if (best > 1) {
-            const size_t need = (size_t)best * (size_t)a.M * Cout * sizeof(float);
-            if (want_workspace) { *want_workspace = need; return OESS_OK; }
-            if (workspace && workspace_bytes >= need) {
-                a.partial = (float*)workspace; a.ksplit = best; a.kt_per = (KTall + best - 1) / best;
-                const size_t lds = (size_t)2 * (BM + 128) * 8 * 16;
-                const dim3 gridk(a.tiles_m * a.tiles_n, best);
-                OESS_ROUTE((fastk ? OESS_ROUTE_SPLITK_FASTK : OESS_ROUTE_SPLITK_SLOWK) | best << 8);
-                if (fastk) hipLaunchKernelGGL((conv_fwd_dma_kernel<128, 128, 2, true>), gridk, block, lds, st, a);
-                else hipLaunchKernelGGL((conv_fwd_dma_kernel<128, 128, 2, false>), gridk, block, lds, st, a);
-                hipLaunchKernelGGL(splitk_reduce_kernel, dim3(a.tiles_m, (Cout + 63) / 64), dim3(256), 0, st, a);
-                OESS_HIP(hipGetLastError());
-                return OESS_OK;
+            p->want_workspace = (size_t)best * (size_t)a.M * Cout * sizeof(float);
+            if (c.workspace_bytes >= p->want_workspace) {        // (conv_launch points a.partial at the workspace)
+                a.ksplit = best; a.kt_per = (KTall + best - 1) / best;
+                return take((fastk ? OESS_ROUTE_SPLITK_FASTK : OESS_ROUTE_SPLITK_SLOWK) | best << 8, dim3(a.tiles_m * a.tiles_n, best), block,
+                            (size_t)2 * (BM + 128) * 8 * 16);
             }
         }
     }
-    if (want_workspace) return OESS_OK;
     // (3b) large plain-GEMM layers (1x1, Cin % 64 == 0, Cout % 256 == 0, K >= 256): 256 x 256 tiles on ONE 8-wave workgroup per
     //      CU, wave tile 64 x 128 (24 fragment reads per 32 MFMAs instead of 16 per 16, half the L2 -> LDS bytes per FLOP).
     //      Same template as rule (6).  Measured against the 128 x 128 tiling on the teacher's layers at M = 140 800:
@@ -2281,7 +2241,7 @@ int conv_fwd_impl(const void* in, long long in_pix_stride, int B, int H, int W, 
     //      (Round 5: under the concurrent step schedule these 128 KB / 512-thread workgroups wait for a CU free of ConvLSTM
     //      workgroups and run 2.2 x longer than alone; the 128 x 128 tiling, which co-resides, was measured there as well:
     //      193.0 vs 194.8 event-frames/s, 318 vs 324 on frame2recon_full -- the big tile stays.)
-    if (!lstm && bn == 128 && fastk && (Cout % 256) == 0 && a.Kpad >= 256 && R == 1 && S == 1 && stride == 1) {
+    if (bn == 128 && fastk && (Cout % 256) == 0 && a.Kpad >= 256 && R == 1 && S == 1 && stride == 1) {
         const long long t256 = (long long)((a.M + 255) / 256) * (Cout / 256);
         // (3a) the same layers in front of a BatchNorm (raw bf16 result + tile statistics; the frozen teacher's conv1 / conv3 /
         //      downsample layers) or with a bias / ReLU (its 2048 -> 256 decoder layer), >= 2 tiles per CU: persistent workgroups on
@@ -2291,29 +2251,23 @@ int conv_fwd_impl(const void* in, long long in_pix_stride, int B, int H, int W, 
         const long long out_extent = ((long long)a.M - 1) * out_pix_stride * 2 + (long long)Cout * 2;
         static const long long min_t = [] { const char* e = getenv("OESS_W128_MIN_TILES"); return e ? atoll(e) : 0ll; }();      // A/B knob
         if (use_w128 && t256 >= (min_t > 0 ? min_t : 2ll * num_cus()) && (relu == 0 || relu == 1) && !residual && !out_f32 && a.Kpad == Cin && (out_pix_stride & 7) == 0 &&
-            (((uintptr_t)out_bf16) & 15) == 0 && out_extent < 0x7ffffff0ll && (long long)Cout * a.Kpad * 2 < 0x7ffffff0ll) {
+            c.out_aligned16 && out_extent < 0x7ffffff0ll && (long long)Cout * a.Kpad * 2 < 0x7ffffff0ll) {
             a.tiles_m = (a.M + 255) / 256; a.tiles_n = Cout / 256;
             // non-temporal result stores where the result is >= 4 x the input (256 -> 1024 168 -> 150 us, 512 -> 2048 402 -> 376;
             // 2 x and reducing layers lose 2-10 % with them: EXPERIMENTS R6-8).  OESS_W128_NT = 0 / 1 forces (A/B).
             static const int nt_env = [] { const char* e = getenv("OESS_W128_NT"); return e ? atoi(e) : -1; }();
             a.ksplit = nt_env >= 0 ? nt_env : (Cout >= 4 * Cin);
-            OESS_ROUTE(OESS_ROUTE_CONV1X1_W128);
-            hipLaunchKernelGGL(conv1x1_w128_kernel, dim3(num_cus() / 8 * 8), dim3(256), (size_t)G128_LDS, st, a);
-            OESS_HIP(hipGetLastError());
-            return OESS_OK;
+            return take(OESS_ROUTE_CONV1X1_W128, dim3(num_cus() / 8 * 8), dim3(256), (size_t)G128_LDS);
         }
         if (getenv("OESS_W128_WHY"))
             fprintf(stderr, "[oess] 1x1 %d -> %d M %d not on conv1x1_w128_kernel: t256 %lld bias %d relu %d residual %d out_f32 %d Kpad %d ops %lld align %d\n", Cin, Cout, a.M,
-                    t256, bias != nullptr, relu, residual != nullptr, out_f32 != nullptr, a.Kpad, (long long)out_pix_stride, (int)(((uintptr_t)out_bf16) & 15));
+                    t256, bias, relu, residual, out_f32, a.Kpad, (long long)out_pix_stride, c.out_aligned16 ? 0 : 1);
         if (t256 >= 400) {
             a.tiles_m = (a.M + 255) / 256; a.tiles_n = Cout / 256;
             size_t lds = (size_t)2 * 512 * 128;                                          // 2 stages x (256 + 256) rows x 128 B
             const size_t epi256 = (size_t)256 * (256 + 8) * 2 + (size_t)4 * 256 * 2 * 4 + 256;   // output image + BatchNorm partials
             if (lds < epi256) lds = epi256;
-            OESS_ROUTE(OESS_ROUTE_TILE256);
-            hipLaunchKernelGGL((conv_fwd_dma_kernel<256, 256, 2, true>), dim3(a.tiles_m * a.tiles_n), dim3(512), lds, st, a);
-            OESS_HIP(hipGetLastError());
-            return OESS_OK;
+            return take(OESS_ROUTE_TILE256, dim3(a.tiles_m * a.tiles_n), dim3(512), lds);
         }
     }
     // (4) short reductions (K <= 256, the 1x1 bottleneck convs): a workgroup lives ~6 us of which the K loop is a fraction, so
@@ -2322,43 +2276,119 @@ int conv_fwd_impl(const void* in, long long in_pix_stride, int B, int H, int W, 
     if (bn == 128 && fastk32 && a.Kpad <= 256) {
         size_t lds3 = (size_t)3 * (BM + 128) * 64;
         if (lds3 < epi) lds3 = epi;
-        OESS_ROUTE(OESS_ROUTE_RING32);
-        hipLaunchKernelGGL((conv_fwd_dma32_kernel<128, true, 0, 3>), grid, block, lds3, st, a);
-        OESS_HIP(hipGetLastError());
-        return OESS_OK;
+        return take(OESS_ROUTE_RING32, grid, block, lds3);
     }
     // (5) 64 x 128 tiles (48 KB of LDS: 3 workgroups per CU) when the 128-row tiling leaves most of its last round of
     //     workgroups empty: e.g. 550 tiles over 512 slots run as two rounds at 54 % - 1100 half tiles over 768 slots do not
     if (want64) {
         a.tiles_m = (a.M + 63) / 64;
-        const dim3 grid64(a.tiles_m * a.tiles_n);
         size_t lds = (size_t)2 * (64 + 128) * 8 * 16;
         const size_t epi64 = (size_t)64 * (128 + 8) * 2 + 4096;
         if (lds < epi64) lds = epi64;
-        OESS_ROUTE(fastk ? OESS_ROUTE_TILE64_FASTK : OESS_ROUTE_TILE64_SLOWK);
-        if (fastk) hipLaunchKernelGGL((conv_fwd_dma_kernel<64, 128, 2, true>), grid64, block, lds, st, a);
-        else hipLaunchKernelGGL((conv_fwd_dma_kernel<64, 128, 2, false>), grid64, block, lds, st, a);
-        OESS_HIP(hipGetLastError());
-        return OESS_OK;
+        return take(fastk ? OESS_ROUTE_TILE64_FASTK : OESS_ROUTE_TILE64_SLOWK, dim3(a.tiles_m * a.tiles_n), block, lds);
     }
     // (6) the general LDS-DMA kernel: 128 x {128, 64, 32} tiles, 2-stage ring, 2 workgroups per CU
-    {
-        size_t lds = (size_t)2 * (BM + bn) * 8 * 16;
-        if (lds < epi) lds = epi;
-#define OESS_LAUNCH_DMA(BN_)                                                                                  \
-        if (fastk) hipLaunchKernelGGL((conv_fwd_dma_kernel<128, BN_, 2, true>), grid, block, lds, st, a);        \
-        else hipLaunchKernelGGL((conv_fwd_dma_kernel<128, BN_, 2, false>), grid, block, lds, st, a);
-        OESS_ROUTE((bn == 128 ? OESS_ROUTE_DMA128_FASTK : (bn == 64 ? OESS_ROUTE_DMA64_FASTK : OESS_ROUTE_DMA32_FASTK)) + (fastk ? 0 : 1));
-        if (bn == 128) { OESS_LAUNCH_DMA(128) }
-        else if (bn == 64) { OESS_LAUNCH_DMA(64) }
-        else { OESS_LAUNCH_DMA(32) }
-#undef OESS_LAUNCH_DMA
+    size_t lds = (size_t)2 * (BM + bn) * 8 * 16;
+    if (lds < epi) lds = epi;
+    return take((bn == 128 ? OESS_ROUTE_DMA128_FASTK : (bn == 64 ? OESS_ROUTE_DMA64_FASTK : OESS_ROUTE_DMA32_FASTK)) + (fastk ? 0 : 1), grid, block, lds);
+}
+
+// plan.args with the call's pointers in place (a ConvLSTM call's a.out is its hidden output; the conv epilogue is not used)
+ConvArgs conv_bind(const ConvPlan& p, const ConvPtrs& q) {
+    ConvArgs a = p.args;
+    a.in = (const uint16_t*)q.in; a.w = (const uint16_t*)q.w; a.bias = q.bias;
+    a.out = q.out_f32 ? nullptr : (uint16_t*)(a.lstm_C ? q.lstm_h : q.out_bf16); a.out_f32 = q.out_f32;
+    a.residual = (const uint16_t*)q.residual;
+    a.stats = q.tile_stats;
+    a.lstm_prev = q.lstm_prev; a.lstm_cell = q.lstm_cell; a.lstm_h = (uint16_t*)q.lstm_h;
+    a.partial = OESS_ROUTE_KSPLIT(p.route) ? (float*)q.workspace : nullptr;
+    return a;
+}
+
+// The one place that names the kernels for launching: one case per OESS_ROUTE_* value.
+int conv_launch(const ConvPlan& p, const ConvPtrs& q, oess_stream_t stream) {
+    conv_set_attrs();
+    const ConvArgs a = conv_bind(p, q);
+    hipStream_t st = (hipStream_t)stream;
+#define OESS_CASE(route_, ...) case route_: hipLaunchKernelGGL((__VA_ARGS__), p.grid, p.block, p.lds, st, a); break;
+    switch (OESS_ROUTE_KERNEL(p.route)) {
+        OESS_CASE(OESS_ROUTE_SMALLCIN, conv_smallcin_kernel<5, 5>)
+        OESS_CASE(OESS_ROUTE_FALLBACK_128, conv_fwd_kernel<128>)
+        OESS_CASE(OESS_ROUTE_FALLBACK_64, conv_fwd_kernel<64>)
+        OESS_CASE(OESS_ROUTE_FALLBACK_32, conv_fwd_kernel<32>)
+        case OESS_ROUTE_S2_HALO: hipLaunchKernelGGL((conv5x5s2_halo_kernel<false>), p.grid, p.block, p.lds, st, a, S2Head{}); break;
+        OESS_CASE(OESS_ROUTE_SMALLMAP_RING, conv_fwd_dma_kernel<128, 128, 4, true, 0, 512>)
+        OESS_CASE(OESS_ROUTE_CONV3X3_W128, conv3x3_w128_kernel)
+        OESS_CASE(OESS_ROUTE_HALO3X3, conv3x3_halo_kernel<0>)
+        OESS_CASE(OESS_ROUTE_HALO3X3_LSTM, conv3x3_halo_kernel<1>)
+        OESS_CASE(OESS_ROUTE_LSTM_FASTK, conv_fwd_dma_kernel<128, 128, 2, true, 1>)
+        OESS_CASE(OESS_ROUTE_LSTM_SLOWK, conv_fwd_dma_kernel<128, 128, 2, false, 1>)
+        OESS_CASE(OESS_ROUTE_SPLITK_FASTK, conv_fwd_dma_kernel<128, 128, 2, true>)        // (+ the reduce below)
+        OESS_CASE(OESS_ROUTE_SPLITK_SLOWK, conv_fwd_dma_kernel<128, 128, 2, false>)
+        OESS_CASE(OESS_ROUTE_CONV1X1_W128, conv1x1_w128_kernel)
+        OESS_CASE(OESS_ROUTE_TILE256, conv_fwd_dma_kernel<256, 256, 2, true>)
+        OESS_CASE(OESS_ROUTE_RING32, conv_fwd_dma32_kernel<128, true, 0, 3>)
+        OESS_CASE(OESS_ROUTE_TILE64_FASTK, conv_fwd_dma_kernel<64, 128, 2, true>)
+        OESS_CASE(OESS_ROUTE_TILE64_SLOWK, conv_fwd_dma_kernel<64, 128, 2, false>)
+        OESS_CASE(OESS_ROUTE_DMA128_FASTK, conv_fwd_dma_kernel<128, 128, 2, true>)
+        OESS_CASE(OESS_ROUTE_DMA128_SLOWK, conv_fwd_dma_kernel<128, 128, 2, false>)
+        OESS_CASE(OESS_ROUTE_DMA64_FASTK, conv_fwd_dma_kernel<128, 64, 2, true>)
+        OESS_CASE(OESS_ROUTE_DMA64_SLOWK, conv_fwd_dma_kernel<128, 64, 2, false>)
+        OESS_CASE(OESS_ROUTE_DMA32_FASTK, conv_fwd_dma_kernel<128, 32, 2, true>)
+        OESS_CASE(OESS_ROUTE_DMA32_SLOWK, conv_fwd_dma_kernel<128, 32, 2, false>)
+        default: return OESS_EINVAL;
     }
-    if (route) return OESS_EINVAL;          // not reached: a query must have returned at an OESS_ROUTE above
+#undef OESS_CASE
+    if (OESS_ROUTE_KSPLIT(p.route)) hipLaunchKernelGGL(splitk_reduce_kernel, dim3(a.tiles_m, (a.Cout + 63) / 64), dim3(256), 0, st, a);
     OESS_HIP(hipGetLastError());
     return OESS_OK;
-#undef OESS_ROUTE
 }
+
+ConvCall conv_call(int B, int H, int W, int Cin, int Cout, int R, int S, int stride, int pad, int dil, int relu, bool has_bias, bool has_residual, bool out_is_f32,
+                   bool with_tile_stats, bool out_aligned16, long long in_pix_stride, long long out_pix_stride, long long res_pix_stride, size_t workspace_bytes) {
+    return ConvCall{B, H, W, Cin, Cout, R, S, stride, pad, dil, relu, has_bias, has_residual, out_is_f32, with_tile_stats, out_aligned16,
+                    in_pix_stride, out_pix_stride, res_pix_stride, 0, 0, workspace_bytes};
+}
+ConvCall lstm_call(int B, int H, int W, int Cin, long long in_pix_stride, int C_hidden, int R, int S, int pad, long long hidden_pix_stride) {
+    ConvCall c = conv_call(B, H, W, Cin, 4 * C_hidden, R, S, 1, pad, 1, 0, false, false, false, false, true, in_pix_stride, 0, 0, 0);
+    c.C_hidden = C_hidden; c.hidden_pix_stride = hidden_pix_stride;
+    return c;
+}
+// Grouped ConvLSTM launches run their problems concurrently: true when an output of one problem (hidden state, cell state)
+// overlaps an input or an output of another, or a problem's hidden output its own input (the single-problem rule).  tiled_cell:
+// the cell is in the w128 kernel's padded layout (oess_convlstm_w128_cell_bytes), and must not overlap its own input either.
+bool lstm_group_overlap(const oess_convlstm_desc_t* d, int n, bool tiled_cell) {
+    auto span = [](const void* p, long long pixels, long long stride, int c, const char** lo, const char** hi) {
+        *lo = (const char*)p; *hi = *lo + (pixels - 1) * stride * 2 + (long long)c * 2;
+    };
+    auto cell_bytes = [tiled_cell](long long px, int C) { return tiled_cell ? (long long)oess_convlstm_w128_cell_bytes(px, C) : px * C * 4; };
+    for (int i = 0; i < n; ++i) {
+        const long long px = (long long)d[i].B * d[i].H * d[i].W;
+        const char *h0, *h1, *c0 = (const char*)d[i].cell, *c1 = c0 + cell_bytes(px, d[i].C_hidden);
+        span(d[i].hidden, px, d[i].hidden_pix_stride, d[i].C_hidden, &h0, &h1);
+        for (int j = 0; j < n; ++j) {
+            const long long pj = (long long)d[j].B * d[j].H * d[j].W;
+            const char *i0, *i1, *g0, *g1, *e0 = (const char*)d[j].cell, *e1 = e0 + cell_bytes(pj, d[j].C_hidden);
+            span(d[j].in, pj, d[j].in_pix_stride, d[j].Cin, &i0, &i1);
+            span(d[j].hidden, pj, d[j].hidden_pix_stride, d[j].C_hidden, &g0, &g1);
+            if (h0 < i1 && i0 < h1) return true;
+            if ((j != i || tiled_cell) && c0 < i1 && i0 < c1) return true;
+            if (j != i && ((h0 < g1 && g0 < h1) || (c0 < e1 && e0 < c1))) return true;
+        }
+    }
+    return false;
+}
+// the row-halo ConvLSTM kernel's arguments for one problem of a grouped launch; false when the problem's plan is another kernel
+bool lstm_group_args(const oess_convlstm_desc_t& d, ConvArgs* a) {
+    ConvPlan p;
+    if (!d.w_packed_gates ||            // (the callers have checked the other pointers)
+        conv_plan(lstm_call(d.B, d.H, d.W, d.Cin, d.in_pix_stride, d.C_hidden, d.R, d.S, d.pad, d.hidden_pix_stride), &p) != OESS_OK ||
+        p.route != OESS_ROUTE_HALO3X3_LSTM)
+        return false;
+    *a = conv_bind(p, ConvPtrs{d.in, d.w_packed_gates, d.bias, nullptr, nullptr, nullptr, nullptr, d.prev_cell, d.cell, d.hidden, nullptr});
+    return true;
+}
+bool aligned16(const void* p) { return (((uintptr_t)p) & 15) == 0; }
 }  // namespace
 
 extern "C" {
@@ -2368,44 +2398,39 @@ int oess_conv2d_fwd_bf16(const void* in, long long in_pix_stride, int B, int H, 
                          const void* residual, long long res_pix_stride, void* out_bf16, float* out_f32,
                          long long out_pix_stride, float* tile_stats, void* workspace, size_t workspace_bytes,
                          oess_stream_t stream) {
-    return conv_fwd_impl(in, in_pix_stride, B, H, W, Cin, w_packed, bias, Cout, R, S, stride, pad, dil, relu, residual,
-                         res_pix_stride, out_bf16, out_f32, out_pix_stride, tile_stats, nullptr, stream, workspace, workspace_bytes);
+    if (!in || !w_packed || (!out_bf16 && !out_f32)) return OESS_EINVAL;
+    ConvPlan p;
+    const int rc = conv_plan(conv_call(B, H, W, Cin, Cout, R, S, stride, pad, dil, relu, bias, residual, out_f32, tile_stats, aligned16(out_bf16),
+                                       in_pix_stride, out_pix_stride, res_pix_stride, workspace ? workspace_bytes : 0), &p);
+    if (rc != OESS_OK) return rc;
+    return conv_launch(p, ConvPtrs{in, w_packed, bias, residual, out_bf16, out_f32, tile_stats, nullptr, nullptr, nullptr, workspace}, stream);
 }
 
 size_t oess_conv2d_fwd_workspace_bytes(int B, int H, int W, int Cin, int Cout, int R, int S, int stride, int pad, int dil,
                                        int with_tile_stats, int out_is_f32) {
-    // runs the dispatch rules of oess_conv2d_fwd_bf16 on dummy (never dereferenced) pointers up to the split-K decision
-    size_t need = 0;
-    static const char dummy[16] = {0};
-    const int rc = conv_fwd_impl(dummy, Cin, B, H, W, Cin, dummy, nullptr, Cout, R, S, stride, pad, dil, 0, nullptr, 0,
-                                 out_is_f32 ? nullptr : (void*)dummy, out_is_f32 ? (float*)dummy : nullptr, (Cout + 7) / 8 * 8,
-                                 with_tile_stats ? (float*)dummy : nullptr, nullptr, nullptr, nullptr, 0, &need);
-    return rc == OESS_OK ? need : 0;
+    // the plan of oess_conv2d_fwd_bf16 with any workspace on offer.  The query has no strides, pointers or epilogue flags, so it
+    // assumes a dense input, an output of pixel stride ceil8(Cout) at a 16-byte aligned address, and no bias / ReLU / residual
+    // (what the dummy call of the earlier implementation amounted to)
+    ConvPlan p;
+    const int rc = conv_plan(conv_call(B, H, W, Cin, Cout, R, S, stride, pad, dil, 0, false, false, out_is_f32, with_tile_stats, true, Cin,
+                                       (Cout + 7) / 8 * 8, 0, ~(size_t)0), &p);
+    return rc == OESS_OK ? p.want_workspace : 0;
 }
 
 int oess_conv2d_fwd_route(int B, int H, int W, int Cin, int Cout, int R, int S, int stride, int pad, int dil, int has_bias,
                           int relu, int has_residual, int out_is_f32, int with_tile_stats, long long in_pix_stride,
                           long long out_pix_stride, long long res_pix_stride, int out_aligned16, size_t workspace_bytes) {
-    // the launch's own walk on dummy (never dereferenced) pointers: only their nullness and the output's alignment matter
-    alignas(16) static char dummy[32] = {0};
-    char* out = dummy + (out_aligned16 ? 0 : 8);
-    int route = 0;
-    const int rc = conv_fwd_impl(dummy, in_pix_stride, B, H, W, Cin, dummy, has_bias ? (const float*)dummy : nullptr, Cout, R, S,
-                                 stride, pad, dil, relu, has_residual ? (const void*)dummy : nullptr, res_pix_stride,
-                                 out_is_f32 ? nullptr : (void*)out, out_is_f32 ? (float*)out : nullptr, out_pix_stride,
-                                 with_tile_stats ? (float*)dummy : nullptr, nullptr, nullptr, workspace_bytes ? (void*)dummy : nullptr,
-                                 workspace_bytes, nullptr, nullptr, &route);
-    return rc == OESS_OK ? route : rc;
+    ConvPlan p;         // the plan the launch itself executes
+    const int rc = conv_plan(conv_call(B, H, W, Cin, Cout, R, S, stride, pad, dil, relu, has_bias, has_residual, out_is_f32, with_tile_stats,
+                                       out_aligned16, in_pix_stride, out_pix_stride, res_pix_stride, workspace_bytes), &p);
+    return rc == OESS_OK ? p.route : rc;
 }
 
 int oess_convlstm_fused_route(int B, int H, int W, int Cin, long long in_pix_stride, int C_hidden, int R, int S, int pad,
                               long long hidden_pix_stride) {
-    alignas(16) static char dummy[32] = {0};
-    LstmOut l{nullptr, (float*)dummy, dummy, hidden_pix_stride, C_hidden};
-    int route = 0;
-    const int rc = conv_fwd_impl(dummy, in_pix_stride, B, H, W, Cin, dummy, nullptr, 4 * C_hidden, R, S, 1, pad, 1, 0, nullptr, 0,
-                                 nullptr, nullptr, 0, nullptr, &l, nullptr, nullptr, 0, nullptr, nullptr, &route);
-    return rc == OESS_OK ? route : rc;
+    ConvPlan p;
+    const int rc = conv_plan(lstm_call(B, H, W, Cin, in_pix_stride, C_hidden, R, S, pad, hidden_pix_stride), &p);
+    return rc == OESS_OK ? p.route : rc;
 }
 
 int oess_conv2d_route_count(void) { return OESS_ROUTE_COUNT; }
@@ -2428,44 +2453,27 @@ const char* oess_conv2d_route_name(int route) {
 int oess_convlstm_fused_bf16(const void* in, long long in_pix_stride, int B, int H, int W, int Cin, const void* w_packed_gates,
                              const float* bias, int C_hidden, int R, int S, int pad, const float* prev_cell, float* cell,
                              void* hidden, long long hidden_pix_stride, oess_stream_t stream) {
-    if (!in || !hidden) return OESS_EINVAL;
+    if (!in || !hidden || !w_packed_gates || !cell) return OESS_EINVAL;
     {   // the hidden output must not alias the convolution input (neighbouring tiles still read the old state)
         const char* i0 = (const char*)in; const char* i1 = i0 + ((long long)B * H * W - 1) * in_pix_stride * 2 + (long long)Cin * 2;
         const char* h0 = (const char*)hidden; const char* h1 = h0 + ((long long)B * H * W - 1) * hidden_pix_stride * 2 + (long long)C_hidden * 2;
         if (h0 < i1 && i0 < h1) return OESS_EINVAL;
     }
-    LstmOut l{prev_cell, cell, hidden, hidden_pix_stride, C_hidden};
-    return conv_fwd_impl(in, in_pix_stride, B, H, W, Cin, w_packed_gates, bias, 4 * C_hidden, R, S, 1, pad, 1, 0, nullptr, 0,
-                         nullptr, nullptr, 0, nullptr, &l, stream);
+    ConvPlan p;
+    const int rc = conv_plan(lstm_call(B, H, W, Cin, in_pix_stride, C_hidden, R, S, pad, hidden_pix_stride), &p);
+    if (rc != OESS_OK) return rc;
+    return conv_launch(p, ConvPtrs{in, w_packed_gates, bias, nullptr, nullptr, nullptr, nullptr, prev_cell, cell, hidden, nullptr}, stream);
 }
 
 int oess_convlstm_fused_group_bf16(const oess_convlstm_desc_t* d, int n, oess_stream_t stream) {
     if (!d || n <= 0 || n > 3) return OESS_EINVAL;
-    auto span = [](const void* p, long long pixels, long long stride, int c, const char** lo, const char** hi) {
-        *lo = (const char*)p; *hi = *lo + (pixels - 1) * stride * 2 + (long long)c * 2;
-    };
-    for (int i = 0; i < n; ++i) {
+    for (int i = 0; i < n; ++i)
         if (!d[i].in || !d[i].hidden || !d[i].cell || d[i].B <= 0 || d[i].H <= 0 || d[i].W <= 0) return OESS_EINVAL;
-        const long long px = (long long)d[i].B * d[i].H * d[i].W;
-        const char *h0, *h1, *c0 = (const char*)d[i].cell, *c1 = c0 + px * d[i].C_hidden * 4;
-        span(d[i].hidden, px, d[i].hidden_pix_stride, d[i].C_hidden, &h0, &h1);
-        for (int j = 0; j < n; ++j) {       // the problems run concurrently: no output of one may overlap anything of another
-            const long long pj = (long long)d[j].B * d[j].H * d[j].W;
-            const char *i0, *i1, *g0, *g1, *e0 = (const char*)d[j].cell, *e1 = e0 + pj * d[j].C_hidden * 4;
-            span(d[j].in, pj, d[j].in_pix_stride, d[j].Cin, &i0, &i1);
-            span(d[j].hidden, pj, d[j].hidden_pix_stride, d[j].C_hidden, &g0, &g1);
-            if (h0 < i1 && i0 < h1) return OESS_EINVAL;                   // (j == i: the single-problem rule)
-            if (j != i && ((h0 < g1 && g0 < h1) || (c0 < e1 && e0 < c1) || (c0 < i1 && i0 < c1))) return OESS_EINVAL;
-        }
-    }
+    if (lstm_group_overlap(d, n, false)) return OESS_EINVAL;
+    // one launch iff every problem's own plan is the row-halo kernel; otherwise the problems go one by one, each on its plan's route
     ConvArgs args[3];
     bool grouped = n >= 2;
-    for (int i = 0; i < n && grouped; ++i) {
-        LstmOut l{d[i].prev_cell, d[i].cell, d[i].hidden, d[i].hidden_pix_stride, d[i].C_hidden};
-        grouped = conv_fwd_impl(d[i].in, d[i].in_pix_stride, d[i].B, d[i].H, d[i].W, d[i].Cin, d[i].w_packed_gates, d[i].bias,
-                                4 * d[i].C_hidden, d[i].R, d[i].S, 1, d[i].pad, 1, 0, nullptr, 0, nullptr, nullptr, 0, nullptr, &l,
-                                stream, nullptr, 0, nullptr, &args[i]) == OESS_OK;
-    }
+    for (int i = 0; i < n && grouped; ++i) grouped = lstm_group_args(d[i], &args[i]);
     if (!grouped) {
         for (int i = 0; i < n; ++i) {
             const int rc = oess_convlstm_fused_bf16(d[i].in, d[i].in_pix_stride, d[i].B, d[i].H, d[i].W, d[i].Cin, d[i].w_packed_gates,
@@ -2475,6 +2483,7 @@ int oess_convlstm_fused_group_bf16(const oess_convlstm_desc_t* d, int n, oess_st
         }
         return OESS_OK;
     }
+    conv_set_attrs();
     int order[3] = {0, 1, 2};                  // longest K first: the launch ends on the short tiles
     for (int i = 1; i < n; ++i)
         for (int j = i; j > 0 && args[order[j]].Kpad > args[order[j - 1]].Kpad; --j) { const int t = order[j]; order[j] = order[j - 1]; order[j - 1] = t; }
@@ -2633,9 +2642,6 @@ int oess_convlstm_w128_cell_relayout(const float* src, float* dst, long long pix
 
 int oess_convlstm_w128_group_bf16(const oess_convlstm_desc_t* d, int n, oess_stream_t stream) {
     if (!d || n <= 0 || n > 3) return OESS_EINVAL;
-    auto span = [](const void* p, long long pixels, long long stride, int c, const char** lo, const char** hi) {
-        *lo = (const char*)p; *hi = *lo + (pixels - 1) * stride * 2 + (long long)c * 2;
-    };
     int ctot = 0;
     for (int i = 0; i < n; ++i) {
         if (!d[i].in || !d[i].hidden || !d[i].cell || d[i].B <= 0 || d[i].H < 8 || d[i].W <= 0 || d[i].R != 3 || d[i].S != 3 || d[i].pad != 1 ||
@@ -2649,26 +2655,13 @@ int oess_convlstm_w128_group_bf16(const oess_convlstm_desc_t* d, int n, oess_str
             const char *p0 = (const char*)d[i].prev_cell, *c0 = (const char*)d[i].cell;
             if (p0 < c0 + cb && c0 < p0 + cb) return OESS_EINVAL;         // a tile updates its own block in place or elsewhere, not a shifted copy
         }
-        const char *h0, *h1, *c0 = (const char*)d[i].cell, *c1 = c0 + cb;
-        span(d[i].hidden, px, d[i].hidden_pix_stride, d[i].C_hidden, &h0, &h1);
-        if ((h1 - h0) >= 0x7fffffffll) return OESS_EINVAL;
-        for (int j = 0; j < n; ++j) {
-            const long long pj = (long long)d[j].B * d[j].H * d[j].W;
-            const char *i0, *i1, *g0, *g1, *e0 = (const char*)d[j].cell, *e1 = e0 + oess_convlstm_w128_cell_bytes(pj, d[j].C_hidden);
-            span(d[j].in, pj, d[j].in_pix_stride, d[j].Cin, &i0, &i1);
-            span(d[j].hidden, pj, d[j].hidden_pix_stride, d[j].C_hidden, &g0, &g1);
-            if (h0 < i1 && i0 < h1) return OESS_EINVAL;
-            if (c0 < i1 && i0 < c1) return OESS_EINVAL;
-            if (j != i && ((h0 < g1 && g0 < h1) || (c0 < e1 && e0 < c1))) return OESS_EINVAL;
-        }
+        if ((px - 1) * d[i].hidden_pix_stride * 2 + (long long)d[i].C_hidden * 2 >= 0x7fffffffll) return OESS_EINVAL;
     }
+    if (lstm_group_overlap(d, n, true)) return OESS_EINVAL;
     if (ctot > W128_BIAS_FLOATS) return OESS_EINVAL;
     ConvArgs args[3];
     for (int i = 0; i < n; ++i) {
-        LstmOut l{d[i].prev_cell, d[i].cell, d[i].hidden, d[i].hidden_pix_stride, d[i].C_hidden};
-        if (conv_fwd_impl(d[i].in, d[i].in_pix_stride, d[i].B, d[i].H, d[i].W, d[i].Cin, d[i].w_packed_gates, d[i].bias, 4 * d[i].C_hidden,
-                          3, 3, 1, 1, 1, 0, nullptr, 0, nullptr, nullptr, 0, nullptr, &l, stream, nullptr, 0, nullptr, &args[i]) != OESS_OK)
-            return OESS_EINVAL;
+        if (!lstm_group_args(d[i], &args[i])) return OESS_EINVAL;
         ConvArgs& a = args[i];
         // halo rows of a 256-pixel tile; a tile may wrap into the next image at most once (rows per tile <= H)
         if (a.Kpad != 9 * a.Cin || (1 + 255 + ((256 + a.W - 2) / a.W) + 1 + 1) > W128_HROWS || ((256 + a.W - 2) / a.W + 1) > a.H || !a.mg_w || !a.mg_wd)
@@ -2676,6 +2669,7 @@ int oess_convlstm_w128_group_bf16(const oess_convlstm_desc_t* d, int n, oess_str
         a.tiles_m = (a.M + 255) / 256;
         a.tiles_n = a.Cout / 256;
     }
+    conv_set_attrs();
     int order[3] = {0, 1, 2};                  // longest K first
     for (int i = 1; i < n; ++i)
         for (int j = i; j > 0 && args[order[j]].Kpad > args[order[j - 1]].Kpad; --j) { const int t = order[j]; order[j] = order[j - 1]; order[j - 1] = t; }
@@ -2742,25 +2736,29 @@ int oess_conv5x5s2_group_bf16(const oess_conv_s2_desc_t* d, int n, oess_stream_t
                 if (!(delta >= cb[i][1] && delta + cb[1 - i][k] <= S)) return OESS_EINVAL;
             }
     }
-    ConvArgs args[2];
+    // one launch iff both problems' own plans are the stride-2 halo kernel; otherwise each goes alone on its plan's route
+    ConvPlan plan[2];
+    ConvPtrs q[2];
+    int rc[2];
     bool grouped = n == 2;
-    for (int i = 0; i < n && grouped; ++i)
-        grouped = conv_fwd_impl(d[i].in, d[i].in_pix_stride, d[i].B, d[i].H, d[i].W, d[i].Cin, d[i].w_packed, d[i].bias, d[i].Cout, 5, 5, 2,
-                                2, 1, d[i].relu, nullptr, 0, d[i].out, nullptr, d[i].out_pix_stride, nullptr, nullptr, stream, nullptr, 0,
-                                nullptr, &args[i]) == OESS_OK;
+    for (int i = 0; i < n; ++i) {
+        q[i] = ConvPtrs{d[i].in, d[i].w_packed, d[i].bias, nullptr, d[i].out, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+        rc[i] = conv_plan(conv_call(d[i].B, d[i].H, d[i].W, d[i].Cin, d[i].Cout, 5, 5, 2, 2, 1, d[i].relu, d[i].bias, false, false, false,
+                                    aligned16(d[i].out), d[i].in_pix_stride, d[i].out_pix_stride, 0, 0), &plan[i]);
+        grouped = grouped && rc[i] == OESS_OK && plan[i].route == OESS_ROUTE_S2_HALO;
+    }
     if (!grouped) {
         for (int i = 0; i < n; ++i) {
-            const int rc = conv_fwd_impl(d[i].in, d[i].in_pix_stride, d[i].B, d[i].H, d[i].W, d[i].Cin, d[i].w_packed, d[i].bias,
-                                         d[i].Cout, 5, 5, 2, 2, 1, d[i].relu, nullptr, 0, d[i].out, nullptr, d[i].out_pix_stride, nullptr,
-                                         nullptr, stream);
-            if (rc != OESS_OK) return rc;
+            const int r = rc[i] != OESS_OK ? rc[i] : conv_launch(plan[i], q[i], stream);
+            if (r != OESS_OK) return r;
         }
         return OESS_OK;
     }
+    conv_set_attrs();
     S2Group g;
     memset(&g, 0, sizeof(g));
-    const int first = args[1].Cin > args[0].Cin ? 1 : 0;           // longest K first
-    g.a[0] = args[first]; g.a[1] = args[1 - first];
+    const int first = plan[1].args.Cin > plan[0].args.Cin ? 1 : 0;           // longest K first
+    g.a[0] = conv_bind(plan[first], q[first]); g.a[1] = conv_bind(plan[1 - first], q[1 - first]);
     g.start8[0] = 0;
     g.start8[1] = (g.a[0].tiles_m * g.a[0].tiles_n + 7) / 8;
     g.start8[2] = g.start8[1] + (g.a[1].tiles_m * g.a[1].tiles_n + 7) / 8;
@@ -2780,7 +2778,7 @@ static int e2vid_head_enc0_launch(const S2Head& hd, int B, int H, int W, const v
     a.Kpad = (25 * 32 + BK - 1) / BK * BK;
     a.M = B * a.Ho * a.Wo; a.relu = enc_relu;
     a.tiles_n = 1;
-    a.tiles_m = B * ((a.Ho + S2_PH - 1) / S2_PH) * ((a.Wo + S2_PW - 1) / S2_PW);
+    a.tiles_m = s2_tiles_m(B, a.Ho, a.Wo);
     hipLaunchKernelGGL((conv5x5s2_halo_kernel<true>), dim3(a.tiles_m), dim3(256), S2_LDS_FUSED, (hipStream_t)stream, a, hd);
     OESS_HIP(hipGetLastError());
     return OESS_OK;

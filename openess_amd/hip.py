@@ -597,6 +597,7 @@ def conv2d_nhwc(x, packed, bias, Cout, R, S, stride=1, pad=0, dil=1, relu=False,
     x's channel count must be a multiple of 8 (zero-padded channels; packed weights are zero there).
     allow_splitk=False withholds the scratch of the split-K form (small-M / long-K layers): one pass, for A/B tests."""
     lib = _lib.load()
+    e0 = None if _CONV_TIMING is None or Cout <= 64 else _timing_start(lstm=False)
     _need_gpu(x, packed)
     B, H, W, Cin, ps_in, out, is_f32, ps_out, ps_res, need = _conv_marshal(x, Cout, R, S, stride, pad, dil, residual, out, out_f32,
                                                                            tile_stats, allow_splitk, True)
@@ -611,6 +612,8 @@ def conv2d_nhwc(x, packed, bias, Cout, R, S, stride=1, pad=0, dil=1, relu=False,
                                         dil, int(relu), _ptr(residual), ps_res, o_bf16, o_f32, ps_out, _ptr(tile_stats),
                                         _ptr(ws), wsn, _stream()),
                "oess_conv2d_fwd_bf16")
+    if e0 is not None:
+        _timing_stop(e0, (H, W, Cin, Cout, R, stride, dil), 2.0 * B * out.shape[1] * out.shape[2] * Cout * Cin * R * S)
     return out
 
 
@@ -701,13 +704,7 @@ def e2vid_events_head_enc0(events, c0, cs, normalize, head_packed, head_bias, he
     _, _, _, _, ops = _nhwc_geom(out)
     if tuple(out.shape) != (B, Ho, Wo, 64):
         raise ValueError(f"bad output shape {tuple(out.shape)} != {(B, Ho, Wo, 64)}")
-    stats = None
-    if normalize and Ct > cs and Ct % cs == 0 and c0 % cs == 0:
-        stats = masked_stats_slices(events, cs, index=c0 // cs)
-    elif normalize:
-        stats = torch.empty(lib.oess_masked_stats_doubles(1), dtype=torch.float64, device=events.device)
-        _lib.check(lib.oess_masked_stats_slice_f32(_ptr(events), B, Ct, c0, cs, H * W, _ptr(stats), _stream()),
-                   "oess_masked_stats_slice_f32")
+    stats = _slice_stats(events, c0, cs) if normalize else None
     _lib.check(lib.oess_e2vid_events_head_enc0_bf16(_ptr(events), B, Ct, c0, cs, H, W, _ptr(stats), int(bool(normalize)),
                                                     _ptr(head_packed), _ptr(head_bias), int(bool(head_relu)), _ptr(enc_packed),
                                                     _ptr(enc_bias), int(bool(enc_relu)), _ptr(out), ops, _stream()),
@@ -736,6 +733,7 @@ def convlstm_fused(xh, packed_gates, bias, cell, hidden_out, k, pad, prev_cell_i
     (NHWC bf16) + cell update; `packed_gates` = pack_conv_weight(Gates.weight, flip=2) (gate-interleaved rows).
     cell: fp32 [B,H,W,C] updated in place; hidden_out: bf16 NHWC view [B,H,W,C] that must NOT overlap xh."""
     lib = _lib.load()
+    e0 = None if _CONV_TIMING is None else _timing_start(lstm=True)
     _need_gpu(xh, packed_gates, cell, hidden_out)
     B, H, W, Cin, ps = _nhwc_geom(xh)
     _, _, _, C, hs = _nhwc_geom(hidden_out)
@@ -746,6 +744,8 @@ def convlstm_fused(xh, packed_gates, bias, cell, hidden_out, k, pad, prev_cell_i
     _lib.check(lib.oess_convlstm_fused_bf16(_ptr(xh), ps, B, H, W, Cin, _ptr(packed_gates), None if bias is None else _ptr(bias),
                                             C, k, k, pad, None if prev_cell_is_zero else _ptr(cell), _ptr(cell),
                                             _ptr(hidden_out), hs, _stream()), "oess_convlstm_fused_bf16")
+    if e0 is not None:
+        _timing_stop(e0, (H, W, Cin, 4 * C, k, 1, "lstm"), 2.0 * B * H * W * 4 * C * Cin * k * k)   # the gate convolution's FLOPs only
     return hidden_out
 
 
@@ -767,43 +767,46 @@ def convlstm_w128_cell_relayout(src, pixels, C, to_tiled):
     return dst
 
 
-def convlstm_w128_group(problems):
-    """oess_convlstm_w128_group_bf16: `problems` as for convlstm_fused_group, except that `cell` is a flat fp32 tensor of
-    convlstm_w128_cell_elems(B*H*W, C) elements in the w128-tiled layout.  Returns False (nothing launched) when the kernel does not
-    take one of the problems; the caller then uses convlstm_fused_group on NHWC cells."""
-    lib = _lib.load()
+def _convlstm_descs(problems, name, cell_elems):
+    """The descriptor array of a grouped ConvLSTM launch from `problems` (tuples as for convlstm_fused_group), with the by-shape
+    keys and the FLOPs of its timing entry: (descs, keys, flops).  cell_elems(pixels, C) = the fp32 elements the launch expects in
+    `cell` (None: it does not take that C); None is returned at the first cell that is not such a contiguous fp32 tensor."""
     n = len(problems)
     if not 1 <= n <= 3:
-        raise ValueError("convlstm_w128_group: 1..3 problems")
+        raise ValueError(f"{name}: 1..3 problems")
     descs = (_lib.ConvLstmDesc * n)()
     flops, keys = 0.0, []
     for d, (xh, packed_gates, bias, cell, hidden_out, k, pad, prev_zero) in zip(descs, problems):
         _need_gpu(xh, packed_gates, cell, hidden_out)
         B, H, W, Cin, ps = _nhwc_geom(xh)
         _, _, _, C, hs = _nhwc_geom(hidden_out)
-        if cell.dtype != torch.float32 or not cell.is_contiguous() or cell.numel() != convlstm_w128_cell_elems(B * H * W, C) or C % 64:
-            return False
+        if cell.dtype != torch.float32 or not cell.is_contiguous() or cell.numel() != cell_elems(B * H * W, C):
+            return None
         if bias is not None and (bias.dtype != torch.float32 or not bias.is_contiguous() or bias.numel() != 4 * C):
-            raise ValueError("convlstm_w128_group: bias must be contiguous fp32 [4C]")
+            raise ValueError(f"{name}: bias must be contiguous fp32 [4C]")
         d.in_, d.in_pix_stride, d.B, d.H, d.W, d.Cin = _ptr(xh), ps, B, H, W, Cin
         d.w_packed_gates, d.bias, d.C_hidden, d.R, d.S, d.pad = _ptr(packed_gates), _ptr(bias), C, k, k, pad
         d.prev_cell, d.cell, d.hidden, d.hidden_pix_stride = (None if prev_zero else _ptr(cell)), _ptr(cell), _ptr(hidden_out), hs
-        fl = 2.0 * B * H * W * 4 * C * Cin * k * k
-        flops += fl
-        keys.append(((H, W, Cin, 4 * C, k, 1, "lstm"), fl))
-    t = _CONV_TIMING
-    if t is not None:
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-    rc = lib.oess_convlstm_w128_group_bf16(ctypes.addressof(descs), n, _stream())
+        flops += 2.0 * B * H * W * 4 * C * Cin * k * k
+        keys.append((H, W, Cin, 4 * C, k, 1, "lstm"))
+    return descs, ("group",) + tuple(keys), flops
+
+
+def convlstm_w128_group(problems):
+    """oess_convlstm_w128_group_bf16: `problems` as for convlstm_fused_group, except that `cell` is a flat fp32 tensor of
+    convlstm_w128_cell_elems(B*H*W, C) elements in the w128-tiled layout.  Returns False (nothing launched) when the kernel does not
+    take one of the problems; the caller then uses convlstm_fused_group on NHWC cells."""
+    lib = _lib.load()
+    m = _convlstm_descs(problems, "convlstm_w128_group", lambda px, C: None if C % 64 else convlstm_w128_cell_elems(px, C))
+    if m is None:
+        return False
+    e0 = None if _CONV_TIMING is None else _timing_start(lstm=True)
+    rc = lib.oess_convlstm_w128_group_bf16(ctypes.addressof(m[0]), len(problems), _stream())
     if rc == -22:                     # OESS_EINVAL: geometry not taken, nothing launched
         return False
     _lib.check(rc, "oess_convlstm_w128_group_bf16")
-    if t is not None:
-        e1.record()
-        t["events"].append((e0, e1))
-        t["flops"] += flops
-        t.setdefault("keys", []).append((("group",) + tuple(k_[0] for k_ in keys), flops))
+    if e0 is not None:
+        _timing_stop(e0, m[1], m[2])
     return True
 
 
@@ -812,35 +815,13 @@ def convlstm_fused_group(problems):
     (xh, packed_gates, bias, cell, hidden_out, k, pad, prev_cell_is_zero) as for convlstm_fused.  Same results as calling
     convlstm_fused on each (the levels of E2VID's recurrent encoder on the skewed schedule, e2vid/model/unet.py mirror)."""
     lib = _lib.load()
-    n = len(problems)
-    if not 1 <= n <= 3:
-        raise ValueError("convlstm_fused_group: 1..3 problems")
-    descs = (_lib.ConvLstmDesc * n)()
-    flops, keys = 0.0, []
-    for d, (xh, packed_gates, bias, cell, hidden_out, k, pad, prev_zero) in zip(descs, problems):
-        _need_gpu(xh, packed_gates, cell, hidden_out)
-        B, H, W, Cin, ps = _nhwc_geom(xh)
-        _, _, _, C, hs = _nhwc_geom(hidden_out)
-        if cell.dtype != torch.float32 or not cell.is_contiguous() or cell.numel() != B * H * W * C:
-            raise ValueError("convlstm_fused_group: cell must be contiguous fp32 [B,H,W,C]")
-        if bias is not None and (bias.dtype != torch.float32 or not bias.is_contiguous() or bias.numel() != 4 * C):
-            raise ValueError("convlstm_fused_group: bias must be contiguous fp32 [4C]")
-        d.in_, d.in_pix_stride, d.B, d.H, d.W, d.Cin = _ptr(xh), ps, B, H, W, Cin
-        d.w_packed_gates, d.bias, d.C_hidden, d.R, d.S, d.pad = _ptr(packed_gates), _ptr(bias), C, k, k, pad
-        d.prev_cell, d.cell, d.hidden, d.hidden_pix_stride = (None if prev_zero else _ptr(cell)), _ptr(cell), _ptr(hidden_out), hs
-        fl = 2.0 * B * H * W * 4 * C * Cin * k * k
-        flops += fl
-        keys.append(((H, W, Cin, 4 * C, k, 1, "lstm"), fl))
-    t = _CONV_TIMING
-    if t is not None:
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-    _lib.check(lib.oess_convlstm_fused_group_bf16(ctypes.addressof(descs), n, _stream()), "oess_convlstm_fused_group_bf16")
-    if t is not None:
-        e1.record()
-        t["events"].append((e0, e1))
-        t["flops"] += flops
-        t.setdefault("keys", []).append((("group",) + tuple(k_[0] for k_ in keys), flops))
+    m = _convlstm_descs(problems, "convlstm_fused_group", lambda px, C: px * C)
+    if m is None:
+        raise ValueError("convlstm_fused_group: cell must be contiguous fp32 [B,H,W,C]")
+    e0 = None if _CONV_TIMING is None else _timing_start(lstm=True)
+    _lib.check(lib.oess_convlstm_fused_group_bf16(ctypes.addressof(m[0]), len(problems), _stream()), "oess_convlstm_fused_group_bf16")
+    if e0 is not None:
+        _timing_stop(e0, m[1], m[2])
     return [p[4] for p in problems]
 
 
@@ -867,16 +848,10 @@ def conv5x5s2_group(problems):
         if Cout > 64:
             flops += fl
             keys.append((H, W, Cin, Cout, 5, 2, 1))
-    t = _family_timing() if flops > 0 else None
-    if t is not None:
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
+    e0 = None if _CONV_TIMING is None or flops <= 0 else _timing_start(lstm=False)
     _lib.check(lib.oess_conv5x5s2_group_bf16(ctypes.addressof(descs), n, _stream()), "oess_conv5x5s2_group_bf16")
-    if t is not None:
-        e1.record()
-        t["events"].append((e0, e1))
-        t["flops"] += flops
-        t.setdefault("keys", []).append((("group",) + tuple(keys), flops))
+    if e0 is not None:
+        _timing_stop(e0, ("group",) + tuple(keys), flops)
     return [p[5] for p in problems]
 
 
@@ -908,6 +883,19 @@ def masked_stats_slices(events, cs, index=None):
     return stats if index is None else stats[index]
 
 
+def _slice_stats(events, c0, cs):
+    """The EventPreprocessor statistics of events[:, c0:c0+cs]: a row of the table of all slices when the tensor is a whole
+    number of cs-channel slices (masked_stats_slices), otherwise one launch for this slice alone."""
+    B, Ct, H, W = events.shape
+    if Ct > cs and Ct % cs == 0 and c0 % cs == 0:
+        return masked_stats_slices(events, cs, index=c0 // cs)
+    lib = _lib.load()
+    stats = torch.empty(lib.oess_masked_stats_doubles(1), dtype=torch.float64, device=events.device)
+    _lib.check(lib.oess_masked_stats_slice_f32(_ptr(events), B, Ct, c0, cs, H * W, _ptr(stats), _stream()),
+               "oess_masked_stats_slice_f32")
+    return stats
+
+
 def event_slice_to_nhwc8(events, c0, cs, normalize=True, out=None):
     """events: contiguous fp32 [B, Ctot, H, W]; returns logical [B, 8, H, W] channels_last bf16 holding the
     (optionally EventPreprocessor-normalised) slice events[:, c0:c0+cs], zero padded to 8 channels.
@@ -920,13 +908,7 @@ def event_slice_to_nhwc8(events, c0, cs, normalize=True, out=None):
     B, Ct, H, W = events.shape
     if out is None:
         out = torch.empty((B, H, W, 8), dtype=torch.bfloat16, device=events.device)
-    stats = None
-    if normalize and Ct > cs and Ct % cs == 0 and c0 % cs == 0:
-        stats = masked_stats_slices(events, cs, index=c0 // cs)
-    elif normalize:
-        stats = torch.empty(lib.oess_masked_stats_doubles(1), dtype=torch.float64, device=events.device)
-        _lib.check(lib.oess_masked_stats_slice_f32(_ptr(events), B, Ct, c0, cs, H * W, _ptr(stats), _stream()),
-                   "oess_masked_stats_slice_f32")
+    stats = _slice_stats(events, c0, cs) if normalize else None
     _lib.check(lib.oess_event_slice_to_nhwc8_bf16(_ptr(events), B, Ct, c0, cs, H * W, _ptr(stats), int(normalize),
                                                   _ptr(out), _stream()), "oess_event_slice_to_nhwc8_bf16")
     return out.permute(0, 3, 1, 2)
@@ -941,13 +923,27 @@ def conv_timing_begin(lstm_only=False):
     timed region (no sync inside it).  lstm_only: only the fused-ConvLSTM launches (the dominant kernel) -- an event record is a
     barrier packet of its own, ~2.8 us of idle queue each: 2 x 115 of them are 1.3 ms of a one-stream step."""
     global _CONV_TIMING
-    _CONV_TIMING = {"events": [], "flops": 0.0, "lstm_only": bool(lstm_only)}
+    _CONV_TIMING = {"events": [], "flops": 0.0, "keys": [], "lstm_only": bool(lstm_only)}
 
 
-def _family_timing():
-    """the timing record for a non-ConvLSTM launch of the family (None when only the dominant kernel is bracketed)"""
+def _timing_start(lstm):
+    """First half of the bracket around one launch of the family, for callers that have seen _CONV_TIMING set: the recorded
+    start event, or None when only the dominant kernel is bracketed and this is not a ConvLSTM launch."""
+    if _CONV_TIMING["lstm_only"] and not lstm:
+        return None
+    e0 = torch.cuda.Event(enable_timing=True)
+    e0.record()
+    return e0
+
+
+def _timing_stop(e0, key, flops):
+    """Second half: the end event, and the launch with its by-shape key and FLOPs into the timing record."""
+    e1 = torch.cuda.Event(enable_timing=True)
+    e1.record()
     t = _CONV_TIMING
-    return None if (t is None or t.get("lstm_only")) else t
+    t["events"].append((e0, e1))
+    t["flops"] += flops
+    t["keys"].append((key, flops))
 
 
 def conv_timing_end():
@@ -960,48 +956,10 @@ def conv_timing_end():
     times = [a.elapsed_time(b) for a, b in t["events"]]
     ms = sum(times)
     by = {}
-    for (k, fl), tm in zip(t.get("keys", []), times):
+    for (k, fl), tm in zip(t["keys"], times):
         e = by.setdefault(k, [0, 0.0, 0.0])
         e[0] += 1; e[1] += tm; e[2] += fl
     return {"ms": ms, "flops": t["flops"], "launches": len(t["events"]), "by_shape": by}
-
-
-_conv2d_nhwc_raw = conv2d_nhwc
-
-
-def conv2d_nhwc(x, packed, bias, Cout, R, S, stride=1, pad=0, dil=1, relu=False, residual=None, out=None,
-                out_f32=False, tile_stats=None, allow_splitk=True):
-    t = _family_timing()
-    if t is None or Cout <= 64:
-        return _conv2d_nhwc_raw(x, packed, bias, Cout, R, S, stride, pad, dil, relu, residual, out, out_f32, tile_stats, allow_splitk)
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    y = _conv2d_nhwc_raw(x, packed, bias, Cout, R, S, stride, pad, dil, relu, residual, out, out_f32, tile_stats, allow_splitk)
-    e1.record()
-    fl = 2.0 * y.shape[0] * y.shape[1] * y.shape[2] * Cout * x.shape[3] * R * S
-    t["events"].append((e0, e1))
-    t["flops"] += fl
-    t.setdefault("keys", []).append(((x.shape[1], x.shape[2], x.shape[3], Cout, R, stride, dil), fl))
-    return y
-
-
-_convlstm_fused_raw = convlstm_fused
-
-
-def convlstm_fused(xh, packed_gates, bias, cell, hidden_out, k, pad, prev_cell_is_zero=False):
-    t = _CONV_TIMING
-    if t is None:
-        return _convlstm_fused_raw(xh, packed_gates, bias, cell, hidden_out, k, pad, prev_cell_is_zero)
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    y = _convlstm_fused_raw(xh, packed_gates, bias, cell, hidden_out, k, pad, prev_cell_is_zero)
-    e1.record()
-    Cout = 4 * hidden_out.shape[3]
-    fl = 2.0 * xh.shape[0] * xh.shape[1] * xh.shape[2] * Cout * xh.shape[3] * k * k     # the gate convolution's FLOPs only
-    t["events"].append((e0, e1))
-    t["flops"] += fl
-    t.setdefault("keys", []).append(((xh.shape[1], xh.shape[2], xh.shape[3], Cout, k, 1, "lstm"), fl))
-    return y
 
 
 # ------------------------------------------------------------------------------------------ ViT pieces (MaskCLIP tower)

@@ -1,6 +1,6 @@
 """Shared convolution dispatch cases: every row is a full call description of hip.conv2d_nhwc (or hip.convlstm_fused) plus
 the kernel each of its call variants is MEANT to reach, by the OESS_ROUTE_* names of include/oess.h.
-tests/test_conv_routes.py (no GPU) asserts the library's own dispatch walk agrees and that the table reaches every route the
+tests/test_conv_routes.py (no GPU) asserts the library's own dispatch plan agrees and that the table reaches every route the
 library declares; tests/test_hip_conv_exact.py runs the same rows on the GPU, so a parity case cannot drift to another kernel
 without the CPU test failing first.
 

@@ -1,5 +1,5 @@
-"""Route coverage of the convolution dispatch (no GPU): oess_conv2d_fwd_route is the launch's own walk of conv_fwd_impl's
-rules stopped at the launch site, so these assertions pin which kernel every row of tests/conv_route_cases.py runs on, and that
+"""Route coverage of the convolution dispatch (no GPU): oess_conv2d_fwd_route is the route of the plan the launch itself
+executes (conv_plan), so these assertions pin which kernel every row of tests/conv_route_cases.py runs on, and that
 the rows together reach every kernel the library declares.  A new kernel without a row, or a threshold change that moves a
 parity case to another kernel, fails here on any machine."""
 import pytest
