@@ -677,6 +677,35 @@ int oess_instance_norm_fwd_f32(const oess_f32_view_t* in, int B, int H, int W, i
 int oess_upsample_nearest2x_concat_f32(const oess_f32_view_t* in, int B, int H, int W, int C, const oess_f32_view_t* skip,
                                        int C_skip, const oess_f32_view_t* out, oess_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------
+ * K16 fp32 DeepLabv3-R50 inference (models/deeplabv3.py:128-189 of the reference in its own arithmetic; frame2recon validation
+ * through val_logits(..., precision='fp32')).  Additions only: the ABI version stays.
+ *
+ * oess_conv2d_dilated_fwd_f32: oess_conv2d_fwd_f32 with a dilation and without its geometry limits: the same kernel, tap
+ *   (r, s) reads input row q stride - pad + r dilation.  dilation >= 1; any pad >= 0 that leaves Ho, Wo >= 1 with
+ *   Ho = (H' + 2 pad - dilation (R - 1) - 1) / stride + 1; R x S <= 25 taps, or the 7 x 7 stem (the one larger size a
+ *   network here has and a test runs; oess_conv2d_f32_packed_floats answers 0 for what is refused, as it did for e.g. 6 x 5); (R - 1) dilation and (S - 1) dilation <= 127 (the tap table
+ *   holds offsets in signed char).  Weight packing, epilogue (bias, residual, act) and summation order are those of
+ *   oess_conv2d_fwd_f32, which is this entry with dilation 1, R x S <= 25 and pad < R, S: bit-identical results.  With
+ *   dilation > 1 and the vector operand path a workgroup leaves out the K steps of every tap that reaches the map from none of
+ *   its pixels (exact zeros; at rate 36 on a 28 x 40 map six of nine taps never do).
+ * oess_maxpool3x3s2_fwd_f32: nn.MaxPool2d(3, 2, 1): in B x H x W x C -> out B x Ho x Wo x C, Ho = (H - 1) / 2 + 1.  Padding never
+ *   wins (-inf); a NaN in the window does (ATen).  16-byte loads / stores when C % 4 == 0 and both views have dense aligned channels.
+ * oess_global_avg_pool_fwd_f32: nn.AdaptiveAvgPool2d(1): in B x H x W x C -> out fp32 [B][C] (dense).  Two launches: per-range
+ *   sums (a thread's own chain of ceil(H W / ranges / rows) terms, ranges <= 64, rows = 4 .. 256 threads per channel, then a
+ *   fixed LDS tree) into ws, then the ranges in index order, divided by H W.  fp32 sums, no
+ *   atomics, bit-repeatable.  ws: oess_global_avg_pool_f32_workspace_bytes(B, H, W, C) bytes (0 for an impossible geometry;
+ *   B <= 65535), 16-byte aligned.
+ * ------------------------------------------------------------------------------------------ */
+int oess_conv2d_dilated_fwd_f32(const oess_f32_view_t* in, const oess_f32_view_t* in2, int B, int H, int W, int Cin, int upsample2x,
+                                const float* w_packed, const float* bias, int Cout, int R, int S, int stride, int pad, int dilation,
+                                int act, const oess_f32_view_t* residual, const oess_f32_view_t* out, oess_stream_t stream);
+int oess_maxpool3x3s2_fwd_f32(const oess_f32_view_t* in, int B, int H, int W, int C, const oess_f32_view_t* out,
+                              oess_stream_t stream);
+size_t oess_global_avg_pool_f32_workspace_bytes(int B, int H, int W, int C);
+int oess_global_avg_pool_fwd_f32(const oess_f32_view_t* in, int B, int H, int W, int C, float* out, void* ws, size_t ws_bytes,
+                                 oess_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -162,6 +162,11 @@ SIGNATURES = {
     "oess_instance_norm_f32_workspace_bytes": (c_sz, [c_int, c_int, c_int, c_int]),
     "oess_instance_norm_fwd_f32": (c_int, [c_view, c_int, c_int, c_int, c_int, c_f, c_int, c_view, c_view, c_vp, c_sz, c_vp]),
     "oess_upsample_nearest2x_concat_f32": (c_int, [c_view, c_int, c_int, c_int, c_int, c_view, c_int, c_view, c_vp]),
+    "oess_conv2d_dilated_fwd_f32": (c_int, [c_view, c_view, c_int, c_int, c_int, c_int, c_int, c_vp, c_vp, c_int, c_int, c_int, c_int,
+                                            c_int, c_int, c_int, c_view, c_view, c_vp]),
+    "oess_maxpool3x3s2_fwd_f32": (c_int, [c_view, c_int, c_int, c_int, c_int, c_view, c_vp]),
+    "oess_global_avg_pool_f32_workspace_bytes": (c_sz, [c_int, c_int, c_int, c_int]),
+    "oess_global_avg_pool_fwd_f32": (c_int, [c_view, c_int, c_int, c_int, c_int, c_vp, c_vp, c_sz, c_vp]),
 }
 
 _lib = None

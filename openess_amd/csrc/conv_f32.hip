@@ -7,6 +7,7 @@
 //   transposed conv:    ConvTranspose2d(k 5, stride 2, pad 2, output_padding 1) as four stride-1 phase sub-convolutions
 //                       (output parity py, px; 3 / 2 taps per axis), input row = q + 1 - t, output row = 2 q + py;
 //   upsample conv:      the operand loader reads the bilinear x2 (align_corners=False) map of its input on the fly.
+//   dilated conv (K16): tap (r, s) at (r d, s d); 7 x 7 taps for the ResNet stem; a workgroup skips the taps it cannot reach.
 // A second input may be summed on load (skip_sum); the epilogue adds bias, an optional residual, then ReLU or sigmoid.
 //
 // Tiling: 256 threads = 4 waves; a wave owns 64 pixels x 32 output channels (two 32 x 32 accumulators, 16 registers each);
@@ -22,7 +23,8 @@ namespace {
 
 constexpr int NT = 256;
 constexpr int BK = 16;
-constexpr int MAXTAP = 25;
+constexpr int MAXTAP = 49;             // tap table: up to the 7 x 7 stem of ResNet (oess_conv2d_dilated_fwd_f32)
+constexpr int MAXTAP_V1 = 25;          // what oess_conv2d_fwd_f32 / oess_convlstm_step_f32 take
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
@@ -44,6 +46,7 @@ struct Params {
     int Hl, Wl;                      // logical input extent seen by the taps
     int Hq, Wq;                      // GEMM grid of one phase: M = B * Hq * Wq
     int stride, off_y, off_x, ostride;
+    int skip;                        // dilated convs: a workgroup walks only the taps that reach the map from one of its pixels
     const float* w;
     int CoutP;
     const float* bias;
@@ -54,6 +57,8 @@ struct Params {
     long long ob, oy, ox, oc;
     Phase ph[4];
 };
+static_assert(sizeof(Params) <= 1024, "Params travels as a kernel argument");
+static_assert(MAXTAP <= 64, "the tap mask of a workgroup is one 64-bit word");
 
 // area_pixel_compute_source_index(scale 0.5, align_corners=False) + the clamp of upsample_bilinear2d
 __device__ __forceinline__ void bil_axis(int d, int n, int& i0, int& i1, float& l0, float& l1) {
@@ -115,6 +120,9 @@ __global__ __launch_bounds__(NT) void conv_f32_kernel(const Params P) {
     constexpr int NB4 = BN * BK / 4;                      // float4s of one B step
     __shared__ float As[BK * LDA];
     __shared__ float Bs[BK * LDB];
+    __shared__ unsigned long long s_mask;
+    __shared__ unsigned char s_tap[MAXTAP];
+    __shared__ int s_ntap;
 
     const Phase& ph = P.ph[blockIdx.z];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -140,13 +148,45 @@ __global__ __launch_bounds__(NT) void conv_f32_kernel(const Params P) {
         ax0 = qx * P.stride + P.off_x;
     }
 
+    // K steps of this workgroup.  skip (VEC only): at dilation d most taps of a tile near the border, and on a map smaller than
+    // d all but the centre tap, read nothing but padding; their products are exact zeros, so the K steps of a tap that no pixel
+    // of the tile reaches are left out whole (no operand loads, no MFMAs).  The taps kept stay in (r, s) order.
+    const int spt = VEC ? P.Cin / BK : 1;                 // K steps per tap
+    const bool skip = VEC && P.skip;
+    int nstep = ph.kp / BK;
+    if (skip) {
+        if (tid == 0) s_mask = 0ull;
+        __syncthreads();
+        unsigned long long mine = 0ull;
+        if (mvalid) {
+            for (int t = 0; t < ph.ntap; ++t) {
+                const int y = ay0 + ph.dy[t], x = ax0 + ph.dx[t];
+                if (y >= 0 && y < P.Hl && x >= 0 && x < P.Wl) mine |= 1ull << t;
+            }
+        }
+        if (mine) atomicOr(&s_mask, mine);                // integer OR in LDS: order-free
+        __syncthreads();
+        if (tid == 0) {
+            int n = 0;
+            for (int t = 0; t < ph.ntap; ++t)
+                if ((s_mask >> t) & 1ull) s_tap[n++] = (unsigned char)t;
+            s_ntap = n;
+        }
+        __syncthreads();
+        nstep = s_ntap * spt;
+    }
+
     float ra[VEC ? NA * 4 : NA];
     float4 rb = make_float4(0.f, 0.f, 0.f, 0.f);
     const int bidx = tid, brow = bidx / (BN / 4), bcol = (bidx % (BN / 4)) * 4;
 
-    auto load = [&](int k0) {
+    auto load = [&](int step) {
+        int k0 = step * BK;                               // first weight row of the step
         if (VEC) {
-            const int tap = k0 / P.Cin, cbase = k0 - tap * P.Cin;
+            const int ti = step / spt;
+            const int tap = skip ? __builtin_amdgcn_readfirstlane((int)s_tap[ti]) : ti;
+            const int cbase = (step - ti * spt) * BK;
+            k0 = tap * P.Cin + cbase;
             const int y = ay0 + ph.dy[tap], x = ax0 + ph.dx[tap];
             const bool ok = mvalid && y >= 0 && y < P.Hl && x >= 0 && x < P.Wl;
 #pragma unroll
@@ -190,13 +230,15 @@ __global__ __launch_bounds__(NT) void conv_f32_kernel(const Params P) {
 #pragma unroll
     for (int r = 0; r < 16; ++r) { acc0[r] = 0.f; acc1[r] = 0.f; }
 
-    load(0);
-    store();
-    __syncthreads();
     const int l31 = lane & 31, lk = lane >> 5;
-    for (int k0 = 0; k0 < ph.kp; k0 += BK) {
-        const bool more = k0 + BK < ph.kp;
-        if (more) load(k0 + BK);
+    if (nstep > 0) {
+        load(0);
+        store();
+    }
+    __syncthreads();
+    for (int step = 0; step < nstep; ++step) {
+        const bool more = step + 1 < nstep;
+        if (more) load(step + 1);
 #pragma unroll
         for (int kk = 0; kk < BK / 2; ++kk) {
             const int kr = 2 * kk + lk;
@@ -313,6 +355,7 @@ extern "C" {
 
 size_t oess_conv2d_f32_packed_floats(int Cout, int Cin, int R, int S) {
     if (Cout < 1 || Cin < 1 || R < 1 || S < 1 || R * S > MAXTAP) return 0;
+    if (R * S > MAXTAP_V1 && (R != 7 || S != 7)) return 0;        // beyond 25 taps: the 7 x 7 stem only (oess.h, K16)
     return (size_t)ceil_to(R * S * Cin, BK) * ceil_to(Cout, 32);
 }
 
@@ -323,20 +366,24 @@ size_t oess_conv_transpose2d_f32_packed_floats(int Cout, int Cin) {
     return rows * ceil_to(Cout, 32);
 }
 
-int oess_conv2d_fwd_f32(const oess_f32_view_t* in, const oess_f32_view_t* in2, int B, int H, int W, int Cin, int upsample2x,
-                        const float* w_packed, const float* bias, int Cout, int R, int S, int stride, int pad, int act,
-                        const oess_f32_view_t* residual, const oess_f32_view_t* out, oess_stream_t stream) {
+int oess_conv2d_dilated_fwd_f32(const oess_f32_view_t* in, const oess_f32_view_t* in2, int B, int H, int W, int Cin, int upsample2x,
+                                const float* w_packed, const float* bias, int Cout, int R, int S, int stride, int pad, int dilation,
+                                int act, const oess_f32_view_t* residual, const oess_f32_view_t* out, oess_stream_t stream) {
     if (!inputs_ok(in, in2, B, H, W, Cin) || !weights_ok(w_packed, bias) || !view_ok(out)) return OESS_EINVAL;
-    if (Cout < 1 || R < 1 || S < 1 || R * S > MAXTAP || (stride != 1 && stride != 2) || pad < 0 || pad >= R || pad >= S) return OESS_EINVAL;
+    if (Cout < 1 || oess_conv2d_f32_packed_floats(Cout, Cin, R, S) == 0 || (stride != 1 && stride != 2)) return OESS_EINVAL;
+    if (pad < 0 || pad > (1 << 20) || dilation < 1 || (long long)(R - 1) * dilation > 127 || (long long)(S - 1) * dilation > 127)
+        return OESS_EINVAL;                                       // tap offsets r * dilation, s * dilation live in signed char
     if (act < 0 || act > 2 || (upsample2x != 0 && upsample2x != 1) || (residual && !residual->data)) return OESS_EINVAL;
     const int Hl = upsample2x ? 2 * H : H, Wl = upsample2x ? 2 * W : W;
-    const int Ho = (Hl + 2 * pad - R) / stride + 1, Wo = (Wl + 2 * pad - S) / stride + 1;
-    if (Ho < 1 || Wo < 1) return OESS_EINVAL;
+    const int ny = Hl + 2 * pad - dilation * (R - 1) - 1, nx = Wl + 2 * pad - dilation * (S - 1) - 1;
+    if (ny < 0 || nx < 0) return OESS_EINVAL;                     // Ho, Wo >= 1
+    const int Ho = ny / stride + 1, Wo = nx / stride + 1;
     Params P{};
     set_inputs(P, in, in2, B, H, W, Cin);
     P.up = upsample2x;
     P.Hl = Hl; P.Wl = Wl; P.Hq = Ho; P.Wq = Wo;
     P.stride = stride; P.off_y = -pad; P.off_x = -pad; P.ostride = 1;
+    P.skip = dilation > 1;
     P.w = w_packed; P.CoutP = ceil_to(Cout, 32); P.bias = bias; P.Cout = Cout; P.act = act;
     P.has_res = residual != nullptr;
     P.res = residual ? to_view(residual) : View{nullptr, 0, 0, 0, 0};
@@ -344,8 +391,16 @@ int oess_conv2d_fwd_f32(const oess_f32_view_t* in, const oess_f32_view_t* in2, i
     Phase& ph = P.ph[0];
     ph.ntap = R * S; ph.py = 0; ph.px = 0; ph.w_off = 0; ph.kp = ceil_to(R * S * Cin, BK);
     for (int r = 0; r < R; ++r)
-        for (int s = 0; s < S; ++s) { ph.dy[r * S + s] = (signed char)r; ph.dx[r * S + s] = (signed char)s; }
+        for (int s = 0; s < S; ++s) { ph.dy[r * S + s] = (signed char)(r * dilation); ph.dx[r * S + s] = (signed char)(s * dilation); }
     return launch(P, 1, (hipStream_t)stream);
+}
+
+int oess_conv2d_fwd_f32(const oess_f32_view_t* in, const oess_f32_view_t* in2, int B, int H, int W, int Cin, int upsample2x,
+                        const float* w_packed, const float* bias, int Cout, int R, int S, int stride, int pad, int act,
+                        const oess_f32_view_t* residual, const oess_f32_view_t* out, oess_stream_t stream) {
+    if (R < 1 || S < 1 || R * S > MAXTAP_V1 || pad < 0 || pad >= R || pad >= S) return OESS_EINVAL;
+    return oess_conv2d_dilated_fwd_f32(in, in2, B, H, W, Cin, upsample2x, w_packed, bias, Cout, R, S, stride, pad, 1, act, residual, out,
+                                       stream);
 }
 
 int oess_conv_transpose2d_fwd_f32(const oess_f32_view_t* in, const oess_f32_view_t* in2, int B, int H, int W, int Cin,
@@ -383,7 +438,7 @@ int oess_convlstm_step_f32(const oess_f32_view_t* xh, int B, int H, int W, int C
                            int C_hidden, int R, int S, int pad, int prev_cell_is_zero, float* cell, const oess_f32_view_t* hidden,
                            void* ws, size_t ws_bytes, oess_stream_t stream) {
     if (!inputs_ok(xh, nullptr, B, H, W, Cin) || !weights_ok(w_packed, bias) || !cell || !view_ok(hidden) || !ws) return OESS_EINVAL;
-    if (C_hidden < 1 || R < 1 || S < 1 || R * S > MAXTAP || 2 * pad != R - 1 || 2 * pad != S - 1) return OESS_EINVAL;
+    if (C_hidden < 1 || R < 1 || S < 1 || R * S > MAXTAP_V1 || 2 * pad != R - 1 || 2 * pad != S - 1) return OESS_EINVAL;
     if ((prev_cell_is_zero != 0 && prev_cell_is_zero != 1) || ((uintptr_t)ws & 15) != 0) return OESS_EINVAL;
     const long long npix = (long long)B * H * W;
     if (ws_bytes < oess_convlstm_f32_workspace_bytes(npix, C_hidden)) return OESS_ENOMEM;

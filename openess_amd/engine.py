@@ -194,7 +194,11 @@ class PackedWeight:
 class PackedWeightF32:
     """fp32 operand of a conv (or, transposed=True, a ConvTranspose2d) weight for the K14 kernels (hip.conv2d_f32,
     hip.conv_transpose2d_f32), with an eval-mode BatchNorm folded in (in float64, rounded once), cached per parameter versions.
-    cin: keep only the first `cin` input channels (the x half of a ConvLSTM Gates weight, for a step from a zero state)."""
+    cin: keep only the first `cin` input channels (the x half of a ConvLSTM Gates weight, for a step from a zero state).
+    The key of a folded BatchNorm holds the versions of its affine parameters, of running_mean / running_var AND of
+    num_batches_tracked: the train-mode HIP norm kernels update the running statistics through their raw pointers, which moves
+    no version counter, but every such step counts a batch (bump_bn_counter), so a training step between two fp32 validations
+    re-packs even when every parameter is frozen (linear probing) and an unchanged model does not."""
 
     def __init__(self):
         self.key = None
@@ -203,6 +207,8 @@ class PackedWeightF32:
 
     def get(self, weight, bias=None, bn=None, transposed=False, cin=None):
         key = param_versions(weight, bias, bn) + (transposed, cin)
+        if bn is not None and bn.num_batches_tracked is not None:
+            key = key + (bn.num_batches_tracked._version,)
         if key != self.key:
             with torch.no_grad():
                 w, b = fold_bn(weight.detach().double(), None if bias is None else bias.detach().double(), bn, 1 if transposed else 0)

@@ -1942,17 +1942,22 @@ def pack_conv_transpose_weight_f32(w):
     return out
 
 
-def conv2d_f32(x, packed, bias, Cout, R, S, stride=1, pad=0, act=None, x2=None, upsample2x=False, residual=None, out=None):
+def conv2d_f32(x, packed, bias, Cout, R, S, stride=1, pad=0, act=None, x2=None, upsample2x=False, residual=None, out=None,
+               dilation=1):
     """out = act(conv(x [+ x2]) + bias [+ residual]) in fp32 on the f32-input MFMA (oess_conv2d_fwd_f32).  x, x2, residual, out:
     logical [B, C, H, W] fp32 tensors with any strides (channels_last and channel slices take the vector loads); act: None, 'relu'
-    or 'sigmoid'; upsample2x: convolve the bilinear x2 (align_corners=False) of x [+ x2].  Returns out (channels_last if new)."""
+    or 'sigmoid'; upsample2x: convolve the bilinear x2 (align_corners=False) of x [+ x2].  dilation > 1, pad >= R or more than 25
+    taps (DeepLabv3: the 7 x 7 stem, the atrous convs) go to oess_conv2d_dilated_fwd_f32, the same kernel without the geometry
+    limits.  Returns out (channels_last if new)."""
     lib = _lib.load()
     B, Cin, H, W = x.shape
     vx, v2 = _f32_operands(x, x2, packed, bias, Cout, lib.oess_conv2d_f32_packed_floats(Cout, Cin, R, S))
     if act not in _F32_ACT:
         raise ValueError(f"act must be one of {list(_F32_ACT)}")
     Hl, Wl = (2 * H, 2 * W) if upsample2x else (H, W)
-    Ho, Wo = (Hl + 2 * pad - R) // stride + 1, (Wl + 2 * pad - S) // stride + 1
+    if dilation < 1 or Hl + 2 * pad < dilation * (R - 1) + 1 or Wl + 2 * pad < dilation * (S - 1) + 1:
+        raise ValueError(f"conv2d_f32: no output for a {Hl} x {Wl} map, {R} x {S} taps, pad {pad}, dilation {dilation}")
+    Ho, Wo = (Hl + 2 * pad - dilation * (R - 1) - 1) // stride + 1, (Wl + 2 * pad - dilation * (S - 1) - 1) // stride + 1
     out = _f32_out(out, B, Cout, Ho, Wo, x.device)
     vr = None
     if residual is not None:
@@ -1961,9 +1966,14 @@ def conv2d_f32(x, packed, bias, Cout, R, S, stride=1, pad=0, act=None, x2=None, 
             raise ValueError(f"residual shape {tuple(residual.shape)} != {(B, Cout, Ho, Wo)}")
         vr = _f32_view(residual, "residual")
     vo = _f32_view(out, "out")
-    _lib.check(lib.oess_conv2d_fwd_f32(ctypes.byref(vx), _f32_ref(v2), B, H, W, Cin, int(bool(upsample2x)), _ptr(packed), _ptr(bias),
-                                       Cout, R, S, stride, pad, _F32_ACT[act], _f32_ref(vr), ctypes.byref(vo), _stream()),
-               "oess_conv2d_fwd_f32")
+    if dilation == 1 and R * S <= 25 and pad < R and pad < S:
+        _lib.check(lib.oess_conv2d_fwd_f32(ctypes.byref(vx), _f32_ref(v2), B, H, W, Cin, int(bool(upsample2x)), _ptr(packed), _ptr(bias),
+                                           Cout, R, S, stride, pad, _F32_ACT[act], _f32_ref(vr), ctypes.byref(vo), _stream()),
+                   "oess_conv2d_fwd_f32")
+    else:
+        _lib.check(lib.oess_conv2d_dilated_fwd_f32(ctypes.byref(vx), _f32_ref(v2), B, H, W, Cin, int(bool(upsample2x)), _ptr(packed),
+                                                   _ptr(bias), Cout, R, S, stride, pad, dilation, _F32_ACT[act], _f32_ref(vr),
+                                                   ctypes.byref(vo), _stream()), "oess_conv2d_dilated_fwd_f32")
     _bump(out)
     return out
 
@@ -2052,4 +2062,36 @@ def upsample2x_concat_f32(x, skip=None, out=None):
     _lib.check(lib.oess_upsample_nearest2x_concat_f32(ctypes.byref(vx), B, H, W, C, _f32_ref(vs), Cs, ctypes.byref(vo), _stream()),
                "oess_upsample_nearest2x_concat_f32")
     _bump(out)
+    return out
+
+
+# ------------------------------------------------------------------------------------------ K16: fp32 DeepLabv3 inference
+def max_pool_3x3s2_f32(x, out=None):
+    """nn.MaxPool2d(3, stride=2, padding=1) in fp32 (oess_maxpool3x3s2_fwd_f32): x, out logical [B, C, H, W] fp32 tensors with any
+    strides (channels_last takes 16-byte loads).  Exact: values are selected, not computed.  Returns out (channels_last if new)."""
+    lib = _lib.load()
+    _need_gpu(x, out)
+    vx = _f32_view(x, "x")
+    B, C, H, W = x.shape
+    out = _f32_out(out, B, C, (H - 1) // 2 + 1, (W - 1) // 2 + 1, x.device)
+    vo = _f32_view(out, "out")
+    _lib.check(lib.oess_maxpool3x3s2_fwd_f32(ctypes.byref(vx), B, H, W, C, ctypes.byref(vo), _stream()), "oess_maxpool3x3s2_fwd_f32")
+    _bump(out)
+    return out
+
+
+def global_avg_pool_f32(x):
+    """nn.AdaptiveAvgPool2d(1) in fp32 (oess_global_avg_pool_fwd_f32): x logical [B, C, H, W] fp32 with any strides -> fp32
+    [B, C, 1, 1] (channels dense).  Fixed summation order: bit-repeatable."""
+    lib = _lib.load()
+    _need_gpu(x)
+    vx = _f32_view(x, "x")
+    B, C, H, W = x.shape
+    need = lib.oess_global_avg_pool_f32_workspace_bytes(B, H, W, C)
+    if need == 0:
+        raise ValueError(f"global_avg_pool_f32: no kernel for a {(B, C, H, W)} map")
+    ws = _workspace(need, x.device, tag="avgpool_f32")
+    out = torch.empty((B, 1, 1, C), dtype=torch.float32, device=x.device).permute(0, 3, 1, 2)     # NHWC: the 1 x 1 conv's vector loads
+    _lib.check(lib.oess_global_avg_pool_fwd_f32(ctypes.byref(vx), B, H, W, C, _ptr(out), _ptr(ws), ws.numel(), _stream()),
+               "oess_global_avg_pool_fwd_f32")
     return out

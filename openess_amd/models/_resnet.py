@@ -15,6 +15,7 @@ class HipConv2d(nn.Conv2d):
         super().__init__(*a, **k)
         self._pw = engine.PackedWeight()
         self._pw_folded = engine.PackedWeight()      # eval-mode BatchNorm folded in
+        self._pw32 = engine.PackedWeightF32()        # the same in fp32 (conv_bn_f32)
 
     def forward(self, x):
         if x.shape[1] % 8 or x.dtype != torch.bfloat16:
@@ -80,6 +81,24 @@ def conv_bn(conv, bn, x, relu=False, residual=None, out=None, skip_in=None, skip
     return engine.conv2d_infer(x, pw, conv.out_channels, k, s, p, d, relu=relu, residual=residual, out=out)
 
 
+def fold_conv_bn_f64(conv, bn):
+    """(weight, bias) in float64 of conv -> eval-mode BatchNorm2d as ONE conv: what PackedWeightF32.get rounds once to fp32."""
+    return engine.fold_bn(conv.weight.detach().double(), None if conv.bias is None else conv.bias.detach().double(), bn)
+
+
+def conv_bn_f32(conv, bn, x, relu=False, residual=None, out=None, pw=None):
+    """conv -> eval-mode BatchNorm2d [-> + residual] [-> ReLU] in fp32, one launch (hip.conv2d_f32): the BatchNorm is folded into
+    the weight and bias in float64 and rounded once; the operand is cached per parameter and running-statistic versions
+    (engine.PackedWeightF32), so a training step between two validations re-packs it and an unchanged model does not.
+    x, residual, out: logical [B, C, H, W] fp32 tensors, any strides.  pw: the cache of a conv that is not a HipConv2d."""
+    if bn.training or bn.running_mean is None:
+        raise NotImplementedError("fp32 inference folds BatchNorm's running statistics: train-mode BatchNorm is not built")
+    op = (conv._pw32 if pw is None else pw).get(conv.weight, conv.bias, bn)
+    (R, S), s, p, d = conv.kernel_size, conv.stride[0], conv.padding[0], conv.dilation[0]
+    return hip.conv2d_f32(x, op.packed, op.bias, conv.out_channels, R, S, stride=s, pad=p, act='relu' if relu else None,
+                          residual=residual, out=out, dilation=d)
+
+
 def conv3x3(in_planes, out_planes, stride=1, groups=1, dilation=1):
     assert groups == 1
     return HipConv2d(in_planes, out_planes, kernel_size=3, stride=stride, padding=dilation, bias=False, dilation=dilation)
@@ -135,6 +154,14 @@ class Bottleneck(nn.Module):
         if self.downsample is not None:
             identity = conv_bn(self.downsample[0], self.downsample[1], x)
         return conv_bn(self.conv3, self.bn3, out, relu=True, residual=identity, skip_out=skip)
+
+    def forward_fp32(self, x):
+        """The block in fp32 (eval mode): three launches, four with a downsample conv; the residual add and the last ReLU ride in
+        conv3's epilogue, the downsample conv is the residual's producer."""
+        out = conv_bn_f32(self.conv1, self.bn1, x, relu=True)
+        out = conv_bn_f32(self.conv2, self.bn2, out, relu=True)
+        identity = x if self.downsample is None else conv_bn_f32(self.downsample[0], self.downsample[1], x)
+        return conv_bn_f32(self.conv3, self.bn3, out, relu=True, residual=identity)
 
 
 class ResNet(nn.Module):

@@ -8,7 +8,7 @@ import torch.nn.functional as F
 
 from .. import engine, hip
 from . import _resnet as resnet
-from ._resnet import HipConv2d, conv_bn
+from ._resnet import HipConv2d, conv_bn, conv_bn_f32
 
 
 class IntermediateLayerGetter(nn.ModuleDict):
@@ -41,10 +41,30 @@ class IntermediateLayerGetter(nn.ModuleDict):
                 out[self.return_layers[name]] = x
         return out
 
+    def forward_fp32(self, x):
+        """forward() in fp32 (eval mode): x fp32 [B, 3, H, W], any layout; the same OrderedDict of fp32 channels_last maps."""
+        out = OrderedDict()
+        for name, module in self.named_children():
+            if name == 'conv1':
+                x = conv_bn_f32(module, self['bn1'], x, relu=True)
+            elif name in ('bn1', 'relu'):
+                continue
+            elif name == 'maxpool':
+                x = hip.max_pool_3x3s2_f32(x)
+            else:
+                for block in module:
+                    x = block.forward_fp32(x)
+            if name in self.return_layers:
+                out[self.return_layers[name]] = x
+        return out
+
 
 class _ConvBNReLU(nn.Sequential):
     def forward(self, x, out=None):
         return conv_bn(self[0], self[1], x, relu=True, out=out)
+
+    def forward_fp32(self, x, out=None):
+        return conv_bn_f32(self[0], self[1], x, relu=True, out=out)
 
 
 class ASPPConv(_ConvBNReLU):
@@ -57,6 +77,14 @@ class ASPPPooling(nn.Sequential):
     def __init__(self, in_channels, out_channels):
         super().__init__(nn.AdaptiveAvgPool2d(1), nn.Conv2d(in_channels, out_channels, 1, bias=False),
                          nn.BatchNorm2d(out_channels), nn.ReLU(inplace=True))
+        self._pw32 = engine.PackedWeightF32()
+
+    def forward_fp32(self, x, out):
+        """Global average pool (fixed-order fp32 sums), the 1 x 1 conv + BatchNorm + ReLU on the B x 1 x 1 map, then the
+        broadcast (bilinear from 1 x 1) into `out`, the branch's channel slice of the concat buffer."""
+        y = conv_bn_f32(self[1], self[2], hip.global_avg_pool_f32(x), relu=True, pw=self._pw32)
+        out.copy_(y.expand(-1, -1, x.shape[2], x.shape[3]))
+        return out
 
     def forward(self, x, out=None):
         size = x.shape[-2:]
@@ -112,6 +140,14 @@ class ASPP(nn.Module):
             return hip.dropout(y, drop.p, True, owner=drop)            # Philox mask recomputed in the backward pass (nn.Dropout(0.1), :343)
         return drop(y)
 
+    def forward_fp32(self, x):
+        B, _, H, W = x.shape
+        oc = self.convs[0][0].out_channels
+        res = engine.empty_cl(B, oc * len(self.convs), H, W, x.device, dtype=torch.float32)
+        for i, conv in enumerate(self.convs):
+            conv.forward_fp32(x, out=res[:, i * oc:(i + 1) * oc])
+        return conv_bn_f32(self.project[0], self.project[1], res, relu=True)          # Dropout: the identity in eval mode
+
 
 class DeepLabHead(nn.Module):
     def __init__(self, text_embeddings_path, text_categories, in_channels, num_classes, aspp_dilate=[12, 24, 36]):
@@ -131,6 +167,14 @@ class DeepLabHead(nn.Module):
                 loaded = torch.load(text_embeddings_path, map_location='cpu')   # reference: map_location='cuda'
                 self.text_embeddings[:, :] = loaded[:, :]
         self._pw_text = engine.PackedWeight()
+        self._pw_text32 = engine.PackedWeightF32()
+
+    def forward_fp32(self, feature):
+        feature = self.ASPP.forward_fp32(feature['out'])
+        x = conv_bn_f32(self.classifier[0], self.classifier[1], feature, relu=True)
+        te = self.text_embeddings
+        op = self._pw_text32.get_composed([te], lambda: (te.detach().double()[:, :, None, None], None))
+        return hip.conv2d_f32(x, op.packed, None, te.shape[0], 1, 1), feature
 
     def forward(self, feature):
         feature = self.ASPP(feature['out'])
@@ -179,6 +223,31 @@ class deeplabv3_resnet50(nn.Module):
                 p.requires_grad = False
             for p in self.classifier.parameters():
                 p.requires_grad = True
+
+    def check_fp32(self):
+        """Raises NotImplementedError for what forward_fp32 does not run: it is the eval-mode network (BatchNorm folded from its
+        running statistics, Dropout the identity)."""
+        for name, m in self.named_modules():
+            if isinstance(m, nn.modules.batchnorm._BatchNorm) and (m.training or m.running_mean is None or m.running_var is None):
+                raise NotImplementedError(f"forward_fp32 folds BatchNorm's running statistics into the convs: {name or 'the model'} "
+                                          "is in train mode (batch statistics); call .eval() first")
+            if isinstance(m, nn.Dropout) and m.training and m.p > 0:
+                raise NotImplementedError(f"forward_fp32 is inference only: dropout {name} is in train mode; call .eval() first")
+
+    @torch.no_grad()
+    def forward_fp32(self, x):
+        """forward() of the eval-mode network in fp32 on the f32-input MFMA kernels: (logits, feats), both fp32 at
+        the input size.  No buffer, operand or state is shared with forward()."""
+        self.check_fp32()
+        if x.dtype != torch.float32 or x.ndim != 4:
+            raise ValueError("forward_fp32 takes a float32 [B, 3, H, W] image batch")
+        input_shape = x.shape[-2:]
+        logist, feats = self.classifier.forward_fp32(self.backbone.forward_fp32(x))
+        logist = hip.bilinear_resize(logist, size=input_shape, align_corners=False)
+        feats = hip.bilinear_resize(feats, size=input_shape, align_corners=False)
+        if self.if_linear_probing:
+            logist = hip.linear_probe(logist, self.linear_probe)
+        return logist, feats
 
     def forward(self, x):
         input_shape = x.shape[-2:]

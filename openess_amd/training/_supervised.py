@@ -27,8 +27,9 @@ class SupervisedTrainer(BaseTrainer):
         if self.eval_precision not in ('bf16', 'fp32'):
             raise ValueError(f"eval_precision must be 'bf16' or 'fp32', got {self.eval_precision!r}")
         if self.eval_precision == 'fp32' and settings.config_option == 'frame2recon':
-            raise NotImplementedError("eval_precision: fp32 with frame2recon needs DeepLabv3 (ResNet-50 + ASPP) in fp32, which is "
-                                      "not built; the fp32 validation path covers frame2voxel / recon2voxel")
+            raise NotImplementedError("eval_precision: fp32 is not wired for frame2recon: the key switches val_step of frame2voxel / "
+                                      "recon2voxel only.  DeepLabv3 in fp32 is reached through val_logits(batch, precision='fp32') "
+                                      "and tools/eval_precision.py --config-option frame2recon")
         super().__init__(settings, train)
 
     def backend_kwargs(self):
@@ -190,19 +191,27 @@ class SupervisedTrainer(BaseTrainer):
     def val_logits(self, batch, precision=None):
         """Class logits of one validation batch in `precision` (default: the trainer's eval_precision).  'fp32' runs the E2VID
         encoder through the fp32 reconstructor and the decoder through SemSegE2VID.forward_fp32 (trainers built with
-        eval_precision: fp32 only); it shares no state with the bf16 path or the training step."""
+        eval_precision: fp32 only), or, frame2recon, deeplabv3_resnet50.forward_fp32 on the eval-mode network (any trainer; the
+        modules' train / eval flags are put back); it shares no state with the bf16 path or the training step."""
         s = self.settings
         precision = self.eval_precision if precision is None else precision
+        if precision not in ('bf16', 'fp32'):
+            raise ValueError(f"precision must be 'bf16' or 'fp32', got {precision!r}")
         if s.config_option not in ('recon2voxel', 'frame2voxel'):
-            if precision != 'bf16':
-                raise NotImplementedError("fp32 validation covers frame2voxel / recon2voxel (no fp32 DeepLabv3)")
-            return self.models_dict['model_recon'](batch[2])[0]
+            model = self.models_dict['model_recon']
+            if precision == 'bf16':
+                return model(batch[2])[0]
+            modes = [(m, m.training) for m in model.modules()]
+            model.eval()
+            try:
+                return model.forward_fp32(batch[2])[0]
+            finally:
+                for m, training in modes:
+                    m.training = training
         if precision == 'fp32':
             if getattr(self, 'reconstructor_fp32', None) is None:
                 raise RuntimeError("this trainer was built without eval_precision: fp32")
             return self.models_dict['back_end'].forward_fp32(self._latents_fp32(batch[0]))[0][1]
-        if precision != 'bf16':
-            raise ValueError(f"precision must be 'bf16' or 'fp32', got {precision!r}")
         return self.models_dict['back_end'](self._latents(batch[0]))[0][1]
 
     def val_step(self, batch, sensor, i_batch, vis_reconstr_idx, file_path):

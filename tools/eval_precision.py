@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
-"""bf16 versus fp32 validation of the event segmentation network: builds the fine-tune trainer from a settings
+"""bf16 versus fp32 validation of the segmentation networks: builds the fine-tune trainer from a settings
 file, optionally loads a checkpoint, and runs the validation split twice from the same weights -- the bf16 kernels the trainers
-validate with by default, and the fp32 path of `eval_precision: fp32` (E2VID and SemSegE2VID in fp32).  Prints one JSON line:
+validate with by default, and the fp32 path: E2VID and SemSegE2VID in fp32 (`eval_precision: fp32`; frame2voxel, recon2voxel) or
+DeepLabv3-R50 in fp32 (--config-option frame2recon).  Prints one JSON line:
 
   bf16 / fp32:      mIoU and accuracy (per cent) of each path,
   argmax_agreement: share of labelled pixels on which the two paths predict the same class (all of them, no margin filter),
@@ -9,6 +10,7 @@ validate with by default, and the fp32 path of `eval_precision: fp32` (E2VID and
   bf16_ms / fp32_ms: milliseconds per validation batch (HIP events, the first --warmup batches excluded).
 
     python tools/eval_precision.py [--settings tests/configs/finetune_dsec_synthetic.yaml] [--checkpoint FILE] [--batches N]
+                                   [--config-option frame2voxel | recon2voxel | frame2recon]
 
 Random-initialised weights (no checkpoint) give near-tied logits, so their agreement figure says little about a trained
 network; the figure that matters is the one from a trained checkpoint."""
@@ -31,9 +33,11 @@ DEFAULT = os.path.join(ROOT, "tests", "configs", "finetune_dsec_synthetic.yaml")
 def build(settings_file, checkpoint=None, config_option='frame2voxel', ckpt_dir=None):
     train.seed_everything()
     s = Settings(settings_file, generate_log=False)
-    s.config_option = config_option            # the fp32 path evaluates the event networks (frame2voxel / recon2voxel)
+    s.config_option = config_option
     s.if_finetuning, s.if_supervised_only = True, False
-    s.eval_precision = 'fp32'
+    # the event networks build their fp32 reconstructor under the key; frame2recon needs none (val_logits(..., 'fp32') runs
+    # deeplabv3_resnet50.forward_fp32 on any trainer) and its trainer refuses the key
+    s.eval_precision = 'bf16' if config_option == 'frame2recon' else 'fp32'
     if ckpt_dir is not None:
         s.ckpt_dir = ckpt_dir
     if checkpoint:
@@ -90,7 +94,7 @@ def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--settings", default=DEFAULT)
     ap.add_argument("--checkpoint", default=None, help="checkpoint written by the trainers' saver (default: seeded random weights)")
-    ap.add_argument("--config-option", default="frame2voxel", choices=("frame2voxel", "recon2voxel"))
+    ap.add_argument("--config-option", default="frame2voxel", choices=("frame2voxel", "recon2voxel", "frame2recon"))
     ap.add_argument("--batches", type=int, default=None, help="stop after this many validation batches (default: the whole split)")
     ap.add_argument("--warmup", type=int, default=1, help="batches left out of the timing")
     a = ap.parse_args(argv)
