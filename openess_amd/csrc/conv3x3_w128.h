@@ -119,17 +119,14 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
     };
 
     // the pixel fragment address of k-step KS is built by a v_xor in front of the read (12 address registers instead of 48)
-#define W128_RD_P(BUF, I, DX, KS, OFF) { uint32_t t_; asm volatile("v_xor_b32 %1, %4, %2\n\tds_read_b128 %0, %1 offset:%3" : "=v"(fp[BUF][I]), "=&v"(t_) : "v"(pa[I][DX]), "n"(OFF), "n"((KS) << 5) : "memory"); }
-#define W128_RD_P0(BUF, I, DX, OFF) asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(fp[BUF][I]) : "v"(pa[I][DX]), "n"(OFF) : "memory")
-#define W128_RD_W(BUF, J, KS, OFF) asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(fw[BUF][J]) : "v"(wa[J][KS]), "n"(OFF) : "memory")
     // read piece q (0..7) of k-step KS of the slab (halo offset HOFF, tap DX, weight stage offset WOFF) into fragment buffer BUF
     auto frag_read = [&fp, &fw, &pa, &wa](auto buf_c, auto q_c, auto dx_c, auto ks_c, auto hoff_c, auto woff_c) __attribute__((always_inline)) {
         constexpr int BUF = decltype(buf_c)::value, q = decltype(q_c)::value, DX = decltype(dx_c)::value, KS = decltype(ks_c)::value;
         constexpr int HOFF = decltype(hoff_c)::value, WOFF = decltype(woff_c)::value;
         if constexpr (q == 0) W128_RD_W(BUF, 0, KS, WOFF);
         else if constexpr (q <= 4) {
-            if constexpr (KS == 0) W128_RD_P0(BUF, q - 1, DX, HOFF);
-            else W128_RD_P(BUF, q - 1, DX, KS, HOFF);
+            if constexpr (KS == 0) W128_RD_P0(BUF, q - 1, pa[q - 1][DX], HOFF);
+            else W128_RD_P(BUF, q - 1, pa[q - 1][DX], KS, HOFF);
         }
         else W128_RD_W(BUF, q - 4, KS, WOFF);
     };
@@ -295,7 +292,4 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
         });
         stores_in_flight = 1;
     }
-#undef W128_RD_P
-#undef W128_RD_P0
-#undef W128_RD_W
 }

@@ -21,17 +21,14 @@
 
 namespace {
 
+#include "f32_view.h"
+
 constexpr int NT = 256;
 constexpr int BK = 16;
 constexpr int MAXTAP = 49;             // tap table: up to the 7 x 7 stem of ResNet (oess_conv2d_dilated_fwd_f32)
 constexpr int MAXTAP_V1 = 25;          // what oess_conv2d_fwd_f32 / oess_convlstm_step_f32 take
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
-
-struct View {
-    const float* p;
-    long long sb, sy, sx, sc;
-};
 
 struct Phase {
     int ntap, py, px, kp;            // kp: K rows of this phase's packed block (multiple of BK)
@@ -298,10 +295,6 @@ __global__ __launch_bounds__(NT) void lstm_cell_f32_kernel(const float* __restri
     const int x = (int)(p % W), y = (int)((p / W) % H), b = (int)(p / ((long long)W * H));
     hid[b * hb + y * hy + x * hx + c * hc] = og * tanhf(cn);
 }
-
-bool view_ok(const oess_f32_view_t* v) { return v && v->data; }
-
-View to_view(const oess_f32_view_t* v) { return View{v->data, v->sb, v->sy, v->sx, v->sc}; }
 
 int ceil_to(int v, int a) { return (v + a - 1) / a * a; }
 

@@ -37,7 +37,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wm = wave >> 1, wn = wave & 1;
     const int p31 = lane & 31, hi = lane >> 5;
-    const int lrow = lane >> 3, slot = lane & 7;
     const uint32_t lds0 = (uint32_t)(uintptr_t)smem;
     const unsigned oob = 0x80000000u;
 
@@ -120,19 +119,16 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
                                                  16, bv, koff, 0, 0);
     };
 
-#define G128_RD_P(BUF, I, KS, PA, OFF) { uint32_t t_; asm volatile("v_xor_b32 %1, %4, %2\n\tds_read_b128 %0, %1 offset:%3" : "=v"(fp[BUF][I]), "=&v"(t_) : "v"(PA[I]), "n"(OFF), "n"((KS) << 5) : "memory"); }
-#define G128_RD_P0(BUF, I, PA, OFF) asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(fp[BUF][I]) : "v"(PA[I]), "n"(OFF) : "memory")
-#define G128_RD_W(BUF, J, KS, OFF) asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(fw[BUF][J]) : "v"(wa[J][KS]), "n"(OFF) : "memory")
     // PST = pixel stage (0..2), WOFF = byte offset of the weight stage
     auto frag_read = [&fp, &fw, &pa, &pa2, &wa](auto buf_c, auto q_c, auto ks_c, auto pst_c, auto woff_c) __attribute__((always_inline)) {
         constexpr int BUF = decltype(buf_c)::value, q = decltype(q_c)::value, KS = decltype(ks_c)::value;
         constexpr int PST = decltype(pst_c)::value, WOFF = decltype(woff_c)::value, POFF = PST == 2 ? 0 : PST * G128_STAGE;
-        if constexpr (q == 0) G128_RD_W(BUF, 0, KS, WOFF);
+        if constexpr (q == 0) W128_RD_W(BUF, 0, KS, WOFF);
         else if constexpr (q <= 4) {
-            if constexpr (PST == 2) { if constexpr (KS == 0) G128_RD_P0(BUF, q - 1, pa2, POFF); else G128_RD_P(BUF, q - 1, KS, pa2, POFF); }
-            else { if constexpr (KS == 0) G128_RD_P0(BUF, q - 1, pa, POFF); else G128_RD_P(BUF, q - 1, KS, pa, POFF); }
+            if constexpr (PST == 2) { if constexpr (KS == 0) W128_RD_P0(BUF, q - 1, pa2[q - 1], POFF); else W128_RD_P(BUF, q - 1, pa2[q - 1], KS, POFF); }
+            else { if constexpr (KS == 0) W128_RD_P0(BUF, q - 1, pa[q - 1], POFF); else W128_RD_P(BUF, q - 1, pa[q - 1], KS, POFF); }
         }
-        else G128_RD_W(BUF, q - 4, KS, WOFF);
+        else W128_RD_W(BUF, q - 4, KS, WOFF);
     };
     auto mma = [&acc, &fp, &fw](auto buf_c, auto m_c) __attribute__((always_inline)) {
         constexpr int BUF = decltype(buf_c)::value, m = decltype(m_c)::value, j = m >> 2, i = m & 3;
@@ -299,7 +295,4 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
         });
         stores_in_flight = 1;
     }
-#undef G128_RD_P
-#undef G128_RD_P0
-#undef G128_RD_W
 }

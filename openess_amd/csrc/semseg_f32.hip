@@ -17,15 +17,12 @@
 
 namespace {
 
+#include "f32_view.h"
+
 constexpr int NT = 256;
 constexpr int MAX_CHUNKS = 256;          // pixel ranges per (sample, channel group): bounds the workspace and the merge loop
 constexpr int MIN_CHUNK_PIX = 128;
 constexpr int TARGET_BLOCKS = 2048;      // 8 workgroups per CU on 256 CUs when the map is large enough
-
-struct View {
-    const float* p;
-    long long sb, sy, sx, sc;
-};
 
 struct NormParams {
     View in, res;
@@ -38,29 +35,6 @@ struct NormParams {
     float eps;
     float* part;                         // [B][nchunk][2][C]: mean, M2
 };
-
-template <int V>
-struct Vec {
-    float v[V];
-};
-
-template <int V>
-__device__ __forceinline__ Vec<V> ldv(const float* p) {
-    Vec<V> r;
-    if constexpr (V == 4) {
-        const float4 t = *(const float4*)p;
-        r.v[0] = t.x; r.v[1] = t.y; r.v[2] = t.z; r.v[3] = t.w;
-    } else {
-        r.v[0] = p[0];
-    }
-    return r;
-}
-
-template <int V>
-__device__ __forceinline__ void stv(float* p, const Vec<V>& r) {
-    if constexpr (V == 4) *(float4*)p = make_float4(r.v[0], r.v[1], r.v[2], r.v[3]);
-    else p[0] = r.v[0];
-}
 
 // Chan et al.: (na, ma, M2a) <- (na, ma, M2a) merged with (nb, mb, M2b)
 template <int V>
@@ -233,19 +207,6 @@ __global__ __launch_bounds__(NT) void upsample_nearest2x_concat_f32_kernel(const
     stv<V>(P.out + b * P.ob + y * P.oy + x * P.ox + c * P.oc, ldv<V>(src));
 }
 
-bool view_ok(const oess_f32_view_t* v) { return v && v->data; }
-
-View to_view(const oess_f32_view_t* v) { return View{v->data, v->sb, v->sy, v->sx, v->sc}; }
-
-// dense channels whose every pixel starts on a 16-byte boundary
-bool vec_ok(const oess_f32_view_t* v) {
-    return v->sc == 1 && ((uintptr_t)v->data & 15) == 0 && v->sb % 4 == 0 && v->sy % 4 == 0 && v->sx % 4 == 0;
-}
-
-bool geometry_ok(int B, int H, int W, int C) {
-    return B >= 1 && B <= 65535 && H >= 1 && W >= 1 && C >= 1 && C <= (1 << 20) && (long long)H * W < (1LL << 30) &&
-           (long long)B * H * W * C < (1LL << 40);
-}
 
 }  // namespace
 
