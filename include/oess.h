@@ -706,6 +706,29 @@ size_t oess_global_avg_pool_f32_workspace_bytes(int B, int H, int W, int C);
 int oess_global_avg_pool_fwd_f32(const oess_f32_view_t* in, int B, int H, int W, int C, float* out, void* ws, size_t ws_bytes,
                                  oess_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------
+ * K17 fp32 image-teacher inference (models/image_model.py:90-143 of the reference, whose frozen ResNet-50 stays in .train()):
+ * the convolutions are oess_conv2d_dilated_fwd_f32 without a fold; this is the layer K16 lacked.  Additions only: the ABI
+ * version stays.
+ *
+ * oess_batch_norm_train_fwd_f32: nn.BatchNorm2d in train mode: out = act((in - mean) * (gamma / sqrt(var + eps)) + beta
+ *   [+ residual]), act ReLU if relu, mean and biased variance per channel over B x H x W.  in, residual (nullable) and out are
+ *   B x H x W x C views; out may be in itself.  gamma, beta: fp32 [C], nullable (1, 0).  save_mean, save_var (nullable): fp32
+ *   [C], the batch mean and the biased variance.  running_mean, running_var (both or neither): r = (1 - momentum) r + momentum
+ *   stat, with the unbiased variance (var P / (P - 1), P = B H W).  P < 2 is OESS_EINVAL (torch raises there); 0 <= momentum <= 1.
+ *   Three launches, no host synchronisation: per-workgroup (mean, M2) partials of shifted sums; one workgroup per channel group
+ *   merges them pairwise (Chan) in a fixed order, writes the statistics and the per-channel coefficients; the apply pass.  No raw
+ *   E[x^2] - E[x]^2, no atomics, bit-repeatable.  Dense 16-byte aligned channels (as for K14) with C % 4 == 0 in every view
+ *   take 16-byte loads and stores; anything else is read element by element.  ws:
+ *   oess_batch_norm_train_f32_workspace_bytes(B, H, W, C) bytes, 16-byte aligned (0 for an impossible geometry: B <= 65535,
+ *   B H W < 2^30); a smaller one is OESS_ENOMEM.
+ * ------------------------------------------------------------------------------------------ */
+size_t oess_batch_norm_train_f32_workspace_bytes(int B, int H, int W, int C);
+int oess_batch_norm_train_fwd_f32(const oess_f32_view_t* in, int B, int H, int W, int C, const float* gamma, const float* beta,
+                                  float eps, float momentum, float* running_mean, float* running_var, float* save_mean,
+                                  float* save_var, int relu, const oess_f32_view_t* residual, const oess_f32_view_t* out, void* ws,
+                                  size_t ws_bytes, oess_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

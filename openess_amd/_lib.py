@@ -167,6 +167,9 @@ SIGNATURES = {
     "oess_maxpool3x3s2_fwd_f32": (c_int, [c_view, c_int, c_int, c_int, c_int, c_view, c_vp]),
     "oess_global_avg_pool_f32_workspace_bytes": (c_sz, [c_int, c_int, c_int, c_int]),
     "oess_global_avg_pool_fwd_f32": (c_int, [c_view, c_int, c_int, c_int, c_int, c_vp, c_vp, c_sz, c_vp]),
+    "oess_batch_norm_train_f32_workspace_bytes": (c_sz, [c_int, c_int, c_int, c_int]),
+    "oess_batch_norm_train_fwd_f32": (c_int, [c_view, c_int, c_int, c_int, c_int, c_vp, c_vp, c_f, c_f, c_vp, c_vp, c_vp, c_vp, c_int,
+                                              c_view, c_view, c_vp, c_sz, c_vp]),
 }
 
 _lib = None

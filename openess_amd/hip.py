@@ -2095,3 +2095,58 @@ def global_avg_pool_f32(x):
     _lib.check(lib.oess_global_avg_pool_fwd_f32(ctypes.byref(vx), B, H, W, C, _ptr(out), _ptr(ws), ws.numel(), _stream()),
                "oess_global_avg_pool_fwd_f32")
     return out
+
+
+# ------------------------------------------------------------------------------------------ K17: fp32 image-teacher inference
+def batch_norm_train_f32(x, bn, relu=False, residual=None, out=None, return_stats=False):
+    """nn.BatchNorm2d in TRAIN mode [+ residual] [+ ReLU] in fp32 (oess_batch_norm_train_fwd_f32), inference only (no autograd):
+    batch statistics over B x H x W, the running statistics moved one momentum step (unbiased variance) and, for a module,
+    num_batches_tracked counted, as torch does.  x, residual, out: logical [B, C, H, W] fp32 tensors with any strides
+    (channels_last and channel slices of it take the vector path); out may be x itself.  bn: an nn.BatchNorm2d, or a dict with
+    'weight', 'bias', 'running_mean', 'running_var' (fp32 [C] or None), 'momentum' and 'eps'.  Statistics are merged from shifted
+    per-thread sums in a fixed order: stable and bit-repeatable.  Returns out, or (out, batch mean, biased batch variance)."""
+    if isinstance(bn, dict):
+        module, p = None, bn
+    else:
+        module, p = bn, dict(weight=bn.weight, bias=bn.bias, running_mean=bn.running_mean, running_var=bn.running_var,
+                             momentum=bn.momentum, eps=bn.eps)
+    if p.get('momentum', 0.1) is None:
+        raise NotImplementedError("batch_norm_train_f32: momentum=None (cumulative moving average) is not built")
+    lib = _lib.load()
+    gamma, beta, rm, rv = (p.get(k) for k in ('weight', 'bias', 'running_mean', 'running_var'))
+    gamma, beta = (None if t is None else t.detach() for t in (gamma, beta))
+    _need_gpu(x, residual, out, gamma, beta, rm, rv)
+    vx = _f32_view(x, "x")
+    B, C, H, W = x.shape
+    if (rm is None) != (rv is None):
+        raise ValueError("running_mean and running_var come together")
+    for name, t in (('weight', gamma), ('bias', beta), ('running_mean', rm), ('running_var', rv)):
+        if t is not None and (t.dtype != torch.float32 or not t.is_contiguous() or t.numel() != C):
+            raise ValueError(f"batch_norm_train_f32: {name} must be a contiguous fp32 tensor of {C} elements")
+    vr = None
+    if residual is not None:
+        if tuple(residual.shape) != (B, C, H, W):
+            raise ValueError(f"residual shape {tuple(residual.shape)} != {(B, C, H, W)}")
+        vr = _f32_view(residual, "residual")
+    if B * H * W < 2:
+        raise ValueError(f"Expected more than 1 value per channel when training, got input size {tuple(x.shape)}")
+    out = _f32_out(out, B, C, H, W, x.device)
+    vo = _f32_view(out, "out")
+    need = lib.oess_batch_norm_train_f32_workspace_bytes(B, H, W, C)
+    if need == 0:
+        raise ValueError(f"batch_norm_train_f32: no kernel for a {(B, C, H, W)} map")
+    ws = _workspace(need, x.device, tag="batchnorm_f32")
+    stats = torch.empty((2, C), dtype=torch.float32, device=x.device) if return_stats else None
+    _lib.check(lib.oess_batch_norm_train_fwd_f32(ctypes.byref(vx), B, H, W, C, _ptr(gamma), _ptr(beta), float(p.get('eps', 1e-5)),
+                                                 float(p.get('momentum', 0.1)), _ptr(rm), _ptr(rv),
+                                                 None if stats is None else _ptr(stats[0]), None if stats is None else _ptr(stats[1]),
+                                                 int(bool(relu)), _f32_ref(vr), ctypes.byref(vo), _ptr(ws), ws.numel(), _stream()),
+               "oess_batch_norm_train_fwd_f32")
+    _bump(out)
+    if rm is not None:
+        _bump(rm)
+        _bump(rv)
+    if module is not None:
+        from . import engine as _engine
+        _engine.bump_bn_counter(module)
+    return (out, stats[0], stats[1]) if return_stats else out

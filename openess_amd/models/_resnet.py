@@ -16,6 +16,7 @@ class HipConv2d(nn.Conv2d):
         self._pw = engine.PackedWeight()
         self._pw_folded = engine.PackedWeight()      # eval-mode BatchNorm folded in
         self._pw32 = engine.PackedWeightF32()        # the same in fp32 (conv_bn_f32)
+        self._pw32_plain = engine.PackedWeightF32()  # fp32 without a fold (conv_bn_train_f32, the teacher's decoder)
 
     def forward(self, x):
         if x.shape[1] % 8 or x.dtype != torch.bfloat16:
@@ -99,6 +100,29 @@ def conv_bn_f32(conv, bn, x, relu=False, residual=None, out=None, pw=None):
                           residual=residual, out=out, dilation=d)
 
 
+def conv_f32(conv, x, relu=False, out=None):
+    """The plain fp32 convolution (+ bias) of a HipConv2d through its un-folded operand cache."""
+    op = conv._pw32_plain.get(conv.weight, conv.bias, None)
+    (R, S), s, p, d = conv.kernel_size, conv.stride[0], conv.padding[0], conv.dilation[0]
+    return hip.conv2d_f32(x, op.packed, op.bias, conv.out_channels, R, S, stride=s, pad=p, act='relu' if relu else None, out=out,
+                          dilation=d)
+
+
+def conv_bn_train_f32(conv, bn, x, relu=False, residual=None):
+    """conv -> train-mode BatchNorm2d [-> + residual] [-> ReLU] in fp32 (the reference's frozen teacher stays in .train()): the
+    plain convolution, then hip.batch_norm_train_f32 in place on its output: batch statistics, the running statistics moved one
+    momentum step.  x, residual: logical [B, C, H, W] fp32 tensors, any strides.  No autograd."""
+    if not bn.training:
+        raise ValueError("conv_bn_train_f32 is the batch-statistics form: an eval-mode BatchNorm folds (conv_bn_f32)")
+    y = conv_f32(conv, x)
+    return hip.batch_norm_train_f32(y, bn, relu=relu, residual=residual, out=y)
+
+
+def conv_bn_any_f32(conv, bn, x, relu=False, residual=None):
+    """conv_bn_train_f32 or conv_bn_f32, as bn.training says: nn.BatchNorm2d's own rule."""
+    return (conv_bn_train_f32 if bn.training else conv_bn_f32)(conv, bn, x, relu=relu, residual=residual)
+
+
 def conv3x3(in_planes, out_planes, stride=1, groups=1, dilation=1):
     assert groups == 1
     return HipConv2d(in_planes, out_planes, kernel_size=3, stride=stride, padding=dilation, bias=False, dilation=dilation)
@@ -162,6 +186,14 @@ class Bottleneck(nn.Module):
         out = conv_bn_f32(self.conv2, self.bn2, out, relu=True)
         identity = x if self.downsample is None else conv_bn_f32(self.downsample[0], self.downsample[1], x)
         return conv_bn_f32(self.conv3, self.bn3, out, relu=True, residual=identity)
+
+    def forward_train_fp32(self, x):
+        """The block in fp32 with every BatchNorm in the form its own `training` flag asks for (conv_bn_any_f32): batch statistics
+        and a running-statistics step in train mode (conv + the BatchNorm's three launches), the folded conv in eval mode."""
+        out = conv_bn_any_f32(self.conv1, self.bn1, x, relu=True)
+        out = conv_bn_any_f32(self.conv2, self.bn2, out, relu=True)
+        identity = x if self.downsample is None else conv_bn_any_f32(self.downsample[0], self.downsample[1], x)
+        return conv_bn_any_f32(self.conv3, self.bn3, out, relu=True, residual=identity)
 
 
 class ResNet(nn.Module):
@@ -227,6 +259,17 @@ class ResNet(nn.Module):
             x = self.layer2(x)
             x = self.layer3(x)
             return self.layer4(x)
+
+    def features_fp32(self, x):
+        """features() in fp32: x fp32 [B, 3, H, W], any layout -> the fp32 channels_last layer4 map.  Per BatchNorm the folded
+        (eval) or the batch-statistics (train) form.  No autograd."""
+        with engine.defer_bn_counters():
+            x = conv_bn_any_f32(self.conv1, self.bn1, x, relu=True)
+            x = hip.max_pool_3x3s2_f32(x)
+            for layer in (self.layer1, self.layer2, self.layer3, self.layer4):
+                for block in layer:
+                    x = block.forward_train_fp32(x)
+            return x
 
     def forward(self, x):
         x = self.features(x)

@@ -6,7 +6,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from .. import engine, hip
-from ._resnet import Bottleneck, HipConv2d, ResNet
+from ._resnet import Bottleneck, HipConv2d, ResNet, conv_f32
 
 
 class ResNetEncoder(ResNet):
@@ -64,3 +64,26 @@ class DilationFeatureExtractor(nn.Module):
             x = hip.bilinear_resize(x, scale_factor=4, align_corners=True)
             return hip.l2_normalize(x) if self.normalize_feature else x
         return hip.bilinear_l2norm(x, 4, self.normalize_feature)
+
+    @torch.no_grad()
+    def forward_fp32(self, x):
+        """forward() in fp32, the reference's own arithmetic, on the f32-input MFMA kernels: x fp32 [B, 3, H, W]
+        -> fp32 [B, 256, H, W] unit-norm features.  Inference only (no autograd: the trainable head's backward stays bf16).
+        Every BatchNorm runs in the form its `training` flag asks for: in train mode (how the reference leaves its frozen
+        encoder) one call moves every running statistic one momentum step, as one forward() does; in eval mode the folded
+        convs of K16.  No buffer, operand or workspace is shared with forward()."""
+        return self.head_fp32(self.encode_fp32(x))
+
+    @torch.no_grad()
+    def encode_fp32(self, x):
+        if self.preprocessing:
+            x = self.preprocessing(x)
+        if x.dtype != torch.float32 or x.ndim != 4:
+            raise ValueError("forward_fp32 takes a float32 [B, 3, H, W] image batch")
+        return self.encoder.features_fp32(x)
+
+    @torch.no_grad()
+    def head_fp32(self, x):
+        x = conv_f32(self.decoder[0], x)
+        x = hip.bilinear_resize(x, scale_factor=4, align_corners=True)
+        return hip.l2_normalize(x) if self.normalize_feature else x
