@@ -729,6 +729,43 @@ int oess_batch_norm_train_fwd_f32(const oess_f32_view_t* in, int B, int H, int W
                                   float* save_var, int relu, const oess_f32_view_t* residual, const oess_f32_view_t* out, void* ws,
                                   size_t ws_bytes, oess_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------
+ * K18 fp32 SemSegE2VID training: the backward of the decoder's three layer types (stride-1 convolution, InstanceNorm2d,
+ * nearest x2 + concat) in fp32.  The data gradient of a stride-1 convolution is oess_conv2d_fwd_f32 itself on the rotated,
+ * transposed weight (hip.pack_conv_weight_f32_dgrad); these are the kernels that were missing.  Additions only: the ABI version
+ * stays.  Nothing here uses an atomic: every result repeats bit for bit, on any device.
+ *
+ * oess_conv2d_wgrad_f32: dw[co][ci][r][s] (fp32 OIHW, dense) = sum over (b, oy, ox) of dy[b, oy, ox, co] *
+ *   x[b, oy - pad + r, ox - pad + s, ci] (zero outside the map); db (nullable) [Cout] = sum of dy.  x: B x H x W x Cin view,
+ *   dy: B x H x W x Cout view.  Geometry: stride 1, dilation 1, R == S in {1, 3}, pad == (R - 1) / 2; anything else is
+ *   OESS_EINVAL and a workspace of 0.  One GEMM per tap on v_mfma_f32_32x32x2_f32, D[ci][co] reduced over the pixels in steps
+ *   of 16; dense 16-byte aligned channels in both views with Cin % 4 == 0 and Cout % 4 == 0 take 16-byte loads, anything else is
+ *   read element by element.  The pixel range is split into n ranges, n a function of the shapes alone (never of the device);
+ *   each workgroup stores its partial tile into ws and a second launch adds the ranges in index order.
+ *   ws: oess_conv2d_wgrad_f32_workspace_bytes(...) = n (R S Cin Cout + Cout) sizeof(float) bytes, 16-byte aligned.
+ * oess_instance_norm_train_fwd_f32: oess_instance_norm_fwd_f32 (same kernels, same bits) that also writes the statistics the
+ *   backward needs: save_mean, save_rstd fp32 [B][C], rstd = 1 / sqrt(var + eps).  Same workspace.
+ * oess_instance_norm_bwd_f32: backward of out = (x - mean) rstd [ReLU if relu].  With xh = (x - mean) rstd and g = dy [xh > 0]
+ *   (relu) or dy:  dx = rstd (g - mean_hw(g) - xh mean_hw(g xh)).  x (the forward's INPUT), dy and dx are B x H x W x C views;
+ *   dx may be dy itself.  mean, rstd: what the training forward saved.  A residual added after the norm takes dy unchanged (no
+ *   kernel).  Two launches: per-range sums of g and g xh (a thread's own chains, a fixed LDS tree), then the ranges in a fixed
+ *   order and the apply pass.  16-byte accesses as for the forward (mean, rstd 16-byte aligned too).
+ *   ws: oess_instance_norm_bwd_f32_workspace_bytes(B, H, W, C) bytes, 16-byte aligned (0 for an impossible geometry).
+ * oess_downsample_sum2x_f32: backward of the nearest x2 gather of oess_upsample_nearest2x_concat_f32:
+ *   dx[b, y, x, c] = ((d[2y][2x] + d[2y][2x+1]) + d[2y+1][2x]) + d[2y+1][2x+1] with d = dout (a B x 2H x 2W x C view: the first
+ *   C channels of the concat gradient); dx: B x H x W x C view.  The skip's gradient is the remaining channel slice, as it lies.
+ * ------------------------------------------------------------------------------------------ */
+size_t oess_conv2d_wgrad_f32_workspace_bytes(int B, int H, int W, int Cin, int Cout, int R, int S, int stride, int pad, int dilation);
+int oess_conv2d_wgrad_f32(const oess_f32_view_t* x, const oess_f32_view_t* dy, int B, int H, int W, int Cin, int Cout, int R, int S,
+                          int stride, int pad, int dilation, float* dw, float* db, void* ws, size_t ws_bytes, oess_stream_t stream);
+int oess_instance_norm_train_fwd_f32(const oess_f32_view_t* in, int B, int H, int W, int C, float eps, int relu,
+                                     const oess_f32_view_t* residual, const oess_f32_view_t* out, float* save_mean, float* save_rstd,
+                                     void* ws, size_t ws_bytes, oess_stream_t stream);
+size_t oess_instance_norm_bwd_f32_workspace_bytes(int B, int H, int W, int C);
+int oess_instance_norm_bwd_f32(const oess_f32_view_t* x, const oess_f32_view_t* dy, const float* mean, const float* rstd, int B, int H,
+                               int W, int C, int relu, const oess_f32_view_t* dx, void* ws, size_t ws_bytes, oess_stream_t stream);
+int oess_downsample_sum2x_f32(const oess_f32_view_t* dout, int B, int H, int W, int C, const oess_f32_view_t* dx, oess_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -170,6 +170,14 @@ SIGNATURES = {
     "oess_batch_norm_train_f32_workspace_bytes": (c_sz, [c_int, c_int, c_int, c_int]),
     "oess_batch_norm_train_fwd_f32": (c_int, [c_view, c_int, c_int, c_int, c_int, c_vp, c_vp, c_f, c_f, c_vp, c_vp, c_vp, c_vp, c_int,
                                               c_view, c_view, c_vp, c_sz, c_vp]),
+    "oess_conv2d_wgrad_f32_workspace_bytes": (c_sz, [c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int]),
+    "oess_conv2d_wgrad_f32": (c_int, [c_view, c_view, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_vp, c_vp,
+                                      c_vp, c_sz, c_vp]),
+    "oess_instance_norm_train_fwd_f32": (c_int, [c_view, c_int, c_int, c_int, c_int, c_f, c_int, c_view, c_view, c_vp, c_vp, c_vp, c_sz,
+                                                 c_vp]),
+    "oess_instance_norm_bwd_f32_workspace_bytes": (c_sz, [c_int, c_int, c_int, c_int]),
+    "oess_instance_norm_bwd_f32": (c_int, [c_view, c_view, c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, c_view, c_vp, c_sz, c_vp]),
+    "oess_downsample_sum2x_f32": (c_int, [c_view, c_int, c_int, c_int, c_int, c_view, c_vp]),
 }
 
 _lib = None

@@ -34,6 +34,8 @@ struct NormParams {
     int nchunk, chunk_pix;
     float eps;
     float* part;                         // [B][nchunk][2][C]: mean, M2
+    float* save_mean;                    // [B][C], nullable: the statistics, kept for a backward pass (K18)
+    float* save_rstd;
 };
 
 #include "f32_chan.h"
@@ -115,6 +117,13 @@ __global__ __launch_bounds__(NT) void instnorm_apply_f32_kernel(const NormParams
             stat[(lane * V + i) * 2] = m[i];
             stat[(lane * V + i) * 2 + 1] = active ? 1.0f / sqrtf(q[i] / n + P.eps) : 0.f;
         }
+        if (P.save_mean && chunk == 0 && active) {
+#pragma unroll
+            for (int i = 0; i < V; ++i) {
+                P.save_mean[(long long)b * P.C + c + i] = stat[(lane * V + i) * 2];
+                P.save_rstd[(long long)b * P.C + c + i] = stat[(lane * V + i) * 2 + 1];
+            }
+        }
     }
     __syncthreads();
     if (!active) return;
@@ -167,19 +176,8 @@ __global__ __launch_bounds__(NT) void upsample_nearest2x_concat_f32_kernel(const
     stv<V>(P.out + b * P.ob + y * P.oy + x * P.ox + c * P.oc, ldv<V>(src));
 }
 
-
-}  // namespace
-
-extern "C" {
-
-size_t oess_instance_norm_f32_workspace_bytes(int B, int H, int W, int C) {
-    if (!geometry_ok(B, H, W, C)) return 0;
-    return (size_t)B * MAX_CHUNKS * 2 * C * sizeof(float);
-}
-
-int oess_instance_norm_fwd_f32(const oess_f32_view_t* in, int B, int H, int W, int C, float eps, int relu,
-                               const oess_f32_view_t* residual, const oess_f32_view_t* out, void* ws, size_t ws_bytes,
-                               oess_stream_t stream) {
+int norm_forward(const oess_f32_view_t* in, int B, int H, int W, int C, float eps, int relu, const oess_f32_view_t* residual,
+                 const oess_f32_view_t* out, float* save_mean, float* save_rstd, void* ws, size_t ws_bytes, oess_stream_t stream) {
     if (!view_ok(in) || !view_ok(out) || (residual && !residual->data) || !ws || ((uintptr_t)ws & 15) != 0) return OESS_EINVAL;
     if (!geometry_ok(B, H, W, C) || !(eps >= 0.f) || (relu != 0 && relu != 1)) return OESS_EINVAL;
     if (ws_bytes < oess_instance_norm_f32_workspace_bytes(B, H, W, C)) return OESS_ENOMEM;
@@ -210,6 +208,7 @@ int oess_instance_norm_fwd_f32(const oess_f32_view_t* in, int B, int H, int W, i
     P.nchunk = nchunk; P.chunk_pix = chunk_pix;
     P.eps = eps;
     P.part = (float*)ws;
+    P.save_mean = save_mean; P.save_rstd = save_rstd;
     const dim3 grid((unsigned)nchunk, (unsigned)ncg, (unsigned)B);
     if (vec) {
         hipLaunchKernelGGL(instnorm_partials_f32_kernel<4>, grid, dim3(NT), 0, (hipStream_t)stream, P);
@@ -220,6 +219,28 @@ int oess_instance_norm_fwd_f32(const oess_f32_view_t* in, int B, int H, int W, i
     }
     OESS_HIP(hipGetLastError());
     return OESS_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+size_t oess_instance_norm_f32_workspace_bytes(int B, int H, int W, int C) {
+    if (!geometry_ok(B, H, W, C)) return 0;
+    return (size_t)B * MAX_CHUNKS * 2 * C * sizeof(float);
+}
+
+int oess_instance_norm_fwd_f32(const oess_f32_view_t* in, int B, int H, int W, int C, float eps, int relu,
+                               const oess_f32_view_t* residual, const oess_f32_view_t* out, void* ws, size_t ws_bytes,
+                               oess_stream_t stream) {
+    return norm_forward(in, B, H, W, C, eps, relu, residual, out, nullptr, nullptr, ws, ws_bytes, stream);
+}
+
+int oess_instance_norm_train_fwd_f32(const oess_f32_view_t* in, int B, int H, int W, int C, float eps, int relu,
+                                     const oess_f32_view_t* residual, const oess_f32_view_t* out, float* save_mean, float* save_rstd,
+                                     void* ws, size_t ws_bytes, oess_stream_t stream) {
+    if (!save_mean || !save_rstd) return OESS_EINVAL;
+    return norm_forward(in, B, H, W, C, eps, relu, residual, out, save_mean, save_rstd, ws, ws_bytes, stream);
 }
 
 int oess_upsample_nearest2x_concat_f32(const oess_f32_view_t* in, int B, int H, int W, int C, const oess_f32_view_t* skip,

@@ -220,6 +220,25 @@ class PackedWeightF32:
             self.key = key
         return self
 
+    def get_train(self, weight, bias=None, ver=None):
+        """Operands of hip.conv2d_f32_train (K18): the forward operand of the fp32 parameter itself (no fold, no rounding) and,
+        packed on the first dgrad() of a weight version, the data-gradient operand.  ver: the version key of a weight that is
+        computed from parameters (the composed head), whose own counter never moves."""
+        key = (param_versions(weight, bias) if ver is None else (ver,)) + ('train',)
+        if key != self.key:
+            with torch.no_grad():
+                self._w = weight.detach()
+                self.packed = hip.pack_conv_weight_f32(self._w)
+                self.packed_dgrad = None
+                self.bias = None if bias is None else bias.detach().contiguous()
+            self.key = key
+        return self
+
+    def dgrad(self):
+        if self.packed_dgrad is None:
+            self.packed_dgrad = hip.pack_conv_weight_f32_dgrad(self._w)
+        return self.packed_dgrad
+
     def get_composed(self, params, make):
         """Operand of a weight that is a function of several parameters (SemSegE2VID's composed head): `make()` returns the
         float64 (weight [Cout, Cin, R, S], bias | None); it runs, and the result is rounded once and packed, only when the

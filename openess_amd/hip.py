@@ -2150,3 +2150,200 @@ def batch_norm_train_f32(x, bn, relu=False, residual=None, out=None, return_stat
         from . import engine as _engine
         _engine.bump_bn_counter(module)
     return (out, stats[0], stats[1]) if return_stats else out
+
+
+# ------------------------------------------------------------------------------------------ K18: fp32 SemSegE2VID training
+def pack_conv_weight_f32_dgrad(w):
+    """Conv2d weight [Cout, Cin, R, S] -> the operand with which oess_conv2d_fwd_f32 computes the DATA gradient of the stride-1
+    convolution: dX = conv(dY, W', pad' = R - 1 - pad) with W'[ci][co][r][s] = W[co][ci][R - 1 - r][S - 1 - s], in
+    pack_conv_weight_f32's layout: [ceil16(R S Cout)][ceil32(Cin)], row (r S + s) Cout + co, column ci.  Needs no library."""
+    Co, Ci, R, S = w.shape
+    Kp, Cp = (R * S * Co + 15) // 16 * 16, (Ci + 31) // 32 * 32
+    out = torch.zeros((Kp, Cp), dtype=torch.float32, device=w.device)
+    out[:R * S * Co, :Ci] = w.detach().float().flip(2, 3).permute(2, 3, 0, 1).reshape(R * S * Co, Ci)
+    return out
+
+
+def _wgrad_f32_check(x, dy, R, stride, pad, dilation):
+    for name, t in (("x", x), ("dy", dy)):
+        if t.dtype != torch.float32 or t.ndim != 4:
+            raise ValueError(f"conv2d_wgrad_f32: {name} must be a 4-D fp32 tensor [B, C, H, W]")
+    if stride != 1 or dilation != 1 or R not in (1, 3) or pad != (R - 1) // 2:
+        raise ValueError(f"conv2d_wgrad_f32 runs stride 1, dilation 1, 1 x 1 or 3 x 3 taps with 'same' padding, not "
+                         f"stride {stride}, dilation {dilation}, {R} x {R}, pad {pad}")
+    if (x.shape[0], x.shape[2], x.shape[3]) != (dy.shape[0], dy.shape[2], dy.shape[3]):
+        raise ValueError(f"conv2d_wgrad_f32: x {tuple(x.shape)} and dy {tuple(dy.shape)} must share B, H, W")
+
+
+def conv2d_wgrad_f32_splits(B, H, W, Cin, Cout, R):
+    """Number of pixel ranges oess_conv2d_wgrad_f32 splits its reduction into for these shapes (a function of the shapes alone),
+    read off the workspace query: n (R R Cin Cout + Cout) floats."""
+    need = _lib.load().oess_conv2d_wgrad_f32_workspace_bytes(B, H, W, Cin, Cout, R, R, 1, (R - 1) // 2, 1)
+    return need // (4 * (R * R * Cin * Cout + Cout))
+
+
+def conv2d_wgrad_f32(x, dy, R, stride=1, pad=None, dilation=1, want_db=True):
+    """Weight and bias gradient of y = conv(x, w, stride 1, 'same' pad) + b in fp32 on the f32-input MFMA (oess_conv2d_wgrad_f32):
+    (dw [Cout, Cin, R, R], db [Cout] or None).  x [B, Cin, H, W], dy [B, Cout, H, W]: fp32 tensors with any strides, read where
+    they lie (channels_last and channel slices of it take the vector loads).  Fixed summation order: bit-repeatable."""
+    pad = (R - 1) // 2 if pad is None else pad
+    _wgrad_f32_check(x, dy, R, stride, pad, dilation)
+    _need_gpu(x, dy)
+    lib = _lib.load()
+    B, Cin, H, W = x.shape
+    Cout = dy.shape[1]
+    need = lib.oess_conv2d_wgrad_f32_workspace_bytes(B, H, W, Cin, Cout, R, R, stride, pad, dilation)
+    if need == 0:
+        raise ValueError(f"conv2d_wgrad_f32: no kernel for x {tuple(x.shape)}, dy {tuple(dy.shape)}, {R} x {R}")
+    ws = _workspace(need, x.device, tag="wgrad_f32")
+    dw = torch.empty((Cout, Cin, R, R), dtype=torch.float32, device=x.device)
+    db = torch.empty((Cout,), dtype=torch.float32, device=x.device) if want_db else None
+    vx, vg = _f32_view(x, "x"), _f32_view(dy, "dy")
+    _lib.check(lib.oess_conv2d_wgrad_f32(ctypes.byref(vx), ctypes.byref(vg), B, H, W, Cin, Cout, R, R, stride, pad, dilation, _ptr(dw),
+                                         _ptr(db), _ptr(ws), ws.numel(), _stream()), "oess_conv2d_wgrad_f32")
+    return dw, db
+
+
+class _Conv2dF32Train(torch.autograd.Function):
+    """conv(x, weight, stride 1, 'same' pad) + bias in fp32: forward oess_conv2d_fwd_f32, backward oess_conv2d_wgrad_f32 and, when
+    x needs a gradient, oess_conv2d_fwd_f32 on the rotated, transposed weight."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, pad, pw, ver):
+        Cout, _, R, _ = weight.shape
+        op = pw.get_train(weight, bias, ver)
+        y = conv2d_f32(x, op.packed, op.bias, Cout, R, R, 1, pad)
+        ctx.save_for_backward(x, weight)
+        ctx.meta = (pad, op, op.key, bias is not None)
+        return y
+
+    @staticmethod
+    def backward(ctx, gy):
+        x, weight = ctx.saved_tensors
+        pad, op, key, has_bias = ctx.meta
+        Cout, Cin, R, _ = weight.shape
+        if gy.dtype != torch.float32:
+            gy = gy.float()
+        gx = gw = gb = None
+        need_gb = has_bias and ctx.needs_input_grad[2]
+        if ctx.needs_input_grad[1] or need_gb:
+            gw, gb = conv2d_wgrad_f32(x, gy, R, 1, pad, 1, want_db=need_gb)
+            if not ctx.needs_input_grad[1]:
+                gw = None
+        if ctx.needs_input_grad[0]:
+            # the operand of the forward's weight version; a holder that moved on since is not this node's
+            wd = op.dgrad() if op.key == key else pack_conv_weight_f32_dgrad(weight)
+            gx = conv2d_f32(gy, wd, None, Cin, R, R, 1, R - 1 - pad)
+        return gx, gw, gb, None, None, None
+
+
+def conv2d_f32_train(x, weight, bias=None, stride=1, pad=None, dilation=1, act=None, pw=None, ver=None):
+    """Differentiable fp32 convolution for training (K18): conv2d_f32 of x with the PARAMETER tensors weight [Cout, Cin, R, R]
+    (R in {1, 3}) and bias, stride 1, 'same' padding.  Backward: the weight / bias gradient on oess_conv2d_wgrad_f32 and the data
+    gradient on the forward kernel with the operand of pack_conv_weight_f32_dgrad; a gradient nobody asks for (the latents of a
+    frozen encoder) is not computed.  pw: an engine.PackedWeightF32 that keeps the two packed operands per weight version (ver:
+    the version key of a weight that is itself computed from parameters); without it the operands are packed per call.
+    act: None only (the decoder's ReLUs sit behind the norm).  fp32 in, fp32 out; everything else raises before any launch."""
+    if x.dtype != torch.float32 or weight.dtype != torch.float32 or (bias is not None and bias.dtype != torch.float32):
+        raise ValueError("conv2d_f32_train takes fp32 tensors (the bf16 training path is engine.conv2d_train)")
+    if x.ndim != 4 or weight.ndim != 4 or weight.shape[2] != weight.shape[3] or weight.shape[1] != x.shape[1]:
+        raise ValueError(f"conv2d_f32_train: x {tuple(x.shape)} does not fit a weight {tuple(weight.shape)}")
+    R = weight.shape[2]
+    pad = (R - 1) // 2 if pad is None else pad
+    if stride != 1 or dilation != 1 or R not in (1, 3) or pad != (R - 1) // 2:
+        raise ValueError(f"conv2d_f32_train runs stride 1, dilation 1, 1 x 1 or 3 x 3 taps with 'same' padding, not stride {stride}, "
+                         f"dilation {dilation}, {R} x {R}, pad {pad} (strided and dilated weight gradients are not built)")
+    if act is not None:
+        raise ValueError("conv2d_f32_train has no fused activation")
+    _need_gpu(x, weight, bias)
+    if pw is None:
+        from . import engine as _engine
+        pw = _engine.PackedWeightF32()
+    return _Conv2dF32Train.apply(x, weight, bias, pad, pw, ver)
+
+
+class _InstanceNormF32Train(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, residual, relu, eps):
+        lib = _lib.load()
+        B, C, H, W = x.shape
+        vx = _f32_view(x, "x")
+        vr = None if residual is None else _f32_view(residual, "residual")
+        out = _f32_out(None, B, C, H, W, x.device)
+        vo = _f32_view(out, "out")
+        stats = torch.empty((2, B, C), dtype=torch.float32, device=x.device)
+        need = lib.oess_instance_norm_f32_workspace_bytes(B, H, W, C)
+        if need == 0:
+            raise ValueError(f"instance_norm_f32_train: no kernel for a {(B, C, H, W)} map")
+        ws = _workspace(need, x.device, tag="instnorm_f32")
+        _lib.check(lib.oess_instance_norm_train_fwd_f32(ctypes.byref(vx), B, H, W, C, float(eps), int(relu), _f32_ref(vr),
+                                                        ctypes.byref(vo), _ptr(stats[0]), _ptr(stats[1]), _ptr(ws), ws.numel(),
+                                                        _stream()), "oess_instance_norm_train_fwd_f32")
+        ctx.save_for_backward(x, stats)
+        ctx.relu, ctx.has_res = relu, residual is not None
+        return out
+
+    @staticmethod
+    def backward(ctx, gy):
+        lib = _lib.load()
+        x, stats = ctx.saved_tensors
+        B, C, H, W = x.shape
+        if gy.dtype != torch.float32:
+            gy = gy.float()
+        dx = None
+        if ctx.needs_input_grad[0]:
+            dx = _f32_out(None, B, C, H, W, x.device)
+            vx, vg, vd = _f32_view(x, "x"), _f32_view(gy, "dy"), _f32_view(dx, "dx")
+            need = lib.oess_instance_norm_bwd_f32_workspace_bytes(B, H, W, C)
+            ws = _workspace(need, x.device, tag="instnorm_bwd_f32")
+            _lib.check(lib.oess_instance_norm_bwd_f32(ctypes.byref(vx), ctypes.byref(vg), _ptr(stats[0]), _ptr(stats[1]), B, H, W, C,
+                                                      int(ctx.relu), ctypes.byref(vd), _ptr(ws), ws.numel(), _stream()),
+                       "oess_instance_norm_bwd_f32")
+        return dx, (gy if ctx.has_res and ctx.needs_input_grad[1] else None), None, None
+
+
+def instance_norm_f32_train(x, relu=False, residual=None, eps=1e-5):
+    """Differentiable nn.InstanceNorm2d(affine=False, eps) [+ residual] [+ ReLU] in fp32 (K18), not in place: the forward is
+    instance_norm_f32's kernels and bits, and keeps x and the per-(sample, channel) mean and rstd for
+    oess_instance_norm_bwd_f32.  The residual's gradient is the incoming gradient itself (no copy)."""
+    if x.dtype != torch.float32 or x.ndim != 4 or (residual is not None and residual.dtype != torch.float32):
+        raise ValueError("instance_norm_f32_train takes 4-D fp32 tensors (the bf16 training path is hip.instance_norm)")
+    if relu and residual is not None:
+        raise NotImplementedError("ReLU after the residual add is not a pattern of the reference")
+    if residual is not None and tuple(residual.shape) != tuple(x.shape):
+        raise ValueError(f"residual shape {tuple(residual.shape)} != {tuple(x.shape)}")
+    _need_gpu(x, residual)
+    return _InstanceNormF32Train.apply(x, residual, bool(relu), float(eps))
+
+
+class _UpsampleConcatF32Train(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, skip):
+        ctx.C = x.shape[1]
+        return upsample2x_concat_f32(x, skip)
+
+    @staticmethod
+    def backward(ctx, g):
+        lib = _lib.load()
+        C = ctx.C
+        if g.dtype != torch.float32:
+            g = g.float()
+        B, _, Ho, Wo = g.shape
+        gx = None
+        if ctx.needs_input_grad[0]:
+            gx = _f32_out(None, B, C, Ho // 2, Wo // 2, g.device)
+            vg, vx = _f32_view(g[:, :C], "g"), _f32_view(gx, "gx")
+            _lib.check(lib.oess_downsample_sum2x_f32(ctypes.byref(vg), B, Ho // 2, Wo // 2, C, ctypes.byref(vx), _stream()),
+                       "oess_downsample_sum2x_f32")
+        gskip = g[:, C:] if g.shape[1] > C and ctx.needs_input_grad[1] else None
+        return gx, gskip
+
+
+def upsample2x_concat_f32_train(x, skip=None):
+    """Differentiable upsample2x_concat_f32 (K18): the gradient of x is the fixed-order sum of the four pixels it was copied to
+    (oess_downsample_sum2x_f32, reading the first C channels of the concat gradient where they lie); the gradient of skip is the
+    remaining channel slice of the incoming gradient, a view."""
+    if x.dtype != torch.float32 or x.ndim != 4 or (skip is not None and skip.dtype != torch.float32):
+        raise ValueError("upsample2x_concat_f32_train takes 4-D fp32 tensors (the bf16 training path is hip.upsample2x_concat)")
+    _need_gpu(x, skip)
+    return _UpsampleConcatF32Train.apply(x, skip)

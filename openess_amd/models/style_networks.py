@@ -29,12 +29,17 @@ class _HipConv2d(nn.Conv2d):
         super().__init__(*a, **k)
         self._pw = engine.PackedWeight()
         self._pw32 = engine.PackedWeightF32()
+        self._pw32_train = engine.PackedWeightF32()
 
     def forward_f32(self, x, act=None, out=None):
         """fp32 inference (K15): act(conv(x) + bias) on the f32-input MFMA kernel, operand cached per parameter versions."""
         pw = self._pw32.get(self.weight, self.bias)
         return hip.conv2d_f32(x, pw.packed, pw.bias, self.out_channels, self.kernel_size[0], self.kernel_size[1], self.stride[0],
                               self.padding[0], act=act, out=out)
+
+    def forward_f32_train(self, x):
+        """fp32 training (K18): conv(x) + bias under autograd, forward and backward on the f32-input MFMA kernels."""
+        return hip.conv2d_f32_train(x, self.weight, self.bias, self.stride[0], self.padding[0], self.dilation[0], pw=self._pw32_train)
 
     def forward(self, x, out_f32=False):
         return engine.conv2d_train(x, self.weight, self.bias, self._pw, self.kernel_size[0], self.stride[0],
@@ -65,6 +70,9 @@ class ReLUINSConv2d(nn.Module):
         y = self.model[0].forward_f32(x)
         return hip.instance_norm_f32(y, relu=True, eps=self.model[1].eps, out=y)
 
+    def forward_f32_train(self, x):
+        return hip.instance_norm_f32_train(self.model[0].forward_f32_train(x), relu=True, eps=self.model[1].eps)
+
 
 class INSResBlock(nn.Module):
     def __init__(self, inplanes, planes, stride=1, dropout=0.0):
@@ -86,6 +94,12 @@ class INSResBlock(nn.Module):
         y = hip.instance_norm_f32(y, relu=True, eps=self.model[1].eps, out=y)
         z = self.model[3].forward_f32(y)
         return hip.instance_norm_f32(z, residual=x, eps=self.model[4].eps, out=z)
+
+    def forward_f32_train(self, x):
+        if len(self.model) > 5:
+            raise NotImplementedError("forward_f32_train has no dropout (INSResBlock(dropout > 0))")
+        y = hip.instance_norm_f32_train(self.model[0].forward_f32_train(x), relu=True, eps=self.model[1].eps)
+        return hip.instance_norm_f32_train(self.model[3].forward_f32_train(y), residual=x, eps=self.model[4].eps)
 
 
 def compose_head_f64(w256, b256, w512, b512, text):
@@ -148,6 +162,7 @@ class SemSegE2VID(nn.Module):
             self.linear_probe = nn.Conv2d(text_categories, text_categories, 1)
         self._pw_head = engine.PackedWeight()
         self._pw32_head, self._pw32_probe = engine.PackedWeightF32(), engine.PackedWeightF32()
+        self._pw32_head_train = engine.PackedWeightF32()
 
     def update_skip_dict(self, skips, x, sz_in):
         rem, scale = sz_in % x.shape[3], sz_in // x.shape[3]
@@ -241,4 +256,42 @@ class SemSegE2VID(nn.Module):
                 pp = self._pw32_probe.get(self.linear_probe.weight, self.linear_probe.bias)
                 logits = hip.conv2d_f32(logits, pp.packed, pp.bias, K, 1, 1)
             self.update_skip_dict(out, logits, sz_in)
+        return out, x_ch256
+
+    def forward_fp32_train(self, input_dict):
+        """fp32 training (K18): forward_fp32 under autograd.  Same inputs, refusals and return structure; every layer is an fp32
+        autograd function of hip (conv2d_f32_train, instance_norm_f32_train, upsample2x_concat_f32_train), so the decoder's
+        parameters (and text_embeddings when it is a parameter) receive fp32 gradients; latents that need no gradient (the frozen
+        encoder's) get none computed.  The head is conv2d_f32_train on the operator of _composed_head(), composed in fp32 by
+        autograd (forward_fp32 composes it in float64 and rounds once: the logits agree within the fp32 bound, not bit for bit).
+        With if_linear_probing the frozen decoder runs under no_grad and only hip.linear_probe trains."""
+        self.check_fp32()
+        for k in (1, 2, 4, 8):
+            if input_dict[k].dtype != torch.float32:
+                raise ValueError("forward_fp32_train takes the fp32 latents of the fp32 E2VID path")
+        frozen = self.if_linear_probing
+        with torch.no_grad() if frozen else torch.enable_grad():
+            sz_in = input_dict[1].shape[3]
+            x = input_dict[8]
+            out = {8: x}
+            for layer in self.decoder_scale_1:
+                x = layer.forward_f32_train(x)
+            x = hip.upsample2x_concat_f32_train(x, input_dict[4])
+            for layer in self.decoder_scale_2:
+                x = layer.forward_f32_train(x)
+            self.update_skip_dict(out, x, sz_in)
+            x = hip.upsample2x_concat_f32_train(x, input_dict[2])
+            for layer in self.decoder_scale_3:
+                x = layer.forward_f32_train(x)
+            self.update_skip_dict(out, x, sz_in)
+            x = hip.upsample2x_concat_f32_train(x)
+            x = self.decoder_scale_4[0].forward_f32_train(x)
+            x_ch256 = self.decoder_ch256[0].forward_f32_train(x) if self.materialize_ch256 else None
+            wf, bf = self._composed_head()
+            ver = tuple(p._version for p in (self.decoder_ch256[0].weight, self.decoder_ch256[0].bias,
+                                             self.decoder_ch512[0].weight, self.decoder_ch512[0].bias, self.text_embeddings))
+            logits = hip.conv2d_f32_train(x, wf, bf, pw=self._pw32_head_train, ver=ver)
+        if frozen:
+            logits = hip.linear_probe(logits, self.linear_probe)
+        self.update_skip_dict(out, logits, sz_in)
         return out, x_ch256
