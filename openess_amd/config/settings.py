@@ -4,7 +4,8 @@ that every file under the reference's config/ tree loads unchanged and the train
 Differences, all opt-in: `dataset_path: 'synthetic'` (or a missing directory together with
 OPENESS_ALLOW_MISSING_DATA=1) selects the synthetic provider instead of failing the isdir assertion
 (settings.py:117); `generate_log=False` creates nothing on disk, exactly like the reference.
-`eval_precision: fp32` in the `clip:` block (next to `use_amp`) validates the stage-2/3 event networks in fp32.
+`eval_precision: fp32` in the `clip:` block (next to `use_amp`) validates the stage-2/3 event networks in fp32;
+`train_precision: fp32` next to it trains them in fp32 (frozen E2VID + SemSegE2VID decoder).
 Quirk reproduced on purpose: `if_linear_probing` is read from the `clip:` block only (settings.py:258), so the
 reference's config/linear_probe/** files, which put it at top level, dispatch to OpenESSModel.
 """
@@ -164,3 +165,8 @@ class Settings:
         self.eval_precision = c.get('eval_precision', 'bf16')
         if self.eval_precision not in ('bf16', 'fp32'):
             raise ValueError(f"clip.eval_precision must be 'bf16' or 'fp32', got {self.eval_precision!r}")
+        # arithmetic of the stage-2/3 training step: 'bf16' (storage; fp32 accumulation) or 'fp32' (the reference's use_amp: False,
+        # DESIGN.md K19); independent of eval_precision and of use_amp
+        self.train_precision = c.get('train_precision', 'bf16')
+        if self.train_precision not in ('bf16', 'fp32'):
+            raise ValueError(f"clip.train_precision must be 'bf16' or 'fp32', got {self.train_precision!r}")

@@ -1,8 +1,9 @@
 """Mirror of e2vid/image_reconstructor.py:ImageReconstructor (:18-123) for the training path:
 preprocess -> pad -> recurrent model step -> keep state.  No CudaTimer syncs in the hot loop.
 PostProcessor (:126-140) of the offline reconstruction: unsharp mask + intensity rescaling in one HIP pass.
-options.precision = 'fp32' (offline reconstruction only) runs the whole network in fp32 (UNetRecurrent.forward_fp32), as the
-reference does; the default 'bf16' is the training path's bf16-storage kernels."""
+options.precision = 'fp32' runs the whole network in fp32 (UNetRecurrent.forward_fp32), as the reference does: the offline
+reconstruction, fp32 validation and (latents_only: head and encoders alone) the frozen front end of an fp32 training step; the
+default 'bf16' is the training path's bf16-storage kernels."""
 from types import SimpleNamespace
 
 import torch
@@ -35,7 +36,7 @@ class ImageReconstructor:
         self.skew = not bool(getattr(options, 'no_skew', False))
 
     def update_reconstruction(self, event_tensor, event_tensor_id=None, stamp=None, channel_slice=None, reconstruct=False, wavefront=None,
-                              need_latents=True):
+                              need_latents=True, latents_only=False):
         """event_tensor: fp32 [B, num_bins, H, W] (reference contract), or -- fused form -- the whole
         [B, C_total, H, W] event tensor plus channel_slice=(c0, cs) so that the slice, the normalisation
         and the NHWC re-layout are one kernel.  Returns (img | None, states, latent): the trainers discard the image
@@ -44,11 +45,15 @@ class ImageReconstructor:
         need_latents=False: the caller drops this call's latents (all but the last sub-window of a step): latent[1] (the head
         output) is None and is never written to memory (head + encoder-0 conv in one kernel).  With `self.skew` (default) such
         calls also run the recurrent encoder on the skewed schedule: the returned states hold levels 1, 2 one / two sub-windows
-        behind until the next call with need_latents=True (or reconstruct=True) drains them -- same results, fewer launches."""
+        behind until the next call with need_latents=True (or reconstruct=True) drains them -- same results, fewer launches.
+        latents_only=True (precision 'fp32', whose step computes the image by default): stop after the encoders; img is None,
+        states and latents are the same bits.  The bf16 step already stops there unless reconstruct=True, which contradicts it."""
         from .model.unet import check_states
         check_states(self.last_states_for_each_channel['grayscale'], self.precision)
+        if latents_only and reconstruct:
+            raise ValueError("latents_only=True asks for no image, reconstruct=True for one")
         if self.precision == 'fp32':
-            return self._update_fp32(event_tensor, channel_slice, wavefront, need_latents)
+            return self._update_fp32(event_tensor, channel_slice, wavefront, need_latents, latents_only)
         with torch.no_grad():
             if channel_slice is None:
                 events = event_tensor.to(self.device).float().contiguous()
@@ -77,9 +82,10 @@ class ImageReconstructor:
             self.last_states_for_each_channel['grayscale'] = None if self.no_recurrent else states
         return img, states, latent
 
-    def _update_fp32(self, event_tensor, channel_slice, wavefront, need_latents):
+    def _update_fp32(self, event_tensor, channel_slice, wavefront, need_latents, latents_only=False):
         """fp32 step: EventPreprocessor (reference contract, fp32 out) -> reflection pad -> UNetRecurrent.forward_fp32.  The image
-        is always computed (the fp32 path is the offline reconstruction); the bf16 schedules have no fp32 form and are refused."""
+        is computed (the offline reconstruction) unless latents_only (a training step); the bf16 schedules have no fp32 form and
+        are refused."""
         if wavefront is not None:
             raise ValueError("precision='fp32': the wavefront schedule (one HIP stream per level) is a bf16-path option")
         if not need_latents:
@@ -96,7 +102,8 @@ class ImageReconstructor:
                     x = hip.masked_normalize_slice(event_tensor, c0, cs)
             if self.crop.needs_pad:
                 x = self.crop.pad(x)
-            img, states, latent = self.model.forward_fp32(x, self.last_states_for_each_channel['grayscale'])
+            img, states, latent = self.model.forward_fp32(x, self.last_states_for_each_channel['grayscale'],
+                                                          reconstruct=not latents_only)
             self.last_states_for_each_channel['grayscale'] = None if self.no_recurrent else states
         return img, states, latent
 

@@ -32,9 +32,9 @@ class E2VIDRecurrent(BaseE2VID):
         return self.unetrecurrent.forward(event_tensor, prev_states, reconstruct=reconstruct, wavefront=wavefront,
                                           need_head=need_head, raw=raw, skew=skew)
 
-    def forward_fp32(self, event_tensor, prev_states):
-        """fp32 inference (UNetRecurrent.forward_fp32): (img, states, latent)."""
-        return self.unetrecurrent.forward_fp32(event_tensor, prev_states)
+    def forward_fp32(self, event_tensor, prev_states, reconstruct=True):
+        """fp32 inference (UNetRecurrent.forward_fp32): (img, states, latent); reconstruct=False stops after the encoders."""
+        return self.unetrecurrent.forward_fp32(event_tensor, prev_states, reconstruct=reconstruct)
 
 
 # architecture of E2VID_lightweight.pth.tar (SURVEY.md 8a row a9); used for random-init synthetic runs

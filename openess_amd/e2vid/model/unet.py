@@ -248,11 +248,13 @@ class UNetRecurrent(nn.Module):
         if self.skip_type != 'sum':
             raise NotImplementedError("E2VID checkpoints use skip_type 'sum'")
 
-    def forward_fp32(self, x, prev_states):
+    def forward_fp32(self, x, prev_states, reconstruct=True):
         """fp32 inference (K14, offline reconstruction): the whole UNetRecurrent forward of the reference (unet.py:146-170) on the
         f32-input MFMA kernels.  x: fp32 [B, num_bins, H, W] (any strides).  Returns (img fp32 [B, 1, H, W], states, latent) with
         the meaning of forward(..., reconstruct=True); latents are fp32 logical-NCHW tensors in channels_last storage (the encoder
-        outputs are the hidden-state halves of the states' cat(x, h) buffers: the next step overwrites them), states are fp32."""
+        outputs are the hidden-state halves of the states' cat(x, h) buffers: the next step overwrites them), states are fp32.
+        reconstruct=False (a training step, which reads the latents alone): returns after the encoders, img is None; the head and
+        the encoders run the same launches on the same operands, so states and latents are the same bits."""
         self.check_fp32()
         check_states(prev_states, 'fp32')
         if x.dtype != torch.float32 or x.ndim != 4 or x.shape[1] != self.num_input_channels:
@@ -266,6 +268,8 @@ class UNetRecurrent(nn.Module):
             x, state = encoder.forward_f32(x, prev_states[i])
             blocks.append(x)
             states.append(state)
+        if not reconstruct:
+            return None, states, _latents(head, blocks)
         for resblock in self.resblocks:
             x = resblock.forward_f32(x)
         for i, decoder in enumerate(self.decoders):

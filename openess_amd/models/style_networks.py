@@ -208,16 +208,22 @@ class SemSegE2VID(nn.Module):
         self.update_skip_dict(out, logits, sz_in)
         return out, x_ch256
 
+    @staticmethod
+    def check_fp32_config(skip_type='concat', materialize_ch256=True):
+        """check_fp32's refusals that follow from the constructor arguments alone, for a caller that must refuse before it
+        builds anything (the trainers' train_precision: fp32)."""
+        if skip_type != 'concat':
+            raise NotImplementedError(f"forward_fp32 runs skip_type='concat' (every shipped config), not {skip_type!r}")
+        if materialize_ch256 == 'pooled':
+            raise NotImplementedError("forward_fp32 has no 'pooled' form of x_ch256 (a pre-training option of the bf16 path)")
+
     def check_fp32(self):
         """The configurations forward_fp32 runs: skip_type 'concat' (with 'sum' the reference's own channel counts do not fit:
         ReLUINSConv2d(256, ...) would receive 128 channels), no dropout in an INSResBlock; raises otherwise, before any launch."""
-        if self.skip_type != 'concat':
-            raise NotImplementedError(f"forward_fp32 runs skip_type='concat' (every shipped config), not {self.skip_type!r}")
+        self.check_fp32_config(self.skip_type, self.materialize_ch256)
         for m in self.modules():
             if isinstance(m, nn.Dropout) and m.p > 0:
                 raise NotImplementedError("forward_fp32 has no dropout (INSResBlock(dropout > 0))")
-        if self.materialize_ch256 == 'pooled':
-            raise NotImplementedError("forward_fp32 has no 'pooled' form of x_ch256 (a pre-training option of the bf16 path)")
 
     def _head_f32(self):
         c256, c512 = self.decoder_ch256[0], self.decoder_ch512[0]

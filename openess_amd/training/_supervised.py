@@ -30,6 +30,19 @@ class SupervisedTrainer(BaseTrainer):
             raise NotImplementedError("eval_precision: fp32 is not wired for frame2recon: the key switches val_step of frame2voxel / "
                                       "recon2voxel only.  DeepLabv3 in fp32 is reached through val_logits(batch, precision='fp32') "
                                       "and tools/eval_precision.py --config-option frame2recon")
+        # `train_precision` (optional YAML key, clip block): arithmetic of the training step, independent of
+        # eval_precision.  What fp32 cannot train is refused here, before any model is built, naming the missing piece.
+        self.train_precision = getattr(settings, 'train_precision', 'bf16')
+        if self.train_precision not in ('bf16', 'fp32'):
+            raise ValueError(f"train_precision must be 'bf16' or 'fp32', got {self.train_precision!r}")
+        if self.train_precision == 'fp32':
+            if settings.config_option not in ('frame2voxel', 'recon2voxel'):
+                raise NotImplementedError(f"train_precision: fp32 trains frame2voxel / recon2voxel, not {settings.config_option!r}: "
+                                          "DeepLabv3 has no fp32 backward (train-mode BatchNorm, strided and dilated convolutions)")
+            if settings.unfrozen_e2vid:
+                raise NotImplementedError("train_precision: fp32 needs the frozen E2VID front end (unfrozen_e2vid: False): E2VID "
+                                          "has no fp32 backward (5x5 stride-2 convolutions, ConvLSTM)")
+            SemSegE2VID.check_fp32_config(settings.skip_connect_task_type, False)
         super().__init__(settings, train)
 
     def backend_kwargs(self):
@@ -47,11 +60,13 @@ class SupervisedTrainer(BaseTrainer):
         self.buildModels()
         self.createOptimizerDict()
         self.task_loss = TaskLoss(losses=list(s.task_loss), gamma=2.0, num_classes=s.semseg_num_classes, ignore_index=255)
-        # One arithmetic mode (bf16 storage, fp32 accumulation) whatever use_amp says; bf16 has fp32's exponent range, so the
-        # GradScaler the reference builds under use_amp (sup_only_trainer.py:247-252) has nothing to do and is None here.
+        # The arithmetic follows train_precision (bf16 storage with fp32 accumulation, or fp32) whatever use_amp says; neither
+        # has fp16's narrow exponent range, so the GradScaler the reference builds under use_amp (sup_only_trainer.py:247-252)
+        # has nothing to do and is None here.
         self.scaler = None
         if self.amp_requested():
-            self.settings.logger.info("use_amp requested: bf16 storage / fp32 accumulation is always on; no GradScaler is built")
+            mode = "fp32" if self.train_precision == 'fp32' else "bf16 storage / fp32 accumulation"
+            self.settings.logger.info(f"use_amp requested: the step runs in {mode} (train_precision); no GradScaler is built")
 
     def buildModels(self):
         """finetune_trainer.py:104-196: `models_dict` (front_sensor_b + back_end, or model_recon) and the reconstructor."""
@@ -87,9 +102,10 @@ class SupervisedTrainer(BaseTrainer):
         if 'front_sensor_b' in self.models_dict:
             self.reconstructor = ImageReconstructor(self.front_end_sensor_b, self.input_height, self.input_width,
                                                     s.nr_temporal_bins_b, self.device, s.e2vid_config)
-            if self.eval_precision == 'fp32':
-                # validation in the reference's arithmetic: a second reconstructor over the SAME model with states and packed
-                # operands of its own, so nothing the training step reads is shared
+            if 'fp32' in (self.eval_precision, self.train_precision):
+                # the reference's arithmetic: a second reconstructor over the SAME model with states and packed operands of its
+                # own, so nothing the bf16 path reads is shared.  ONE serves fp32 validation and fp32 training: the two never run
+                # at the same time, and each sequence starts from and leaves empty states (_latents_fp32)
                 self.task_backend.check_fp32()
                 opts = SimpleNamespace(**dict(vars(s.e2vid_config), precision='fp32'))
                 self.reconstructor_fp32 = ImageReconstructor(self.front_end_sensor_b, self.input_height, self.input_width,
@@ -116,14 +132,25 @@ class SupervisedTrainer(BaseTrainer):
                                                                     need_latents=(i == s.nr_events_data_b - 1))
         return latent
 
-    def _latents_fp32(self, event):
+    def _latents_fp32(self, event, latents_only=False):
+        """fp32 latents of the last sub-window.  latents_only (the training step): the encoder-only E2VID step, same bits.
+        The encoder latents are views of the sequence's own cat(x, h) state buffers.  Every call starts from empty states, so these
+        buffers are allocated by this call, and it drops the states before it returns: the returned views are then the only
+        references, no later call can reach (let alone write) the buffers, and the caching allocator cannot hand them out again
+        while a view lives.  Within the call only earlier sub-windows are overwritten, whose latents nobody keeps."""
         s = self.settings
         rec = self.reconstructor_fp32
         rec.last_states_for_each_channel = {'grayscale': None}
         for i in range(s.nr_events_data_b):
-            _, _, latent = rec.update_reconstruction(event, channel_slice=(i * s.input_channels_b, s.input_channels_b))
+            _, _, latent = rec.update_reconstruction(event, channel_slice=(i * s.input_channels_b, s.input_channels_b),
+                                                     latents_only=latents_only)
         rec.last_states_for_each_channel = {'grayscale': None}
         return latent
+
+    def _train_latents(self, event):
+        """Detached latents of the frozen front end in the arithmetic of the training step."""
+        latent = self._latents_fp32(event, latents_only=True) if self.train_precision == 'fp32' else self._latents(event)
+        return {k: v.detach() for k, v in latent.items()}
 
     def _set_modes(self):
         s = self.settings
@@ -136,7 +163,10 @@ class SupervisedTrainer(BaseTrainer):
         """Frozen half of a step: the recurrent E2VID encoder (frozen in every fine-tune / linear-probe YAML) depends on no weight
         the optimiser touches, so BaseTrainer.trainEpoch enqueues it for batch i+1 on its own HIP stream BEFORE the trainable half
         of batch i (decoder forward / backward / AdamW, bound by HBM) and it runs under it.  Returns None when there is nothing
-        frozen to run ahead (frame2recon, unfrozen_e2vid): the step then runs whole in train_step."""
+        frozen to run ahead (frame2recon, unfrozen_e2vid): the step then runs whole in train_step.
+        train_precision fp32 takes the same route: the latents of batch i (saved by the decoder's fp32 conv backward) are views
+        of buffers that front_step(batch i + 1) cannot reach (_latents_fp32), allocated on the front stream and handed to the main
+        stream with the same event / record_stream pair; the kernels' workspaces are kept per stream (hip._workspace)."""
         s = self.settings
         if s.config_option not in ('recon2voxel', 'frame2voxel') or s.unfrozen_e2vid or not batch[0].is_cuda:
             return None
@@ -146,7 +176,7 @@ class SupervisedTrainer(BaseTrainer):
         F, main = self._front_stream, torch.cuda.current_stream(self.device)
         F.wait_stream(main)
         with torch.cuda.stream(F):
-            latent = {k: v.detach() for k, v in self._latents(batch[0]).items()}
+            latent = self._train_latents(batch[0])
             self.reconstructor.last_states_for_each_channel = {'grayscale': None}
             done = torch.cuda.Event()
             done.record(F)
@@ -166,8 +196,11 @@ class SupervisedTrainer(BaseTrainer):
                     if torch.is_tensor(v):
                         v.record_stream(main)
             else:
-                latent = {k: v.detach() for k, v in self._latents(batch[0]).items()}
-            pred, _ = self.task_backend(latent)
+                latent = self._train_latents(batch[0])
+            if self.train_precision == 'fp32':
+                pred, _ = self.task_backend.forward_fp32_train(latent)
+            else:
+                pred, _ = self.task_backend(latent)
             labels = f.interpolate(gt.float().unsqueeze(1), size=(self.input_height, self.input_width), mode='nearest').squeeze(1).long()
             loss = self.task_loss(pred[1], labels) * s.weight_task_loss
             losses['semseg_sensor_b_loss'] = loss.detach()

@@ -33,11 +33,19 @@ class BaseTrainer(object):
         self._png_pending = []                   # (slot, status tensor, file names) of device-decoded PNG maps not yet checked
         self._png_batches = 0                    # batches that queued at least one status vector since the last check
         # Precision contract (INTEGRATION.md "Precision"): the reference's `use_amp` switches torch.autocast(fp16) + GradScaler
-        # (pretrain_trainer.py:344-353).  This build has ONE numeric mode whatever the flag says: bf16 storage of activations /
-        # activation gradients / MFMA weight operands, fp32 accumulation, fp32 master weights, optimiser state and losses; no
-        # loss scaling is needed (bf16 has fp32's exponent range).  Say so once instead of silently ignoring the key.
-        msg = ("numeric mode: bf16 storage / fp32 accumulate (MFMA), fp32 master weights and losses; YAML use_amp={} is accepted "
-               "and has no effect (no fp32-activation or fp16-autocast mode in this build)".format(getattr(settings, 'use_amp', False)))
+        # (pretrain_trainer.py:344-353).  Here the flag is accepted and changes nothing: the arithmetic of the training step is bf16
+        # storage of activations / activation gradients / MFMA weight operands with fp32 accumulation, or -- stage-2/3 trainers with
+        # `train_precision: fp32` -- fp32 throughout; fp32 master weights, optimiser state and losses either way;
+        # no loss scaling is needed (bf16 has fp32's exponent range).  Say once what the run really does.
+        use_amp = getattr(settings, 'use_amp', False)
+        if getattr(self, 'train_precision', 'bf16') == 'fp32':
+            msg = ("numeric mode: train_precision fp32 -- fp32 activations, gradients and MFMA operands (f32-input MFMA), fp32 "
+                   "weights, optimiser state and losses; YAML use_amp={} is accepted and has no effect (no fp16-autocast mode, no "
+                   "GradScaler)".format(use_amp))
+        else:
+            msg = ("numeric mode: bf16 storage / fp32 accumulate (MFMA), fp32 master weights and losses; YAML use_amp={} is "
+                   "accepted and has no effect (no fp16-autocast mode; fp32 training is train_precision: fp32 of the stage-2/3 "
+                   "trainers)".format(use_amp))
         settings.logger.info(msg)
         if self.rank_hint() == 0:
             print(msg)
