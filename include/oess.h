@@ -547,6 +547,26 @@ int oess_bilinear_l2norm_pool_bwd_bf16(const void* feat, long long feat_pix_stri
                                        void* grad_in, long long gin_pix_stride, oess_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * The same node in fp32 WITHOUT a full-resolution tensor (K20): forward and backward recompute the four-corner blend of every
+ * output pixel from x, the head's fp32 NHWC conv output [B x H x W x C] (pixel stride x_pix_stride, 16-byte aligned rows),
+ * C in {64, 128, 256}, any integer scale >= 1, both align_corners modes, Ho = H * scale, Wo = W * scale.
+ *   fwd: k [S x C] and count [S] fp32 = scatter_mean(normalize(upsample(x)), ids + sample * superpixel_size); partial sums meet as
+ *        the 2^-32 fixed-point integers of oess_segment_mean_fwd (same workspace: oess_segment_mean_fwd_workspace_bytes(S, C) bytes,
+ *        same range / finiteness contract: a non-finite input makes the whole of k NaN); bit-repeatable.
+ *   bwd: grad_x [B x H x W x C] fp32 from grad_k [S x C] and count; workspace =
+ *        oess_bilinear_l2norm_pool_bwd_workspace_bytes(B, W, C, Ho, S) bytes.  Deterministic (gather form, no atomics).
+ * The index rule and eps (1 / max(|u|, eps)) are those of oess_resize_bilinear_nhwc_fwd / oess_l2norm_nhwc_fwd; only the
+ * association of the blend differs (rows first, then columns).
+ * ------------------------------------------------------------------------------------------ */
+int oess_bilinear_l2norm_pool_fwd_f32(const float* x, long long x_pix_stride, const int64_t* ids, int superpixel_size, int S, int B, int H,
+                                      int W, int C, int scale, int align_corners, float eps, float* k, float* count, void* workspace,
+                                      size_t workspace_bytes, oess_stream_t stream);
+int oess_bilinear_l2norm_pool_bwd_f32(const float* x, long long x_pix_stride, const int64_t* ids, const float* grad_k, const float* count,
+                                      int superpixel_size, int S, int B, int H, int W, int C, int scale, int align_corners, float eps,
+                                      void* workspace, size_t workspace_bytes, float* grad_x, long long gx_pix_stride,
+                                      oess_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * Superpixel mean of a bilinearly upsampled map through its pooling matrix (models/deeplabv3.py:184 F.interpolate(feats, size=
  * input, bilinear, align_corners=False) followed by training/pretrain_trainer.py:445-465 on it): k[s] = (sum_q M[s][q] y[q]) /
  * (n[s] + 1e-6) with M[s][q] = the summed bilinear weights of superpixel row s's pixels on low-resolution pixel q.

@@ -9,6 +9,7 @@
 #include <stdlib.h>
 #include "oess.h"
 #include "oess_common.h"
+#include "seg_fixed.h"
 
 namespace {
 using namespace oess;
@@ -201,16 +202,7 @@ constexpr int SEGF_IDS = 256;                     // raw ids held in LDS
 constexpr int SEGF_ROW = SEGF_CH + 1;             // u64 per table row: one pad entry rotates the banks from row to row
 constexpr int SEGF_MAX_PPW = 65536;
 constexpr size_t SEGF_LDS = (size_t)SEGF_IDS * SEGF_ROW * 8 + (size_t)SEGF_IDS * 4;
-typedef unsigned long long u64_t;
-
-__device__ __forceinline__ long long seg_to_fixed(float v) { return __float2ll_rn(v * 4294967296.0f); }
-
-__device__ __forceinline__ void seg_global_add(u64_t* __restrict__ acc_lo, u64_t* __restrict__ acc_hi, int64_t idx, long long v) {
-    if (v == 0) return;
-    atomicAdd(&acc_lo[idx], (u64_t)v & 0xffffffffull);
-    const long long hi = v >> 32;                                        // arithmetic shift: v = hi * 2^32 + lo, lo in [0, 2^32)
-    if (hi != 0) atomicAdd(&acc_hi[idx], (u64_t)hi);
-}
+// u64_t, seg_to_fixed, seg_global_add and segmean_fx_finalize_kernel: seg_fixed.h (shared with headpool_f32.hip)
 
 struct SegGeom { int64_t P, pps; int sps, Cf, S, nslice, pix_per_wg; };
 
@@ -422,22 +414,6 @@ __global__ __launch_bounds__(SEGF_THREADS) void segmean_fwd_fx_scalar_kernel(con
     if (amax >= 0x47000000u) atomicOr(err, 1);
     __syncthreads();
     seg_flush_table(g, tab, cnt, slice, id_off, acc_lo, acc_hi, gcnt, [](int ch) { return ch; });
-}
-
-// k = fp32( (hi * 2^32 + lo) * 2^-32 ) / (count + 1e-6)   (pretrain_trainer.py:462); count as the fp32 row sum the reference forms
-__global__ __launch_bounds__(THREADS) void segmean_fx_finalize_kernel(const u64_t* __restrict__ acc_lo, const u64_t* __restrict__ acc_hi,
-                                                                      const int* __restrict__ gcnt, const int* __restrict__ err,
-                                                                      float* __restrict__ k, float* __restrict__ count, int S, int Cf) {
-    const int64_t n = (int64_t)S * Cf;
-    const bool bad = *err != 0;
-    for (int64_t i = (int64_t)blockIdx.x * THREADS + threadIdx.x; i < n; i += (int64_t)gridDim.x * THREADS) {
-        const int64_t s = i / Cf;
-        const double tot = (double)(long long)acc_hi[i] * 4294967296.0 + (double)acc_lo[i];
-        const float sum = (float)(tot * (1.0 / 4294967296.0));
-        const float cn = (float)gcnt[s];
-        k[i] = bad ? __uint_as_float(0x7fc00000u) : sum / __fadd_rn(cn, 1e-6f);
-        if (i - s * Cf == 0) count[s] = cn;
-    }
 }
 
 template <bool BF16>
@@ -941,7 +917,7 @@ int oess_segment_mean_fwd(const void* feat, int is_bf16, const int64_t* ids, int
     if (vec) { if (is_bf16) OESS_SEGF(segmean_fwd_fx_kernel<true>) else OESS_SEGF(segmean_fwd_fx_kernel<false>) }
     else { if (is_bf16) OESS_SEGF(segmean_fwd_fx_scalar_kernel<true>) else OESS_SEGF(segmean_fwd_fx_scalar_kernel<false>) }
 #undef OESS_SEGF
-    hipLaunchKernelGGL(segmean_fx_finalize_kernel, dim3(stream_grid((int64_t)S * Cf, THREADS)), dim3(THREADS), 0, st, acc_lo, acc_hi,
+    hipLaunchKernelGGL(segmean_fx_finalize_kernel, dim3(stream_grid((int64_t)S * Cf, SEG_FIN_THREADS)), dim3(SEG_FIN_THREADS), 0, st, acc_lo, acc_hi,
                        gcnt, err, k, count, S, Cf);
     OESS_HIP(hipGetLastError());
     return OESS_OK;

@@ -307,9 +307,15 @@ class PointwiseFeature:
         return torch.Size((B, self.conv.weight.shape[0], H, W))
 
     def materialize(self):
+        if self.x.dtype == torch.float32:           # fp32 training (K20): the conv's fp32 autograd form, not its bf16 forward
+            return self.conv.forward_f32_train(self.x)
+        if self.x.dtype != torch.bfloat16:
+            raise ValueError(f"PointwiseFeature holds a bfloat16 or float32 map, not {self.x.dtype}")
         return self.conv(self.x)
 
     def pool(self, superpixels, superpixel_size, S=None):
+        if self.x.dtype not in (torch.float32, torch.bfloat16):
+            raise ValueError(f"PointwiseFeature holds a bfloat16 or float32 map, not {self.x.dtype}")
         k_in, cnt = superpixel_pool(self.x, superpixels, superpixel_size, S, with_count=True)
         w = self.conv.weight.flatten(1).float()                                   # Cout x Cin
         k = k_in @ w.t()
@@ -1300,12 +1306,61 @@ class _BilinearL2NormPool(torch.autograd.Function):
         return gin.permute(0, 3, 1, 2), None, None, None, None
 
 
+HEADPOOL_F32_CHANNELS = (64, 128, 256)
+
+
+class _BilinearL2NormPoolF32(torch.autograd.Function):
+    """The same node in fp32 (K20) with NO full-resolution tensor in either direction: forward and backward recompute every
+    output pixel's four-corner blend from x (oess_bilinear_l2norm_pool_fwd_f32 / _bwd_f32).  Saves x, ids and count only."""
+
+    @staticmethod
+    def forward(ctx, x, scale, ids, sps, S):
+        if x.dtype != torch.float32 or x.ndim != 4 or x.shape[1] not in HEADPOOL_F32_CHANNELS:
+            raise ValueError(f"the fp32 head-pool node takes a float32 [B, C, H, W] map with C in {HEADPOOL_F32_CHANNELS}, not "
+                             f"{x.dtype} {tuple(x.shape)}")
+        lib = _lib.load()
+        xn = _nhwc_any(x)
+        B, H, W, C = xn.shape
+        k = torch.empty((S, C), dtype=torch.float32, device=x.device)
+        cnt = torch.empty((S,), dtype=torch.float32, device=x.device)
+        ws_bytes = lib.oess_segment_mean_fwd_workspace_bytes(S, C)
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=x.device)
+        _lib.check(lib.oess_bilinear_l2norm_pool_fwd_f32(_ptr(xn), _pix_stride(xn), _ptr(ids), sps, S, B, H, W, C, scale, 1, 1e-12, _ptr(k),
+                                                         _ptr(cnt), _ptr(ws), ws_bytes, _stream()), "oess_bilinear_l2norm_pool_fwd_f32")
+        ctx.save_for_backward(xn, ids, cnt)
+        ctx.meta = (B, H, W, C, scale, sps, S)
+        ctx.mark_non_differentiable(cnt)
+        return k, cnt
+
+    @staticmethod
+    def backward(ctx, gk, _gcnt):
+        lib = _lib.load()
+        xn, ids, cnt = ctx.saved_tensors
+        B, H, W, C, scale, sps, S = ctx.meta
+        gk = gk.contiguous().float()
+        gin = torch.empty((B, H, W, C), dtype=torch.float32, device=gk.device)
+        nbytes = lib.oess_bilinear_l2norm_pool_bwd_workspace_bytes(B, W, C, H * scale, S)
+        ws = _workspace(nbytes, gk.device, tag="resize")
+        _lib.check(lib.oess_bilinear_l2norm_pool_bwd_f32(_ptr(xn), _pix_stride(xn), _ptr(ids), _ptr(gk), _ptr(cnt), sps, S, B, H, W, C, scale, 1,
+                                                         1e-12, _ptr(ws), ws.numel(), _ptr(gin), C, _stream()),
+                   "oess_bilinear_l2norm_pool_bwd_f32")
+        return gin.permute(0, 3, 1, 2), None, None, None, None
+
+
 class UpsampledNormalizedFeature:
     """DilationFeatureExtractor's output  F.normalize(nn.Upsample(x4, bilinear, align_corners=True)(x))  (models/image_model.py:
     121-143) kept as (x, scale) for a consumer that only pools it over superpixels (training/pretrain_trainer.py:445-465):
-    `pool` is the one-node form above; `materialize()` is the full-resolution tensor for anything else."""
+    `pool` is the one-node form above; `materialize()` is the full-resolution tensor for anything else.  bf16 x: the bf16 nodes;
+    fp32 x (C in HEADPOOL_F32_CHANNELS): the fp32 node / the composed fp32 chain.  Anything else raises before any launch."""
 
     def __init__(self, x, scale):
+        if x.dtype == torch.float32:
+            if x.ndim != 4 or x.shape[1] not in HEADPOOL_F32_CHANNELS:
+                raise ValueError(f"the fp32 head-pool node runs C in {HEADPOOL_F32_CHANNELS}, not a map of shape {tuple(x.shape)}")
+        elif x.dtype != torch.bfloat16:
+            raise ValueError(f"UpsampledNormalizedFeature holds a bfloat16 or float32 map, not {x.dtype}")
+        if int(scale) != scale or int(scale) < 1:
+            raise ValueError("integer scale factors >= 1 only")
         self.x, self.scale = x, int(scale)
 
     @property
@@ -1314,9 +1369,11 @@ class UpsampledNormalizedFeature:
         return torch.Size((B, C, H * self.scale, W * self.scale))
 
     def materialize(self):
+        if self.x.dtype == torch.float32:
+            return l2_normalize(bilinear_resize(self.x, scale_factor=self.scale, align_corners=True))
         return bilinear_l2norm_train(self.x, self.scale)
 
-    def pool(self, superpixels, superpixel_size, S=None):
+    def pool(self, superpixels, superpixel_size, S=None, with_count=False):
         B, C, Ho, Wo = self.shape
         _need_gpu(self.x, superpixels)
         if tuple(superpixels.shape) != (B, Ho, Wo):
@@ -1325,6 +1382,11 @@ class UpsampledNormalizedFeature:
             off = torch.arange(0, B * superpixel_size, superpixel_size, device=superpixels.device)[:, None, None]
             S = int((superpixels + off).max().item()) + 1
         ids = superpixels.reshape(-1).contiguous().to(torch.int64)
+        if self.x.dtype == torch.float32:
+            k, cnt = _BilinearL2NormPoolF32.apply(self.x, self.scale, ids, int(superpixel_size), int(S))
+            return (k, cnt) if with_count else k
+        if with_count:
+            raise ValueError("with_count is a form of the fp32 node")
         return _BilinearL2NormPool.apply(self.x, self.scale, ids, int(superpixel_size), int(S))
 
 

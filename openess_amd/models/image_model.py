@@ -39,6 +39,7 @@ class DilationFeatureExtractor(nn.Module):
         # True: the differentiable path returns hip.UpsampledNormalizedFeature (x, 4) for a consumer that only pools the features
         # over superpixels (PretrainStep with the contrastive loss); its .materialize() is the tensor this module returns otherwise
         self.lazy_features = False
+        self._pw32_head_train = engine.PackedWeightF32()     # operands of head_fp32_train, per version of the head's parameters
 
     def forward(self, x):
         return self.head(self.encode(x))
@@ -87,3 +88,16 @@ class DilationFeatureExtractor(nn.Module):
         x = conv_f32(self.decoder[0], x)
         x = hip.bilinear_resize(x, scale_factor=4, align_corners=True)
         return hip.l2_normalize(x) if self.normalize_feature else x
+
+    def head_fp32_train(self, x):
+        """The trainable head under autograd in fp32 (K20): hip.conv2d_f32_train on decoder[0], then -- with lazy_features --
+        hip.UpsampledNormalizedFeature(x, 4), whose pool() is the fused fp32 head-pool node (no full-resolution tensor), or
+        without it the materialised fp32 chain bilinear_resize -> l2_normalize.  x: the fp32 output of encode_fp32."""
+        if x.dtype != torch.float32:
+            raise ValueError("head_fp32_train takes the float32 output of encode_fp32")
+        conv = self.decoder[0]
+        x = hip.conv2d_f32_train(x, conv.weight, conv.bias, conv.stride[0], conv.padding[0], conv.dilation[0], pw=self._pw32_head_train)
+        if self.normalize_feature:
+            feat = hip.UpsampledNormalizedFeature(x, 4)
+            return feat if self.lazy_features else feat.materialize()
+        return hip.bilinear_resize(x, scale_factor=4, align_corners=True)

@@ -209,18 +209,19 @@ class SemSegE2VID(nn.Module):
         return out, x_ch256
 
     @staticmethod
-    def check_fp32_config(skip_type='concat', materialize_ch256=True):
+    def check_fp32_config(skip_type='concat', materialize_ch256=True, train=False):
         """check_fp32's refusals that follow from the constructor arguments alone, for a caller that must refuse before it
-        builds anything (the trainers' train_precision: fp32)."""
+        builds anything (the trainers' train_precision: fp32).  train=True: the rules of forward_fp32_train, which has the
+        'pooled' form (the fp32 hip.PointwiseFeature); inference has no consumer for it."""
         if skip_type != 'concat':
             raise NotImplementedError(f"forward_fp32 runs skip_type='concat' (every shipped config), not {skip_type!r}")
-        if materialize_ch256 == 'pooled':
+        if materialize_ch256 == 'pooled' and not train:
             raise NotImplementedError("forward_fp32 has no 'pooled' form of x_ch256 (a pre-training option of the bf16 path)")
 
-    def check_fp32(self):
+    def check_fp32(self, train=False):
         """The configurations forward_fp32 runs: skip_type 'concat' (with 'sum' the reference's own channel counts do not fit:
         ReLUINSConv2d(256, ...) would receive 128 channels), no dropout in an INSResBlock; raises otherwise, before any launch."""
-        self.check_fp32_config(self.skip_type, self.materialize_ch256)
+        self.check_fp32_config(self.skip_type, self.materialize_ch256, train=train)
         for m in self.modules():
             if isinstance(m, nn.Dropout) and m.p > 0:
                 raise NotImplementedError("forward_fp32 has no dropout (INSResBlock(dropout > 0))")
@@ -270,8 +271,9 @@ class SemSegE2VID(nn.Module):
         parameters (and text_embeddings when it is a parameter) receive fp32 gradients; latents that need no gradient (the frozen
         encoder's) get none computed.  The head is conv2d_f32_train on the operator of _composed_head(), composed in fp32 by
         autograd (forward_fp32 composes it in float64 and rounds once: the logits agree within the fp32 bound, not bit for bit).
-        With if_linear_probing the frozen decoder runs under no_grad and only hip.linear_probe trains."""
-        self.check_fp32()
+        With if_linear_probing the frozen decoder runs under no_grad and only hip.linear_probe trains.
+        materialize_ch256='pooled' returns x_ch256 as the fp32 hip.PointwiseFeature."""
+        self.check_fp32(train=True)
         for k in (1, 2, 4, 8):
             if input_dict[k].dtype != torch.float32:
                 raise ValueError("forward_fp32_train takes the fp32 latents of the fp32 E2VID path")
@@ -292,7 +294,10 @@ class SemSegE2VID(nn.Module):
             self.update_skip_dict(out, x, sz_in)
             x = hip.upsample2x_concat_f32_train(x)
             x = self.decoder_scale_4[0].forward_f32_train(x)
-            x_ch256 = self.decoder_ch256[0].forward_f32_train(x) if self.materialize_ch256 else None
+            if self.materialize_ch256 == 'pooled':      # pre-training (K20): the superpixel mean commutes with the 1x1 conv
+                x_ch256 = hip.PointwiseFeature(x, self.decoder_ch256[0])
+            else:
+                x_ch256 = self.decoder_ch256[0].forward_f32_train(x) if self.materialize_ch256 else None
             wf, bf = self._composed_head()
             ver = tuple(p._version for p in (self.decoder_ch256[0].weight, self.decoder_ch256[0].bias,
                                              self.decoder_ch512[0].weight, self.decoder_ch512[0].bias, self.text_embeddings))

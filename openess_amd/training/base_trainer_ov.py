@@ -34,8 +34,9 @@ class BaseTrainer(object):
         self._png_batches = 0                    # batches that queued at least one status vector since the last check
         # Precision contract (INTEGRATION.md "Precision"): the reference's `use_amp` switches torch.autocast(fp16) + GradScaler
         # (pretrain_trainer.py:344-353).  Here the flag is accepted and changes nothing: the arithmetic of the training step is bf16
-        # storage of activations / activation gradients / MFMA weight operands with fp32 accumulation, or -- stage-2/3 trainers with
-        # `train_precision: fp32` -- fp32 throughout; fp32 master weights, optimiser state and losses either way;
+        # storage of activations / activation gradients / MFMA weight operands with fp32 accumulation, or -- with
+        # `train_precision: fp32` (DESIGN.md K19 stage 2/3, K20 frame2voxel pre-training) -- fp32 throughout; fp32 master weights,
+        # optimiser state and losses either way;
         # no loss scaling is needed (bf16 has fp32's exponent range).  Say once what the run really does.
         use_amp = getattr(settings, 'use_amp', False)
         if getattr(self, 'train_precision', 'bf16') == 'fp32':
@@ -44,8 +45,7 @@ class BaseTrainer(object):
                    "GradScaler)".format(use_amp))
         else:
             msg = ("numeric mode: bf16 storage / fp32 accumulate (MFMA), fp32 master weights and losses; YAML use_amp={} is "
-                   "accepted and has no effect (no fp16-autocast mode; fp32 training is train_precision: fp32 of the stage-2/3 "
-                   "trainers)".format(use_amp))
+                   "accepted and has no effect (no fp16-autocast mode; fp32 training is train_precision: fp32)".format(use_amp))
         settings.logger.info(msg)
         if self.rank_hint() == 0:
             print(msg)

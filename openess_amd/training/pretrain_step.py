@@ -5,6 +5,7 @@ smoke() and the trainer classes; it owns the models_dict / optimizers_dict with 
 """
 import contextlib
 import math
+from types import SimpleNamespace
 
 import torch
 
@@ -50,7 +51,22 @@ class PretrainStep:
     def __init__(self, config_option='frame2voxel', num_classes=11, img_size=(440, 640), nr_events_data=20,
                  nr_temporal_bins=5, if_spatial_contrastive=False, if_dense_clip_supervision=True, superpixel_size=100,
                  lr=5e-4, weight_task_loss=1.0, task_loss=('dice', 'cross_entropy'), output_stride=32, device='cuda',
-                 e2vid_config=None, text_embeddings=None, seed=1205, online_teacher=None, wavefront=False):
+                 e2vid_config=None, text_embeddings=None, seed=1205, online_teacher=None, wavefront=False, precision='bf16'):
+        # precision: arithmetic of the whole step.  'bf16' (default) builds and runs exactly the bf16 step.  'fp32'
+        # is the reference's arithmetic (use_amp: False in every YAML); what it cannot run is refused here, before any model is built
+        if precision not in ('bf16', 'fp32'):
+            raise ValueError(f"precision must be 'bf16' or 'fp32', got {precision!r}")
+        if precision == 'fp32':
+            if config_option != 'frame2voxel':
+                raise NotImplementedError(f"precision='fp32' pre-trains frame2voxel, not {config_option!r}: DeepLabv3 has no fp32 "
+                                          "backward (train-mode BatchNorm, strided and dilated convolutions)")
+            if online_teacher is not None:
+                raise NotImplementedError("precision='fp32' has no online teacher: the MaskCLIP ViT has no fp32 form")
+            if wavefront:
+                raise NotImplementedError("precision='fp32' has no wavefront schedule: fp32 E2VID runs on one stream "
+                                          "(the per-level streams are a bf16-path option)")
+            SemSegE2VID.check_fp32_config('concat', 'pooled', train=True)
+        self.precision = precision
         self.config_option = config_option
         # a frozen MaskCLIP tower as ONLINE teacher: pseudo-labels = argmax of its logits on the frame, computed inside
         # the step, instead of the offline `pl_*_rgb` PNGs (README.md:295).  None = the reference's behaviour (labels from the batch).
@@ -100,6 +116,12 @@ class PretrainStep:
             if wavefront and self.device.type == 'cuda':
                 from ..e2vid.wavefront import EncoderWavefront
                 self.wavefront = EncoderWavefront(self.device, self.front_end_sensor_b.num_encoders)
+            if precision == 'fp32':
+                # a second reconstructor over the SAME frozen model with fp32 states and packed operands of its own (as the
+                # stage-2/3 trainers keep one, _supervised.buildModels): nothing the bf16 path reads is shared
+                self.task_backend.check_fp32(train=True)
+                self.reconstructor_fp32 = ImageReconstructor(self.front_end_sensor_b, self.input_height, self.input_width,
+                                                             nr_temporal_bins, self.device, SimpleNamespace(precision='fp32'))
         self.task_loss = TaskLoss(losses=list(task_loss), gamma=2.0, num_classes=num_classes, ignore_index=255)
         self.nce_loss = NCELoss(temperature=0.07)
         # createOptimizerDict (pretrain_trainer.py:225-259)
@@ -145,7 +167,13 @@ class PretrainStep:
         with ctx(T if cuda else None):
             # the teacher head is trained by the contrastive loss: then it belongs to the back half; otherwise nothing can reach it
             # and the whole forward runs here without autograd bookkeeping (the reference runs it too, pretrain_trainer.py:434,484)
-            if self.if_spatial_contrastive:
+            if self.precision == 'fp32':
+                # encode_fp32 / forward_fp32 are no_grad; train-mode BatchNorm moves the running statistics one step as encode does
+                if self.if_spatial_contrastive or not self.run_unused_teacher_head:
+                    h.teacher_enc = self.model_frame.encode_fp32(frame.float())
+                else:
+                    h.teacher_out = self.model_frame.forward_fp32(frame.float())
+            elif self.if_spatial_contrastive:
                 h.teacher_enc = self.model_frame.encode(frame)
             elif self.run_unused_teacher_head:
                 with torch.no_grad():
@@ -158,24 +186,38 @@ class PretrainStep:
         if self.config_option == 'frame2voxel':
             event = batch[0]
             with ctx(F if cuda else None):
-                wf = getattr(self, 'wavefront', None)
-                if wf is not None:
-                    wf.begin()
-                self.reconstructor.last_states_for_each_channel = {'grayscale': None}
-                for i in range(self.nr_events_data):
-                    _, _, latent_real = self.reconstructor.update_reconstruction(
-                        event, channel_slice=(i * self.bins, self.bins), wavefront=wf,
-                        need_latents=(i == self.nr_events_data - 1))      # only the last sub-window's latents are used (:437-441)
-                if wf is not None:
-                    wf.end(*latent_real.values())
-                self.reconstructor.last_states_for_each_channel = {'grayscale': None}    # the sequence ends with the step
-                h.content = {k: v.detach() for k, v in latent_real.items()}              # trainTaskStepPretrain (:550-562)
+                if self.precision == 'fp32':
+                    h.content = self._latents_fp32(event)
+                else:
+                    wf = getattr(self, 'wavefront', None)
+                    if wf is not None:
+                        wf.begin()
+                    self.reconstructor.last_states_for_each_channel = {'grayscale': None}
+                    for i in range(self.nr_events_data):
+                        _, _, latent_real = self.reconstructor.update_reconstruction(
+                            event, channel_slice=(i * self.bins, self.bins), wavefront=wf,
+                            need_latents=(i == self.nr_events_data - 1))      # only the last sub-window's latents are used (:437-441)
+                    if wf is not None:
+                        wf.end(*latent_real.values())
+                    self.reconstructor.last_states_for_each_channel = {'grayscale': None}    # the sequence ends with the step
+                    h.content = {k: v.detach() for k, v in latent_real.items()}              # trainTaskStepPretrain (:550-562)
         if cuda:
             h.streams = (F, T)
             h.done = (torch.cuda.Event(), torch.cuda.Event())
             h.done[0].record(F)
             h.done[1].record(T)
         return h
+
+    def _latents_fp32(self, event):
+        """Detached fp32 latents of the last sub-window from the encoder-only fp32 E2VID step.  They are views of the sequence's
+        own cat(x, h) state buffers: every call starts from empty states, so it allocates them, and it drops the states before it
+        returns -- the views saved by the decoder's conv backward of batch i cannot be reached by front(batch i + 1)."""
+        rec = self.reconstructor_fp32
+        rec.last_states_for_each_channel = {'grayscale': None}
+        for i in range(self.nr_events_data):
+            _, _, latent = rec.update_reconstruction(event, channel_slice=(i * self.bins, self.bins), latents_only=True)
+        rec.last_states_for_each_channel = {'grayscale': None}
+        return {k: v.detach() for k, v in latent.items()}
 
     def _join_front(self, h):
         """The current stream continues after the front half; tensors allocated on the front streams are handed to it."""
@@ -218,10 +260,13 @@ class PretrainStep:
         self._join_front(h)
         if h.online_pl is not None:
             batch = (*batch[:3], h.online_pl, *batch[4:])
-        feat_frame = self.model_frame.head(h.teacher_enc) if self.if_spatial_contrastive else h.teacher_out
+        if self.precision == 'fp32':
+            feat_frame = self.model_frame.head_fp32_train(h.teacher_enc) if self.if_spatial_contrastive else h.teacher_out
+        else:
+            feat_frame = self.model_frame.head(h.teacher_enc) if self.if_spatial_contrastive else h.teacher_out
         if self.config_option == 'frame2voxel':
             pl = batch[3]
-            pred, feat_voxel = self.task_backend(h.content)
+            pred, feat_voxel = self.task_backend.forward_fp32_train(h.content) if self.precision == 'fp32' else self.task_backend(h.content)
             loss_dense = self.task_loss(pred[1], pl) * self.weight_task_loss
             losses['dense_clip_loss'] = loss_dense.detach()
             if self.if_spatial_contrastive:

@@ -7,6 +7,26 @@ from .pretrain_step import PretrainStep
 
 
 class OpenESSPretrainModel(BaseTrainer):
+    def __init__(self, settings, train=True):
+        # `train_precision` (optional YAML key, clip block): arithmetic of the pre-training step.  Set before
+        # BaseTrainer.__init__ logs the numeric mode; what fp32 cannot pre-train is refused here, before anything is built
+        # (the same refusals as PretrainStep's constructor, which the online teacher's construction would otherwise precede).
+        # val_step stays bf16: eval_precision is not wired for this trainer.
+        self.train_precision = getattr(settings, 'train_precision', 'bf16')
+        if self.train_precision not in ('bf16', 'fp32'):
+            raise ValueError(f"train_precision must be 'bf16' or 'fp32', got {self.train_precision!r}")
+        if self.train_precision == 'fp32':
+            if settings.config_option != 'frame2voxel':
+                raise NotImplementedError(f"train_precision: fp32 pre-trains frame2voxel, not {settings.config_option!r}: DeepLabv3 "
+                                          "has no fp32 backward (train-mode BatchNorm, strided and dilated convolutions)")
+            if getattr(settings, 'pl_sources', '') == 'online_maskclip':
+                raise NotImplementedError("train_precision: fp32 has no online teacher (pl_sources: online_maskclip): the MaskCLIP "
+                                          "ViT has no fp32 form")
+            if getattr(settings, 'unfrozen_e2vid', False):
+                raise NotImplementedError("train_precision: fp32 needs the frozen E2VID front end (unfrozen_e2vid: False): E2VID "
+                                          "has no fp32 backward (5x5 stride-2 convolutions, ConvLSTM)")
+        super().__init__(settings, train)
+
     def init_fn(self):
         """pretrain_trainer.py:87-89: models, then optimisers, then the loss objects."""
         self.buildModels()
@@ -32,7 +52,8 @@ class OpenESSPretrainModel(BaseTrainer):
                                  if_spatial_contrastive=s.if_spatial_contrastive,
                                  if_dense_clip_supervision=s.if_dense_clip_supervision, superpixel_size=s.superpixel_size,
                                  lr=s.lr_voxel, weight_task_loss=s.weight_task_loss, task_loss=tuple(s.task_loss),
-                                 output_stride=s.output_stride, device=self.device, text_embeddings=text)
+                                 output_stride=s.output_stride, device=self.device, text_embeddings=text,
+                                 precision=self.train_precision)
         self.models_dict = self.step.models_dict
         self.reconstructor = getattr(self.step, 'reconstructor', None)
 
