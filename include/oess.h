@@ -786,6 +786,63 @@ int oess_instance_norm_bwd_f32(const oess_f32_view_t* x, const oess_f32_view_t* 
                                int W, int C, int relu, const oess_f32_view_t* dx, void* ws, size_t ws_bytes, oess_stream_t stream);
 int oess_downsample_sum2x_f32(const oess_f32_view_t* dout, int B, int H, int W, int C, const oess_f32_view_t* dx, oess_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------
+ * K21 fp32 ResNet-50 training: the backward half of the fp32 layer set of the dilated backbone (models/_resnet.py of the
+ * reference: strided and dilated convolutions, train-mode BatchNorm2d, the stem's max pool).  The data gradient of a stride-1
+ * dilated convolution is oess_conv2d_dilated_fwd_f32 itself on the operand of hip.pack_conv_weight_f32_dgrad with
+ * pad' = dilation (R - 1) - pad; these are the kernels that were missing.  Additions only: the ABI version stays.  Nothing here
+ * uses an atomic: every result repeats bit for bit, on any device.
+ *
+ * oess_conv2d_dilated_wgrad_f32: oess_conv2d_wgrad_f32 with a stride, a dilation and free padding: dw[co][ci][r][s] = sum over
+ *   (b, oy, ox) of dy[b, oy, ox, co] * x[b, oy stride - pad + r dilation, ox stride - pad + s dilation, ci] (zero outside the
+ *   map); db (nullable) [Cout] = sum of dy.  x: B x H x W x Cin view, dy: B x Ho x Wo x Cout view, Ho and Wo by the formula of
+ *   oess_conv2d_dilated_fwd_f32.  Geometry: R == S in {1, 3, 7}, stride 1 or 2, dilation >= 1 with (R - 1) dilation <= 127, any
+ *   pad >= 0 that leaves Ho, Wo >= 1; anything else is OESS_EINVAL and a workspace of 0.  The same kernel, reduced over the
+ *   OUTPUT pixels; the ranges and ws (n (R S Cin Cout + Cout) floats) follow B Ho Wo.  A tap that reaches the map from no output
+ *   pixel (dilation 12 on a 3 x 4 map: all but the centre) is written as exact zeros without a K loop.  At stride 1, dilation 1,
+ *   R in {1, 3} and pad == (R - 1) / 2 result and workspace size are bit-identical to oess_conv2d_wgrad_f32.
+ *   R == 7 with Cin % 4 != 0 (the stem, Cin = 3) folds the taps into the GEMM's M: row tap Cin + ci, ceil(49 Cin / 128) tiles
+ *   instead of 49, and the split follows that tile count.
+ * oess_conv2d_dgrad_s2_f32: data gradient of a stride-2, dilation-1 convolution, R == S in {1, 3}, 0 <= pad < R: dx (B x H x W x
+ *   Cin view) from dy (B x Ho x Wo x Cout view, Ho = (H + 2 pad - R) / 2 + 1), as four stride-1 phase sub-convolutions of dy in
+ *   ONE launch of the forward kernel: input pixel (2 qy + py, 2 qx + px) gathers the taps r == py + pad, s == px + pad (mod 2)
+ *   from dy[qy + (py + pad - r) / 2][qx + (px + pad - s) / 2].  Every element of dx is written exactly once; a pixel no window
+ *   reads (the odd rows and columns of a 1 x 1 conv, a last row or column beyond the last window) gets 0.0.
+ *   w_packed (hip.pack_conv_weight_f32_dgrad_s2): oess_conv2d_dgrad_s2_f32_packed_floats(Cout, Cin, R) floats, 16-byte aligned:
+ *   four blocks, one per tap parity class c = 2 ry + rx in this order, class (ry, rx) holding the taps r = ry + 2 ty,
+ *   s = rx + 2 tx (ny = (R - ry + 1) / 2, nx = (R - rx + 1) / 2 of them; none for R == 1 outside class 0); each block is
+ *   [ceil16(ny nx Cout)][ceil32(Cin)], row (ty nx + tx) Cout + co, column ci = weight[co][ci][ry + 2 ty][rx + 2 tx], zeros in
+ *   the padding.  The layout does not depend on pad: phase (py, px) reads class ((py + pad) & 1, (px + pad) & 1).
+ * oess_batch_norm_bwd_f32: backward of out = act((x - mean) gamma rstd + beta [+ residual]), rstd = 1 / sqrt(var + eps).  With
+ *   xh = (x - mean) rstd and g = dy [out > 0] (relu) or dy:  dbeta = sum g, dgamma = sum g xh,
+ *   dx = gamma rstd (g - mean_P(g) - xh mean_P(g xh)), dres = g.  x (the forward's INPUT), out (the forward's OUTPUT, read only
+ *   with relu: the mask is the forward's bit for bit), dy, dx, dres: B x H x W x C views; mean, var: what
+ *   oess_batch_norm_train_fwd_f32 saved (batch mean, biased variance); gamma nullable (1).  dx, dgamma, dbeta, dres are each
+ *   nullable and nothing not asked for is computed or stored; dres is written only with relu (without, it is dy).  dx may be dy
+ *   itself.  Two launches: per-range sums of g and g xh (a thread's own two-level sums, no accumulator longer than 64 terms
+ *   until B H W exceeds 4096 pixels per thread; then a fixed LDS tree), then the ranges in a fixed order and the apply pass.
+ *   16-byte accesses as for the forward (mean, var, gamma 16-byte aligned too).
+ *   ws: oess_batch_norm_bwd_f32_workspace_bytes(B, H, W, C) bytes, 16-byte aligned (0 for an impossible geometry).
+ * oess_maxpool3x3s2_bwd_f32: backward of nn.MaxPool2d(3, 2, 1) in gather form: every pixel of dx (B x H x W x C view) recomputes,
+ *   from x, the winner of each of the up to four windows that contain it (ATen's scan: row-major, a value wins when it is
+ *   greater than the running maximum or is a NaN; padding never wins) and adds the dy (B x Ho x Wo x C view) of the windows it
+ *   won, window rows first.  Every element of dx is written once.
+ * ------------------------------------------------------------------------------------------ */
+size_t oess_conv2d_dilated_wgrad_f32_workspace_bytes(int B, int H, int W, int Cin, int Cout, int R, int S, int stride, int pad,
+                                                     int dilation);
+int oess_conv2d_dilated_wgrad_f32(const oess_f32_view_t* x, const oess_f32_view_t* dy, int B, int H, int W, int Cin, int Cout, int R,
+                                  int S, int stride, int pad, int dilation, float* dw, float* db, void* ws, size_t ws_bytes,
+                                  oess_stream_t stream);
+size_t oess_conv2d_dgrad_s2_f32_packed_floats(int Cout, int Cin, int R);   /* 0 for an impossible geometry */
+int oess_conv2d_dgrad_s2_f32(const oess_f32_view_t* dy, int B, int H, int W, int Cin, const float* w_packed, int Cout, int R, int S,
+                             int pad, const oess_f32_view_t* dx, oess_stream_t stream);
+size_t oess_batch_norm_bwd_f32_workspace_bytes(int B, int H, int W, int C);
+int oess_batch_norm_bwd_f32(const oess_f32_view_t* x, const oess_f32_view_t* out, const oess_f32_view_t* dy, int B, int H, int W, int C,
+                            const float* mean, const float* var, float eps, const float* gamma, int relu, const oess_f32_view_t* dx,
+                            float* dgamma, float* dbeta, const oess_f32_view_t* dres, void* ws, size_t ws_bytes, oess_stream_t stream);
+int oess_maxpool3x3s2_bwd_f32(const oess_f32_view_t* x, const oess_f32_view_t* dy, int B, int H, int W, int C, const oess_f32_view_t* dx,
+                              oess_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -182,6 +182,15 @@ SIGNATURES = {
     "oess_instance_norm_bwd_f32_workspace_bytes": (c_sz, [c_int, c_int, c_int, c_int]),
     "oess_instance_norm_bwd_f32": (c_int, [c_view, c_view, c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, c_view, c_vp, c_sz, c_vp]),
     "oess_downsample_sum2x_f32": (c_int, [c_view, c_int, c_int, c_int, c_int, c_view, c_vp]),
+    "oess_conv2d_dilated_wgrad_f32_workspace_bytes": (c_sz, [c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int]),
+    "oess_conv2d_dilated_wgrad_f32": (c_int, [c_view, c_view, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_vp,
+                                              c_vp, c_vp, c_sz, c_vp]),
+    "oess_conv2d_dgrad_s2_f32_packed_floats": (c_sz, [c_int, c_int, c_int]),
+    "oess_conv2d_dgrad_s2_f32": (c_int, [c_view, c_int, c_int, c_int, c_int, c_vp, c_int, c_int, c_int, c_int, c_view, c_vp]),
+    "oess_batch_norm_bwd_f32_workspace_bytes": (c_sz, [c_int, c_int, c_int, c_int]),
+    "oess_batch_norm_bwd_f32": (c_int, [c_view, c_view, c_view, c_int, c_int, c_int, c_int, c_vp, c_vp, c_f, c_vp, c_int, c_view, c_vp,
+                                        c_vp, c_view, c_vp, c_sz, c_vp]),
+    "oess_maxpool3x3s2_bwd_f32": (c_int, [c_view, c_view, c_int, c_int, c_int, c_int, c_view, c_vp]),
 }
 
 _lib = None

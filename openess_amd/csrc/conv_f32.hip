@@ -8,6 +8,8 @@
 //                       (output parity py, px; 3 / 2 taps per axis), input row = q + 1 - t, output row = 2 q + py;
 //   upsample conv:      the operand loader reads the bilinear x2 (align_corners=False) map of its input on the fly.
 //   dilated conv (K16): tap (r, s) at (r d, s d); 7 x 7 taps for the ResNet stem; a workgroup skips the taps it cannot reach.
+//   stride-2 dgrad (K21): the data gradient of a stride-2 conv as four stride-1 phase sub-convolutions of dY (input parity py,
+//                       px; the taps of matching parity), output row = 2 q + py; a phase without taps writes zeros.
 // A second input may be summed on load (skip_sum); the epilogue adds bias, an optional residual, then ReLU or sigmoid.
 //
 // Tiling: 256 threads = 4 waves; a wave owns 64 pixels x 32 output channels (two 32 x 32 accumulators, 16 registers each);
@@ -43,6 +45,7 @@ struct Params {
     int Hl, Wl;                      // logical input extent seen by the taps
     int Hq, Wq;                      // GEMM grid of one phase: M = B * Hq * Wq
     int stride, off_y, off_x, ostride;
+    int oh, ow;                      // output extent: a phase pixel beyond it is not written (odd maps under ostride 2)
     int skip;                        // dilated convs: a workgroup walks only the taps that reach the map from one of its pixels
     const float* w;
     int CoutP;
@@ -268,6 +271,7 @@ __global__ __launch_bounds__(NT) void conv_f32_kernel(const Params P) {
             const int qy = (int)(t % P.Hq);
             const int b = (int)(t / P.Hq);
             const int oy = qy * P.ostride + ph.py, ox = qx * P.ostride + ph.px;
+            if (oy >= P.oh || ox >= P.ow) continue;
             float v = (s ? acc1[r] : acc0[r]) + bias;
             if (P.has_res) v = v + P.res.p[b * P.res.sb + oy * P.res.sy + ox * P.res.sx + n * P.res.sc];
             if (P.act == 1) v = v > 0.f ? v : 0.f;
@@ -376,6 +380,7 @@ int oess_conv2d_dilated_fwd_f32(const oess_f32_view_t* in, const oess_f32_view_t
     P.up = upsample2x;
     P.Hl = Hl; P.Wl = Wl; P.Hq = Ho; P.Wq = Wo;
     P.stride = stride; P.off_y = -pad; P.off_x = -pad; P.ostride = 1;
+    P.oh = Ho; P.ow = Wo;
     P.skip = dilation > 1;
     P.w = w_packed; P.CoutP = ceil_to(Cout, 32); P.bias = bias; P.Cout = Cout; P.act = act;
     P.has_res = residual != nullptr;
@@ -406,6 +411,7 @@ int oess_conv_transpose2d_fwd_f32(const oess_f32_view_t* in, const oess_f32_view
     P.up = 0;
     P.Hl = H; P.Wl = W; P.Hq = H; P.Wq = W;
     P.stride = 1; P.off_y = 1; P.off_x = 1; P.ostride = 2;
+    P.oh = 2 * H; P.ow = 2 * W;
     P.w = w_packed; P.CoutP = ceil_to(Cout, 32); P.bias = bias; P.Cout = Cout; P.act = act;
     P.has_res = 0;
     set_output(P, out);
@@ -418,6 +424,51 @@ int oess_conv_transpose2d_fwd_f32(const oess_f32_view_t* in, const oess_f32_view
         for (int ty = 0; ty < ny; ++ty)
             for (int tx = 0; tx < nx; ++tx) { ph.dy[ty * nx + tx] = (signed char)-ty; ph.dx[ty * nx + tx] = (signed char)-tx; }
         off += (long long)ph.kp * P.CoutP;
+    }
+    return launch(P, 4, (hipStream_t)stream);
+}
+
+size_t oess_conv2d_dgrad_s2_f32_packed_floats(int Cout, int Cin, int R) {
+    if (Cout < 1 || Cin < 1 || (R != 1 && R != 3)) return 0;
+    size_t rows = 0;
+    for (int c = 0; c < 4; ++c) rows += ceil_to(((R - (c >> 1) + 1) / 2) * ((R - (c & 1) + 1) / 2) * Cout, BK);
+    return rows * ceil_to(Cin, 32);
+}
+
+int oess_conv2d_dgrad_s2_f32(const oess_f32_view_t* dy, int B, int H, int W, int Cin, const float* w_packed, int Cout, int R, int S,
+                             int pad, const oess_f32_view_t* dx, oess_stream_t stream) {
+    if (!view_ok(dy) || !view_ok(dx) || !weights_ok(w_packed, nullptr)) return OESS_EINVAL;
+    if (B < 1 || H < 1 || W < 1 || Cin < 1 || Cout < 1 || (long long)B * H * W * Cin >= (1LL << 40)) return OESS_EINVAL;
+    if (R != S || (R != 1 && R != 3) || pad < 0 || pad >= R || H + 2 * pad < R || W + 2 * pad < R) return OESS_EINVAL;
+    const int Ho = (H + 2 * pad - R) / 2 + 1, Wo = (W + 2 * pad - R) / 2 + 1;
+    if ((long long)B * Ho * Wo * Cout >= (1LL << 40)) return OESS_EINVAL;
+    Params P{};
+    set_inputs(P, dy, nullptr, B, Ho, Wo, Cout);
+    P.up = 0;
+    P.Hl = Ho; P.Wl = Wo; P.Hq = (H + 1) / 2; P.Wq = (W + 1) / 2;
+    P.stride = 1; P.off_y = 0; P.off_x = 0; P.ostride = 2;
+    P.oh = H; P.ow = W;
+    P.w = w_packed; P.CoutP = ceil_to(Cin, 32); P.bias = nullptr; P.Cout = Cin; P.act = 0;
+    P.has_res = 0;
+    set_output(P, dx);
+    // the packed blocks, by tap parity class c = 2 ry + rx: taps r = ry + 2 ty, s = rx + 2 tx
+    long long off[4], o = 0;
+    for (int c = 0; c < 4; ++c) {
+        off[c] = o;
+        o += (long long)ceil_to(((R - (c >> 1) + 1) / 2) * ((R - (c & 1) + 1) / 2) * Cout, BK) * P.CoutP;
+    }
+    for (int p = 0; p < 4; ++p) {
+        Phase& ph = P.ph[p];
+        ph.py = p >> 1; ph.px = p & 1;
+        // input row 2 q + py is read by tap r of window oy when 2 oy - pad + r == 2 q + py: r of the parity of py + pad
+        const int ry = (ph.py + pad) & 1, rx = (ph.px + pad) & 1;
+        const int ny = (R - ry + 1) / 2, nx = (R - rx + 1) / 2;
+        ph.ntap = ny * nx; ph.w_off = off[2 * ry + rx]; ph.kp = ceil_to(ny * nx * Cout, BK);
+        for (int ty = 0; ty < ny; ++ty)
+            for (int tx = 0; tx < nx; ++tx) {
+                ph.dy[ty * nx + tx] = (signed char)((ph.py + pad - ry) / 2 - ty);
+                ph.dx[ty * nx + tx] = (signed char)((ph.px + pad - rx) / 2 - tx);
+            }
     }
     return launch(P, 4, (hipStream_t)stream);
 }

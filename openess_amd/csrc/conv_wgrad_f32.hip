@@ -1,9 +1,13 @@
-// K18 fp32 SemSegE2VID training: weight and bias gradient of a stride-1 convolution on the f32-input MFMA of gfx950
-// (v_mfma_f32_32x32x2_f32).
+// K18 fp32 SemSegE2VID training, K21 fp32 ResNet-50 training: weight and bias gradient of a convolution on the f32-input MFMA
+// of gfx950 (v_mfma_f32_32x32x2_f32).
 //
-//   dW[co][ci][r][s] = sum over (b, oy, ox) of dY[b, oy, ox, co] * X[b, oy - pad + r, ox - pad + s, ci],   db[co] = sum of dY
-// as one GEMM per tap, D[ci][co] reduced over the output pixels: with NHWC operands both LDS tiles are [k = pixel][channel], the
+//   dW[co][ci][r][s] = sum over (b, oy, ox) of dY[b, oy, ox, co] * X[b, oy stride - pad + r dilation, ox stride - pad + s dilation, ci]
+//   db[co] = sum of dY
+// as one GEMM per tap, D[ci][co] reduced over the OUTPUT pixels: with NHWC operands both LDS tiles are [k = pixel][channel], the
 // k-major layout conv_f32_kernel feeds its MFMAs from (no transpose); a tap that leaves the map is a row of zeros.
+// oess_conv2d_wgrad_f32 (K18) is the stride-1, dilation-1, "same"-pad form; oess_conv2d_dilated_wgrad_f32 (K21) takes stride 1 or
+// 2, any dilation and pad and the 7 x 7 stem, and leaves out the K loop of a tap that reaches the map from no output pixel at all
+// (dilation 12 on a 3 x 4 map: eight of nine taps): such a tile is exact zeros.  The 7 x 7 stem folds its taps into M (folds()).
 //
 // Tiling: 256 threads = 4 waves in 2 x 2; a wave owns (32 NACC) input channels x 32 output channels (NACC 32 x 32 accumulators);
 // block tile BM x 64 with BM = 64 or 128 input channels; K steps of 16 pixels staged through LDS, the next step's global loads
@@ -34,7 +38,10 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 struct Params {
     View x, dy;
     int B, H, W, Cin, Cout, R, pad;
-    int P;                               // B * H * W
+    int Ho, Wo, stride, dil;             // dy is B x Ho x Wo x Cout
+    unsigned long long tap_mask;         // bit (r R + s): the tap reaches the map from some output pixel
+    int fold;                            // element path only: the taps are folded into M, row m = tap Cin + ci (the 7 x 7 stem)
+    int P;                               // B * Ho * Wo
     int range_pix, nsplit;
     int ntile_n;                         // output-channel tiles; blockIdx.y = tap * ntile_n + tile
     int want_db;
@@ -67,16 +74,26 @@ __global__ __launch_bounds__(NT) void conv_wgrad_f32_kernel(const Params P) {
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int wm = wave & 1, wn = wave >> 1;
-    const int tap = blockIdx.y / P.ntile_n;
+    const bool fold = !VEC && P.fold;
+    const int tap = blockIdx.y / P.ntile_n;                   // fold: 0, the rows of a tile carry their own taps
     const int m0 = blockIdx.x * BM, n0 = (blockIdx.y - tap * P.ntile_n) * BN;
-    const int dy_tap = tap / P.R - P.pad, dx_tap = tap % P.R - P.pad;
     const int p0 = blockIdx.z * P.range_pix, p1 = min(p0 + P.range_pix, P.P);
-    const int nstep = (p1 - p0 + BK - 1) / BK;
     const bool do_db = P.want_db && blockIdx.x == 0 && tap == 0;
+    // a tap no output pixel reaches the map through: zeros without a K loop (the db workgroup still walks dy)
+    const int nstep = ((P.tap_mask >> tap) & 1ull) || do_db || fold ? (p1 - p0 + BK - 1) / BK : 0;
 
     const int acol = tid % AQ, arow = tid / AQ, bcol = tid % BQ, brow = tid / BQ;
-    const int ac = m0 + acol * (VEC ? 4 : 1), bc = n0 + bcol * (VEC ? 4 : 1);
-    const bool a_on = ac < P.Cin, b_on = bc < P.Cout;
+    int ac = m0 + acol * (VEC ? 4 : 1);
+    const int bc = n0 + bcol * (VEC ? 4 : 1);
+    int my_tap = tap;
+    bool a_on = ac < P.Cin;
+    if (fold) {                                               // this thread's column of the A tile: row tap Cin + ci of dW
+        a_on = ac < P.R * P.R * P.Cin;
+        my_tap = a_on ? ac / P.Cin : 0;
+        ac -= my_tap * P.Cin;
+    }
+    const bool b_on = bc < P.Cout;
+    const int dy_tap = (my_tap / P.R) * P.dil - P.pad, dx_tap = (my_tap % P.R) * P.dil - P.pad;
 
     float ra[VEC ? NA * 4 : NA], rb[VEC ? NB * 4 : NB];
 
@@ -88,8 +105,8 @@ __global__ __launch_bounds__(NT) void conv_wgrad_f32_kernel(const Params P) {
             bool ok = a_on && p < p1;
             long long off = 0;
             if (ok) {
-                const Pix q = pix_of(p, P.H, P.W);
-                const int y = q.y + dy_tap, x = q.x + dx_tap;
+                const Pix q = pix_of(p, P.Ho, P.Wo);
+                const int y = q.y * P.stride + dy_tap, x = q.x * P.stride + dx_tap;
                 ok = y >= 0 && y < P.H && x >= 0 && x < P.W;
                 off = q.b * P.x.sb + y * P.x.sy + x * P.x.sx + ac * P.x.sc;
             }
@@ -107,7 +124,7 @@ __global__ __launch_bounds__(NT) void conv_wgrad_f32_kernel(const Params P) {
             const bool ok = b_on && p < p1;
             long long off = 0;
             if (ok) {
-                const Pix q = pix_of(p, P.H, P.W);
+                const Pix q = pix_of(p, P.Ho, P.Wo);
                 off = q.b * P.dy.sb + q.y * P.dy.sy + q.x * P.dy.sx + bc * P.dy.sc;
             }
             if (VEC) {
@@ -178,12 +195,13 @@ __global__ __launch_bounds__(NT) void conv_wgrad_f32_kernel(const Params P) {
     const int n = n0 + wn * 32 + l31;
     if (n >= P.Cout) return;
     float* o = P.part + ((long long)blockIdx.z * K + (long long)tap * P.Cin) * P.Cout + n;
+    const int rows = fold ? (int)K : P.Cin;                   // fold: row m of the tile is row m of [R R Cin][Cout]
 #pragma unroll
     for (int s = 0; s < NACC; ++s) {
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
             const int ci = m0 + wm * 32 * NACC + s * 32 + (r & 3) + 8 * (r >> 2) + 4 * lk;
-            if (ci < P.Cin) o[(long long)ci * P.Cout] = acc[s][r];
+            if (ci < rows) o[(long long)ci * P.Cout] = acc[s][r];
         }
     }
 }
@@ -209,18 +227,41 @@ __global__ __launch_bounds__(NT) void conv_wgrad_f32_reduce_kernel(const float* 
     }
 }
 
-bool wgrad_geometry_ok(int B, int H, int W, int Cin, int Cout, int R, int S, int stride, int pad, int dilation) {
+// Ho, Wo of the forward (oess_conv2d_dilated_fwd_f32's formula); false when there is no output
+bool out_extent(int H, int W, int R, int stride, int pad, int dilation, int& Ho, int& Wo) {
+    const long long ny = (long long)H + 2LL * pad - (long long)dilation * (R - 1) - 1, nx = (long long)W + 2LL * pad - (long long)dilation * (R - 1) - 1;
+    if (ny < 0 || nx < 0) return false;
+    Ho = (int)(ny / stride) + 1;
+    Wo = (int)(nx / stride) + 1;
+    return true;
+}
+
+// K21 geometry: R == S in {1, 3, 7}, stride 1 or 2, dilation >= 1 with (R - 1) dilation <= 127, pad >= 0, Ho, Wo >= 1
+bool dilated_geometry_ok(int B, int H, int W, int Cin, int Cout, int R, int S, int stride, int pad, int dilation) {
     if (!geometry_ok(B, H, W, Cin) || Cout < 1 || Cout > (1 << 20)) return false;
-    if ((long long)B * H * W >= (1LL << 31) - MAX_RANGE_PIX) return false;
-    if (R != S || (R != 1 && R != 3) || stride != 1 || dilation != 1 || 2 * pad != R - 1) return false;
+    if (R != S || (R != 1 && R != 3 && R != 7) || (stride != 1 && stride != 2)) return false;
+    if (pad < 0 || pad > (1 << 20) || dilation < 1 || (long long)(R - 1) * dilation > 127) return false;
+    int Ho, Wo;
+    if (!out_extent(H, W, R, stride, pad, dilation, Ho, Wo) || !geometry_ok(B, Ho, Wo, Cout)) return false;
+    if ((long long)B * Ho * Wo >= (1LL << 31) - MAX_RANGE_PIX) return false;
     return (long long)R * S * Cin * Cout < (1LL << 31);
 }
 
-// the split of the pixel range: a function of the shapes alone
-void split_of(int B, int H, int W, int Cin, int Cout, int R, int& nsplit, int& range_pix) {
-    const long long P = (long long)B * H * W;
-    const int BM = Cin > 64 ? 128 : 64;
-    const long long tiles = (long long)R * R * ((Cin + BM - 1) / BM) * ((Cout + BN - 1) / BN);
+// K18 geometry: the stride-1, "same"-pad subset of the above (Ho == H, Wo == W)
+bool wgrad_geometry_ok(int B, int H, int W, int Cin, int Cout, int R, int S, int stride, int pad, int dilation) {
+    if (R != S || (R != 1 && R != 3) || stride != 1 || dilation != 1 || 2 * pad != R - 1) return false;
+    return dilated_geometry_ok(B, H, W, Cin, Cout, R, S, stride, pad, dilation);
+}
+
+// the split of the OUTPUT pixel range: a function of the shapes alone
+// The 7 x 7 stem (Cin = 3): one tap per tile would run 49 tiles of 64 rows with 3 rows of data each and read dy 49 times; its
+// taps are folded into M instead (147 rows = two tiles of 128).  Cin % 4 != 0 is always the element path: a function of the shapes.
+bool folds(int Cin, int R) { return R == 7 && Cin % 4 != 0 && Cin < 64; }
+
+void split_of(int B, int Ho, int Wo, int Cin, int Cout, int R, int& nsplit, int& range_pix) {
+    const long long P = (long long)B * Ho * Wo;
+    const int M = folds(Cin, R) ? R * R * Cin : Cin, BM = M > 64 ? 128 : 64;
+    const long long tiles = (long long)(folds(Cin, R) ? 1 : R * R) * ((M + BM - 1) / BM) * ((Cout + BN - 1) / BN);
     long long n = (TARGET_WG + tiles - 1) / tiles;
     const long long by_size = (P + MIN_RANGE_PIX - 1) / MIN_RANGE_PIX, by_chain = (P + MAX_RANGE_PIX - 1) / MAX_RANGE_PIX;
     n = n < by_size ? n : by_size;
@@ -232,37 +273,51 @@ void split_of(int B, int H, int W, int Cin, int Cout, int R, int& nsplit, int& r
     nsplit = (int)((P + rp - 1) / rp);
 }
 
-}  // namespace
-
-extern "C" {
-
-size_t oess_conv2d_wgrad_f32_workspace_bytes(int B, int H, int W, int Cin, int Cout, int R, int S, int stride, int pad, int dilation) {
-    if (!wgrad_geometry_ok(B, H, W, Cin, Cout, R, S, stride, pad, dilation)) return 0;
-    int nsplit, range_pix;
-    split_of(B, H, W, Cin, Cout, R, nsplit, range_pix);
-    return (size_t)nsplit * ((size_t)R * S * Cin * Cout + Cout) * sizeof(float);
+// does tap offset t (= r dilation - pad) reach [0, n) from some output index in [0, no)?
+bool tap_reaches(int t, int n, int no, int stride) {
+    const int lo = t >= 0 ? 0 : (-t + stride - 1) / stride;
+    if (n - 1 - t < 0) return false;
+    const int hi = (n - 1 - t) / stride < no - 1 ? (n - 1 - t) / stride : no - 1;
+    return lo <= hi;
 }
 
-int oess_conv2d_wgrad_f32(const oess_f32_view_t* x, const oess_f32_view_t* dy, int B, int H, int W, int Cin, int Cout, int R, int S,
-                          int stride, int pad, int dilation, float* dw, float* db, void* ws, size_t ws_bytes, oess_stream_t stream) {
-    if (!view_ok(x) || !view_ok(dy) || !dw || !ws || ((uintptr_t)ws & 15) != 0) return OESS_EINVAL;
-    if (!wgrad_geometry_ok(B, H, W, Cin, Cout, R, S, stride, pad, dilation)) return OESS_EINVAL;
-    if (ws_bytes < oess_conv2d_wgrad_f32_workspace_bytes(B, H, W, Cin, Cout, R, S, stride, pad, dilation)) return OESS_ENOMEM;
+size_t workspace_bytes(int B, int H, int W, int Cin, int Cout, int R, int stride, int pad, int dilation) {
+    int Ho, Wo, nsplit, range_pix;
+    out_extent(H, W, R, stride, pad, dilation, Ho, Wo);
+    split_of(B, Ho, Wo, Cin, Cout, R, nsplit, range_pix);
+    return (size_t)nsplit * ((size_t)R * R * Cin * Cout + Cout) * sizeof(float);
+}
+
+// geometry already checked.  skip_taps: leave out the K loop of the taps that read nothing but padding
+int run(const oess_f32_view_t* x, const oess_f32_view_t* dy, int B, int H, int W, int Cin, int Cout, int R, int stride, int pad,
+        int dilation, bool skip_taps, float* dw, float* db, void* ws, oess_stream_t stream) {
     Params P{};
     P.x = to_view(x);
     P.dy = to_view(dy);
     P.B = B; P.H = H; P.W = W; P.Cin = Cin; P.Cout = Cout; P.R = R; P.pad = pad;
-    P.P = B * H * W;
-    split_of(B, H, W, Cin, Cout, R, P.nsplit, P.range_pix);
+    P.stride = stride; P.dil = dilation;
+    out_extent(H, W, R, stride, pad, dilation, P.Ho, P.Wo);
+    P.P = B * P.Ho * P.Wo;
+    P.tap_mask = ~0ull;
+    if (skip_taps) {
+        P.tap_mask = 0ull;
+        for (int r = 0; r < R; ++r)
+            for (int s = 0; s < R; ++s)
+                if (tap_reaches(r * dilation - pad, H, P.Ho, stride) && tap_reaches(s * dilation - pad, W, P.Wo, stride))
+                    P.tap_mask |= 1ull << (r * R + s);
+    }
+    split_of(B, P.Ho, P.Wo, Cin, Cout, R, P.nsplit, P.range_pix);
     P.ntile_n = (Cout + BN - 1) / BN;
     P.want_db = db != nullptr;
     P.part = (float*)ws;
-    const bool big = Cin > 64;
+    P.fold = folds(Cin, R);
+    const int M = P.fold ? R * R * Cin : Cin;
+    const bool big = M > 64;
     const int BM = big ? 128 : 64;
-    const long long gy = (long long)R * S * P.ntile_n;
-    if (gy > 65535 || (Cin + BM - 1) / BM > 65535) return OESS_EINVAL;
+    const long long gy = (long long)(P.fold ? 1 : R * R) * P.ntile_n;
+    if (gy > 65535 || (M + BM - 1) / BM > 65535) return OESS_EINVAL;
     const bool vec = Cin % 4 == 0 && Cout % 4 == 0 && vec_ok(x) && vec_ok(dy);
-    const dim3 grid((unsigned)((Cin + BM - 1) / BM), (unsigned)gy, (unsigned)P.nsplit);
+    const dim3 grid((unsigned)((M + BM - 1) / BM), (unsigned)gy, (unsigned)P.nsplit);
     hipStream_t st = (hipStream_t)stream;
     if (big) {
         if (vec) hipLaunchKernelGGL((conv_wgrad_f32_kernel<2, true>), grid, dim3(NT), 0, st, P);
@@ -272,11 +327,43 @@ int oess_conv2d_wgrad_f32(const oess_f32_view_t* x, const oess_f32_view_t* dy, i
         else hipLaunchKernelGGL((conv_wgrad_f32_kernel<1, false>), grid, dim3(NT), 0, st, P);
     }
     OESS_HIP(hipGetLastError());
-    const long long total = (long long)R * S * Cin * Cout + Cout;
+    const long long total = (long long)R * R * Cin * Cout + Cout;
     hipLaunchKernelGGL(conv_wgrad_f32_reduce_kernel, dim3((unsigned)((total + NT - 1) / NT)), dim3(NT), 0, st, (const float*)ws, P.nsplit,
-                       Cin, Cout, R * S, dw, db);
+                       Cin, Cout, R * R, dw, db);
     OESS_HIP(hipGetLastError());
     return OESS_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+size_t oess_conv2d_wgrad_f32_workspace_bytes(int B, int H, int W, int Cin, int Cout, int R, int S, int stride, int pad, int dilation) {
+    if (!wgrad_geometry_ok(B, H, W, Cin, Cout, R, S, stride, pad, dilation)) return 0;
+    return workspace_bytes(B, H, W, Cin, Cout, R, stride, pad, dilation);
+}
+
+int oess_conv2d_wgrad_f32(const oess_f32_view_t* x, const oess_f32_view_t* dy, int B, int H, int W, int Cin, int Cout, int R, int S,
+                          int stride, int pad, int dilation, float* dw, float* db, void* ws, size_t ws_bytes, oess_stream_t stream) {
+    if (!view_ok(x) || !view_ok(dy) || !dw || !ws || ((uintptr_t)ws & 15) != 0) return OESS_EINVAL;
+    if (!wgrad_geometry_ok(B, H, W, Cin, Cout, R, S, stride, pad, dilation)) return OESS_EINVAL;
+    if (ws_bytes < workspace_bytes(B, H, W, Cin, Cout, R, stride, pad, dilation)) return OESS_ENOMEM;
+    return run(x, dy, B, H, W, Cin, Cout, R, stride, pad, dilation, false, dw, db, ws, stream);
+}
+
+size_t oess_conv2d_dilated_wgrad_f32_workspace_bytes(int B, int H, int W, int Cin, int Cout, int R, int S, int stride, int pad,
+                                                     int dilation) {
+    if (!dilated_geometry_ok(B, H, W, Cin, Cout, R, S, stride, pad, dilation)) return 0;
+    return workspace_bytes(B, H, W, Cin, Cout, R, stride, pad, dilation);
+}
+
+int oess_conv2d_dilated_wgrad_f32(const oess_f32_view_t* x, const oess_f32_view_t* dy, int B, int H, int W, int Cin, int Cout, int R,
+                                  int S, int stride, int pad, int dilation, float* dw, float* db, void* ws, size_t ws_bytes,
+                                  oess_stream_t stream) {
+    if (!view_ok(x) || !view_ok(dy) || !dw || !ws || ((uintptr_t)ws & 15) != 0) return OESS_EINVAL;
+    if (!dilated_geometry_ok(B, H, W, Cin, Cout, R, S, stride, pad, dilation)) return OESS_EINVAL;
+    if (ws_bytes < workspace_bytes(B, H, W, Cin, Cout, R, stride, pad, dilation)) return OESS_ENOMEM;
+    return run(x, dy, B, H, W, Cin, Cout, R, stride, pad, dilation, true, dw, db, ws, stream);
 }
 
 }  // extern "C"

@@ -230,6 +230,7 @@ class PackedWeightF32:
                 self._w = weight.detach()
                 self.packed = hip.pack_conv_weight_f32(self._w)
                 self.packed_dgrad = None
+                self.packed_dgrad_s2 = None
                 self.bias = None if bias is None else bias.detach().contiguous()
             self.key = key
         return self
@@ -238,6 +239,12 @@ class PackedWeightF32:
         if self.packed_dgrad is None:
             self.packed_dgrad = hip.pack_conv_weight_f32_dgrad(self._w)
         return self.packed_dgrad
+
+    def dgrad_s2(self):
+        """The stride-2 data-gradient operand (K21), packed on first use of a weight version."""
+        if self.packed_dgrad_s2 is None:
+            self.packed_dgrad_s2 = hip.pack_conv_weight_f32_dgrad_s2(self._w)
+        return self.packed_dgrad_s2
 
     def get_composed(self, params, make):
         """Operand of a weight that is a function of several parameters (SemSegE2VID's composed head): `make()` returns the

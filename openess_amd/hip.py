@@ -2409,3 +2409,247 @@ def upsample2x_concat_f32_train(x, skip=None):
         raise ValueError("upsample2x_concat_f32_train takes 4-D fp32 tensors (the bf16 training path is hip.upsample2x_concat)")
     _need_gpu(x, skip)
     return _UpsampleConcatF32Train.apply(x, skip)
+
+
+# ------------------------------------------------------------------------------------------ K21: fp32 ResNet-50 training
+def pack_conv_weight_f32_dgrad_s2(w):
+    """Conv2d weight [Cout, Cin, R, R] (R in {1, 3}) -> the operand of oess_conv2d_dgrad_s2_f32 (include/oess.h): four blocks, one
+    per tap parity class c = 2 ry + rx holding the taps r = ry + 2 ty, s = rx + 2 tx; block [ceil16(ny nx Cout)][ceil32(Cin)], row
+    (ty nx + tx) Cout + co, column ci = w[co][ci][r][s].  The layout does not depend on the padding.  Needs no library."""
+    Co, Ci, R, S = w.shape
+    if R != S or R not in (1, 3):
+        raise ValueError(f"pack_conv_weight_f32_dgrad_s2 takes 1 x 1 and 3 x 3 kernels, not {R} x {S}")
+    Cp = (Ci + 31) // 32 * 32
+    wf = w.detach().float()
+    blocks = []
+    for c in range(4):
+        sub = wf[:, :, (c >> 1)::2, (c & 1)::2]                       # [Cout, Cin, ny, nx]
+        n = sub.shape[2] * sub.shape[3] * Co
+        blk = torch.zeros(((n + 15) // 16 * 16, Cp), dtype=torch.float32, device=w.device)
+        if n:
+            blk[:n, :Ci] = sub.permute(2, 3, 0, 1).reshape(n, Ci)
+        blocks.append(blk)
+    return torch.cat(blocks, 0).reshape(-1)
+
+
+def _conv_out_hw(H, W, R, stride, pad, dilation):
+    return (H + 2 * pad - dilation * (R - 1) - 1) // stride + 1, (W + 2 * pad - dilation * (R - 1) - 1) // stride + 1
+
+
+def _dilated_geometry_check(what, R, stride, pad, dilation, H, W):
+    if R not in (1, 3, 7) or stride not in (1, 2) or dilation < 1 or (R - 1) * dilation > 127 or pad < 0:
+        raise ValueError(f"{what} runs 1 x 1, 3 x 3 and 7 x 7 taps, stride 1 or 2, dilation >= 1 with (R - 1) dilation <= 127, not "
+                         f"{R} x {R}, stride {stride}, dilation {dilation}, pad {pad}")
+    if min(H, W) + 2 * pad < dilation * (R - 1) + 1:
+        raise ValueError(f"{what}: no output for a {H} x {W} map, {R} x {R} taps, pad {pad}, dilation {dilation}")
+
+
+def conv2d_dilated_wgrad_f32(x, dy, R, stride, pad, dilation, want_db=True):
+    """Weight and bias gradient of y = conv(x, w, stride, pad, dilation) + b in fp32 on the f32-input MFMA
+    (oess_conv2d_dilated_wgrad_f32): (dw [Cout, Cin, R, R], db [Cout] or None).  x [B, Cin, H, W], dy [B, Cout, Ho, Wo]: fp32
+    tensors with any strides, read where they lie.  R in {1, 3, 7}, stride 1 or 2, any dilation and padding.  At stride 1,
+    dilation 1 and 'same' padding the bits are conv2d_wgrad_f32's.  Fixed summation order: bit-repeatable."""
+    for name, t in (("x", x), ("dy", dy)):
+        if t.dtype != torch.float32 or t.ndim != 4:
+            raise ValueError(f"conv2d_dilated_wgrad_f32: {name} must be a 4-D fp32 tensor [B, C, H, W]")
+    B, Cin, H, W = x.shape
+    _dilated_geometry_check("conv2d_dilated_wgrad_f32", R, stride, pad, dilation, H, W)
+    Cout = dy.shape[1]
+    if (dy.shape[0], dy.shape[2], dy.shape[3]) != (B,) + _conv_out_hw(H, W, R, stride, pad, dilation):
+        raise ValueError(f"conv2d_dilated_wgrad_f32: dy {tuple(dy.shape)} is not the output of x {tuple(x.shape)} under {R} x {R}, "
+                         f"stride {stride}, pad {pad}, dilation {dilation}")
+    _need_gpu(x, dy)
+    lib = _lib.load()
+    need = lib.oess_conv2d_dilated_wgrad_f32_workspace_bytes(B, H, W, Cin, Cout, R, R, stride, pad, dilation)
+    if need == 0:
+        raise ValueError(f"conv2d_dilated_wgrad_f32: no kernel for x {tuple(x.shape)}, dy {tuple(dy.shape)}, {R} x {R}")
+    ws = _workspace(need, x.device, tag="wgrad_f32")
+    dw = torch.empty((Cout, Cin, R, R), dtype=torch.float32, device=x.device)
+    db = torch.empty((Cout,), dtype=torch.float32, device=x.device) if want_db else None
+    vx, vg = _f32_view(x, "x"), _f32_view(dy, "dy")
+    _lib.check(lib.oess_conv2d_dilated_wgrad_f32(ctypes.byref(vx), ctypes.byref(vg), B, H, W, Cin, Cout, R, R, stride, pad, dilation,
+                                                 _ptr(dw), _ptr(db), _ptr(ws), ws.numel(), _stream()), "oess_conv2d_dilated_wgrad_f32")
+    return dw, db
+
+
+def conv2d_dgrad_s2_f32(dy, packed, Cin, H, W, R, pad, out=None):
+    """Data gradient [B, Cin, H, W] of a stride-2, dilation-1 R x R convolution (R in {1, 3}, pad < R) from dy [B, Cout, Ho, Wo]
+    in fp32 (oess_conv2d_dgrad_s2_f32): four phase sub-convolutions of dy in one launch; every element is written once, a pixel no
+    window reads gets 0.0.  `packed` from pack_conv_weight_f32_dgrad_s2.  Returns out (channels_last if new)."""
+    lib = _lib.load()
+    if dy.dtype != torch.float32 or dy.ndim != 4:
+        raise ValueError("conv2d_dgrad_s2_f32: dy must be a 4-D fp32 tensor [B, Cout, Ho, Wo]")
+    B, Cout, Ho, Wo = dy.shape
+    if R not in (1, 3) or not 0 <= pad < R or min(H, W) + 2 * pad < R or (Ho, Wo) != _conv_out_hw(H, W, R, 2, pad, 1):
+        raise ValueError(f"conv2d_dgrad_s2_f32: dy {tuple(dy.shape)} is not the output of a {H} x {W} map under {R} x {R}, stride 2, "
+                         f"pad {pad}")
+    _need_gpu(dy, packed, out)
+    need = lib.oess_conv2d_dgrad_s2_f32_packed_floats(Cout, Cin, R)
+    if packed.dtype != torch.float32 or not packed.is_contiguous() or need == 0 or packed.numel() < need:
+        raise ValueError(f"packed weight must be a contiguous fp32 tensor of at least {need} floats")
+    out = _f32_out(out, B, Cin, H, W, dy.device)
+    vg, vo = _f32_view(dy, "dy"), _f32_view(out, "out")
+    _lib.check(lib.oess_conv2d_dgrad_s2_f32(ctypes.byref(vg), B, H, W, Cin, _ptr(packed), Cout, R, R, pad, ctypes.byref(vo), _stream()),
+               "oess_conv2d_dgrad_s2_f32")
+    _bump(out)
+    return out
+
+
+class _Conv2dDilatedF32Train(torch.autograd.Function):
+    """conv(x, weight, stride, pad, dilation) + bias in fp32: forward hip.conv2d_f32, backward oess_conv2d_dilated_wgrad_f32 and,
+    when x needs a gradient, oess_conv2d_dgrad_s2_f32 (stride 2) or the dilated forward on the rotated, transposed weight."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, stride, pad, dilation, pw, ver):
+        Cout, _, R, _ = weight.shape
+        op = pw.get_train(weight, bias, ver)
+        y = conv2d_f32(x, op.packed, op.bias, Cout, R, R, stride, pad, dilation=dilation)
+        ctx.save_for_backward(x, weight)
+        ctx.meta = (stride, pad, dilation, op, op.key, bias is not None)
+        return y
+
+    @staticmethod
+    def backward(ctx, gy):
+        x, weight = ctx.saved_tensors
+        stride, pad, dilation, op, key, has_bias = ctx.meta
+        Cout, Cin, R, _ = weight.shape
+        if gy.dtype != torch.float32:
+            gy = gy.float()
+        gx = gw = gb = None
+        need_gb = has_bias and ctx.needs_input_grad[2]
+        if ctx.needs_input_grad[1] or need_gb:
+            gw, gb = conv2d_dilated_wgrad_f32(x, gy, R, stride, pad, dilation, want_db=need_gb)
+            if not ctx.needs_input_grad[1]:
+                gw = None
+        if ctx.needs_input_grad[0]:
+            same = op.key == key                     # a holder that moved on since the forward is not this node's
+            if stride == 2:
+                wd = op.dgrad_s2() if same else pack_conv_weight_f32_dgrad_s2(weight)
+                gx = conv2d_dgrad_s2_f32(gy, wd, Cin, x.shape[2], x.shape[3], R, pad)
+            else:
+                wd = op.dgrad() if same else pack_conv_weight_f32_dgrad(weight)
+                gx = conv2d_f32(gy, wd, None, Cin, R, R, 1, dilation * (R - 1) - pad, dilation=dilation)
+        return gx, gw, gb, None, None, None, None, None
+
+
+def conv2d_dilated_f32_train(x, weight, bias=None, stride=1, pad=0, dilation=1, pw=None, ver=None):
+    """Differentiable fp32 convolution for training the dilated ResNet (K21): hip.conv2d_f32(..., dilation=) of x with the
+    PARAMETER tensors weight [Cout, Cin, R, R] (R in {1, 3, 7}) and bias, stride 1 or 2, any padding and dilation.  Backward: the
+    weight / bias gradient on oess_conv2d_dilated_wgrad_f32; the data gradient, only when x needs one, on oess_conv2d_dgrad_s2_f32
+    (stride 2) or on the dilated forward with the operand of pack_conv_weight_f32_dgrad and pad' = dilation (R - 1) - pad
+    (stride 1).  Stride 2 with dilation > 1, and the data gradient of a 7 x 7 kernel (the stem reads the image), do not occur in
+    ResNet-50 and are refused.  pw: an engine.PackedWeightF32 that keeps the packed operands per weight version.  fp32 in, fp32
+    out; everything else raises before any launch."""
+    if x.dtype != torch.float32 or weight.dtype != torch.float32 or (bias is not None and bias.dtype != torch.float32):
+        raise ValueError("conv2d_dilated_f32_train takes fp32 tensors (the bf16 training path is engine.conv2d_train)")
+    if x.ndim != 4 or weight.ndim != 4 or weight.shape[2] != weight.shape[3] or weight.shape[1] != x.shape[1]:
+        raise ValueError(f"conv2d_dilated_f32_train: x {tuple(x.shape)} does not fit a weight {tuple(weight.shape)}")
+    R = weight.shape[2]
+    _dilated_geometry_check("conv2d_dilated_f32_train", R, stride, pad, dilation, x.shape[2], x.shape[3])
+    if stride == 2 and dilation != 1:
+        raise ValueError("conv2d_dilated_f32_train: stride 2 together with dilation > 1 is not built (no layer of ResNet-50 has it)")
+    if x.requires_grad and torch.is_grad_enabled():
+        if R == 7:
+            raise ValueError("conv2d_dilated_f32_train: the data gradient of a 7 x 7 kernel is not built (the stem reads the image)")
+        if (stride == 2 and pad >= R) or (stride == 1 and pad > dilation * (R - 1)):
+            raise ValueError(f"conv2d_dilated_f32_train: no data gradient for pad {pad} with {R} x {R} taps, stride {stride}, "
+                             f"dilation {dilation}")
+    _need_gpu(x, weight, bias)
+    if pw is None:
+        from . import engine as _engine
+        pw = _engine.PackedWeightF32()
+    return _Conv2dDilatedF32Train.apply(x, weight, bias, stride, pad, dilation, pw, ver)
+
+
+class _BatchNormF32Train(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, gamma, beta, residual, bn, relu, eps):
+        out, mean, var = batch_norm_train_f32(x, bn, relu=relu, residual=residual, return_stats=True)
+        ctx.save_for_backward(x, out if relu else None, mean, var, gamma)
+        ctx.relu, ctx.eps, ctx.has_res = relu, eps, residual is not None
+        ctx.has_beta = beta is not None
+        return out
+
+    @staticmethod
+    def backward(ctx, gy):
+        lib = _lib.load()
+        x, out, mean, var, gamma = ctx.saved_tensors
+        B, C, H, W = x.shape
+        if gy.dtype != torch.float32:
+            gy = gy.float()
+        need_dx = ctx.needs_input_grad[0]
+        need_dg = gamma is not None and ctx.needs_input_grad[1]
+        need_db = ctx.has_beta and ctx.needs_input_grad[2]
+        need_dr = ctx.has_res and ctx.needs_input_grad[3]
+        dx = _f32_out(None, B, C, H, W, x.device) if need_dx else None
+        dgb = torch.empty((2, C), dtype=torch.float32, device=x.device) if need_dg or need_db else None
+        dres = None
+        if need_dr:
+            dres = _f32_out(None, B, C, H, W, x.device) if ctx.relu else gy      # without a ReLU: the incoming gradient itself
+        if need_dx or dgb is not None or (need_dr and ctx.relu):
+            vx, vg = _f32_view(x, "x"), _f32_view(gy, "dy")
+            vo = _f32_view(out, "out") if ctx.relu else None
+            vd = None if dx is None else _f32_view(dx, "dx")
+            vr = _f32_view(dres, "dres") if need_dr and ctx.relu else None
+            need = lib.oess_batch_norm_bwd_f32_workspace_bytes(B, H, W, C)
+            ws = _workspace(need, x.device, tag="batchnorm_bwd_f32")
+            _lib.check(lib.oess_batch_norm_bwd_f32(ctypes.byref(vx), _f32_ref(vo), ctypes.byref(vg), B, H, W, C, _ptr(mean), _ptr(var),
+                                                   ctx.eps, _ptr(None if gamma is None else gamma.detach()), int(ctx.relu), _f32_ref(vd),
+                                                   _ptr(dgb[1]) if need_dg else None, _ptr(dgb[0]) if need_db else None, _f32_ref(vr),
+                                                   _ptr(ws), ws.numel(), _stream()), "oess_batch_norm_bwd_f32")
+        return dx, (dgb[1] if need_dg else None), (dgb[0] if need_db else None), dres, None, None, None
+
+
+def batch_norm_f32_train(x, bn, relu=False, residual=None):
+    """Differentiable train-mode nn.BatchNorm2d [+ residual] [+ ReLU] in fp32 (K21), not in place: the forward is
+    batch_norm_train_f32's kernels and bits (batch statistics, the running statistics moved one momentum step, the batch counted
+    once) and keeps x, the output (the ReLU mask) and the batch mean and variance for oess_batch_norm_bwd_f32, which gives dx,
+    dgamma, dbeta and the residual's gradient, each only when asked for (frozen gamma / beta still give dx).  bn: an
+    nn.BatchNorm2d in train mode, or batch_norm_train_f32's dict.  An eval-mode BatchNorm folds into its conv: conv_bn_f32."""
+    if x.dtype != torch.float32 or x.ndim != 4 or (residual is not None and residual.dtype != torch.float32):
+        raise ValueError("batch_norm_f32_train takes 4-D fp32 tensors (the bf16 training path is hip.batch_norm_train)")
+    if isinstance(bn, dict):
+        gamma, beta, eps, momentum = bn.get('weight'), bn.get('bias'), bn.get('eps', 1e-5), bn.get('momentum', 0.1)
+    else:
+        if not bn.training:
+            raise NotImplementedError("batch_norm_f32_train is the batch-statistics form: an eval-mode BatchNorm folds into its "
+                                      "convolution (models._resnet.conv_bn_f32)")
+        gamma, beta, eps, momentum = bn.weight, bn.bias, bn.eps, bn.momentum
+    if momentum is None:
+        raise NotImplementedError("batch_norm_f32_train: momentum=None (cumulative moving average) is not built")
+    for name, t in (('weight', gamma), ('bias', beta)):
+        if t is not None and t.dtype != torch.float32:
+            raise ValueError(f"batch_norm_f32_train: {name} must be fp32")
+    if residual is not None and tuple(residual.shape) != tuple(x.shape):
+        raise ValueError(f"residual shape {tuple(residual.shape)} != {tuple(x.shape)}")
+    _need_gpu(x, residual, gamma, beta)
+    return _BatchNormF32Train.apply(x, gamma, beta, residual, bn, bool(relu), float(eps))
+
+
+class _MaxPool3x3s2F32Train(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x):
+        ctx.save_for_backward(x)
+        return max_pool_3x3s2_f32(x)
+
+    @staticmethod
+    def backward(ctx, g):
+        x, = ctx.saved_tensors
+        B, C, H, W = x.shape
+        if g.dtype != torch.float32:
+            g = g.float()
+        dx = _f32_out(None, B, C, H, W, x.device)
+        vx, vg, vd = _f32_view(x, "x"), _f32_view(g, "dy"), _f32_view(dx, "dx")
+        _lib.check(_lib.load().oess_maxpool3x3s2_bwd_f32(ctypes.byref(vx), ctypes.byref(vg), B, H, W, C, ctypes.byref(vd), _stream()),
+                   "oess_maxpool3x3s2_bwd_f32")
+        return dx
+
+
+def max_pool_3x3s2_f32_train(x):
+    """Differentiable max_pool_3x3s2_f32 (K21): the backward recomputes each window's winner from x with ATen's rule (first
+    maximum in scan order, a NaN wins) and gathers, per input pixel, the gradient of the windows it won
+    (oess_maxpool3x3s2_bwd_f32): no index map is kept, every element of the gradient is written once."""
+    if x.dtype != torch.float32 or x.ndim != 4:
+        raise ValueError("max_pool_3x3s2_f32_train takes a 4-D fp32 tensor (the bf16 training path is hip.max_pool_3x3s2)")
+    _need_gpu(x)
+    return _MaxPool3x3s2F32Train.apply(x)

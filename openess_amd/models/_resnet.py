@@ -17,6 +17,7 @@ class HipConv2d(nn.Conv2d):
         self._pw_folded = engine.PackedWeight()      # eval-mode BatchNorm folded in
         self._pw32 = engine.PackedWeightF32()        # the same in fp32 (conv_bn_f32)
         self._pw32_plain = engine.PackedWeightF32()  # fp32 without a fold (conv_bn_train_f32, the teacher's decoder)
+        self._pw32_train = engine.PackedWeightF32()  # fp32 training operands (conv_bn_f32_autograd)
 
     def forward(self, x):
         if x.shape[1] % 8 or x.dtype != torch.bfloat16:
@@ -123,6 +124,16 @@ def conv_bn_any_f32(conv, bn, x, relu=False, residual=None):
     return (conv_bn_train_f32 if bn.training else conv_bn_f32)(conv, bn, x, relu=relu, residual=residual)
 
 
+def conv_bn_f32_autograd(conv, bn, x, relu=False, residual=None):
+    """conv -> train-mode BatchNorm2d [-> + residual] [-> ReLU] in fp32 WITH autograd (K21): hip.conv2d_dilated_f32_train, then
+    hip.batch_norm_f32_train.  The forward's bits are conv_bn_train_f32's.  An eval-mode BatchNorm is refused (conv_bn_f32)."""
+    if not bn.training:
+        raise NotImplementedError("conv_bn_f32_autograd is the batch-statistics form: an eval-mode BatchNorm folds (conv_bn_f32)")
+    y = hip.conv2d_dilated_f32_train(x, conv.weight, conv.bias, stride=conv.stride[0], pad=conv.padding[0], dilation=conv.dilation[0],
+                                     pw=conv._pw32_train)
+    return hip.batch_norm_f32_train(y, bn, relu=relu, residual=residual)
+
+
 def conv3x3(in_planes, out_planes, stride=1, groups=1, dilation=1):
     assert groups == 1
     return HipConv2d(in_planes, out_planes, kernel_size=3, stride=stride, padding=dilation, bias=False, dilation=dilation)
@@ -194,6 +205,14 @@ class Bottleneck(nn.Module):
         out = conv_bn_any_f32(self.conv2, self.bn2, out, relu=True)
         identity = x if self.downsample is None else conv_bn_any_f32(self.downsample[0], self.downsample[1], x)
         return conv_bn_any_f32(self.conv3, self.bn3, out, relu=True, residual=identity)
+
+    def forward_fp32_autograd(self, x):
+        """forward_train_fp32 with autograd (K21): the same bits forward, every BatchNorm in train mode; backward on the fp32
+        kernels (weight, BatchNorm and data gradients)."""
+        out = conv_bn_f32_autograd(self.conv1, self.bn1, x, relu=True)
+        out = conv_bn_f32_autograd(self.conv2, self.bn2, out, relu=True)
+        identity = x if self.downsample is None else conv_bn_f32_autograd(self.downsample[0], self.downsample[1], x)
+        return conv_bn_f32_autograd(self.conv3, self.bn3, out, relu=True, residual=identity)
 
 
 class ResNet(nn.Module):
@@ -269,6 +288,17 @@ class ResNet(nn.Module):
             for layer in (self.layer1, self.layer2, self.layer3, self.layer4):
                 for block in layer:
                     x = block.forward_train_fp32(x)
+            return x
+
+    def features_fp32_autograd(self, x):
+        """features_fp32 with autograd (K21): stem, max pool and layer1-4 in fp32 with every BatchNorm in train mode; the same
+        bits forward, the gradients of every parameter on the fp32 backward kernels."""
+        with engine.defer_bn_counters():
+            x = conv_bn_f32_autograd(self.conv1, self.bn1, x, relu=True)
+            x = hip.max_pool_3x3s2_f32_train(x)
+            for layer in (self.layer1, self.layer2, self.layer3, self.layer4):
+                for block in layer:
+                    x = block.forward_fp32_autograd(x)
             return x
 
     def forward(self, x):
