@@ -843,6 +843,29 @@ int oess_batch_norm_bwd_f32(const oess_f32_view_t* x, const oess_f32_view_t* out
 int oess_maxpool3x3s2_bwd_f32(const oess_f32_view_t* x, const oess_f32_view_t* dy, int B, int H, int W, int C, const oess_f32_view_t* dx,
                               oess_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------
+ * K22 fp32 DeepLabv3-R50 training: what the ASPP head (models/deeplabv3.py:305-348 of the reference) needs next to the K18 / K21
+ * layer set.  The head's convolutions and BatchNorms are the K21 entries; the pooling branch's forward is
+ * oess_global_avg_pool_fwd_f32 + oess_aspp_pool_fwd_f32 (pooled = the means, in_scale = 1, z_bf16 = NULL).  Additions only: the
+ * ABI version stays.  No atomics: every result repeats bit for bit.
+ *
+ * oess_dropout_f32: nn.Dropout(p) on fp32 views: y = x * (1.0f / (1.0f - p)) (one fp32 multiply) where the element is kept, 0.0f
+ *   where it is dropped.  x, y: B x H x W x C views with any strides (channel slices included); y may be x.  The keep decision
+ *   of element (pixel, c) is oess_dropout_nhwc_bf16's for the same (seed, offset, P = B H W, C): group i = pixel (C / 8) + c / 8
+ *   with pixels in dense B H W order, Philox-4x32-10 counter (i, offset) and key seed, 16-bit lane c % 8 of its four words,
+ *   kept when lane >= thr = (unsigned)(p 65536 + 0.5).  The backward pass is the same call on the gradient with the same
+ *   (seed, offset).  One thread per 8 channels of a pixel and one Philox call; two 16-byte accesses per view when both views have
+ *   dense 16-byte aligned channels, element accesses otherwise.  OESS_EINVAL before any launch: a null view, C % 8 != 0, p outside
+ *   [0, 1), a non-positive size.
+ * oess_aspp_pool_bwd_f32o: oess_aspp_pool_bwd_f32 whose gradient of the pooled vectors leaves as fp32 [B x Cin] (nullable): the
+ *   same two kernels, the last one instantiated for a float store.  Every other output has oess_aspp_pool_bwd_f32's bits.
+ * ------------------------------------------------------------------------------------------ */
+int oess_dropout_f32(const oess_f32_view_t* x, const oess_f32_view_t* y, int B, int H, int W, int C, float p, unsigned long long seed,
+                     unsigned long long offset, oess_stream_t stream);
+int oess_aspp_pool_bwd_f32o(const float* grad_z, const float* pooled, float in_scale, const float* w, const float* gamma, const float* y_pre,
+                            const float* stat, const float* z, int B, int Cin, int Cout, float* dy_scratch, float* grad_w,
+                            float* grad_gamma, float* grad_beta, float* grad_pooled, oess_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -191,6 +191,9 @@ SIGNATURES = {
     "oess_batch_norm_bwd_f32": (c_int, [c_view, c_view, c_view, c_int, c_int, c_int, c_int, c_vp, c_vp, c_f, c_vp, c_int, c_view, c_vp,
                                         c_vp, c_view, c_vp, c_sz, c_vp]),
     "oess_maxpool3x3s2_bwd_f32": (c_int, [c_view, c_view, c_int, c_int, c_int, c_int, c_view, c_vp]),
+    "oess_dropout_f32": (c_int, [c_view, c_view, c_int, c_int, c_int, c_int, c_f, c_u64, c_u64, c_vp]),
+    "oess_aspp_pool_bwd_f32o": (c_int, [c_vp, c_vp, c_f, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_vp,
+                                        c_vp]),
 }
 
 _lib = None

@@ -9,6 +9,7 @@
 #include <stdint.h>
 #include "oess.h"
 #include "oess_common.h"
+#include "philox.h"
 
 namespace {
 using namespace oess;
@@ -102,17 +103,7 @@ __global__ __launch_bounds__(THREADS) void maxpool3x3s2_bwd_kernel(const uint16_
 }
 
 // ------------------------------------------------------------------------------------------------ dropout
-// Philox-4x32-10 (Salmon et al. 2011): counter = (element group, call offset), key = seed.
-__device__ __forceinline__ uint4 philox4x32_10(uint4 c, uint2 k) {
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        const uint32_t hi0 = __umulhi(0xD2511F53u, c.x), lo0 = 0xD2511F53u * c.x;
-        const uint32_t hi1 = __umulhi(0xCD9E8D57u, c.z), lo1 = 0xCD9E8D57u * c.z;
-        c = make_uint4(hi1 ^ c.y ^ k.x, lo1, hi0 ^ c.w ^ k.y, lo0);
-        k.x += 0x9E3779B9u; k.y += 0xBB67AE85u;
-    }
-    return c;
-}
+// Philox-4x32-10 and the keep rule: philox.h, shared with the fp32 kernel (deeplab_bwd_f32.hip).
 // y = x * keep / (1 - p) with keep ~ Bernoulli(1 - thr / 65536); the same (seed, offset) reproduces the mask, so the backward
 // pass is this kernel applied to the gradient.  8 channels (16 bytes) per thread, one Philox call per thread.
 __global__ __launch_bounds__(THREADS) void dropout_kernel(const uint16_t* __restrict__ x, int64_t xps, uint16_t* __restrict__ y, int64_t yps,
@@ -123,17 +114,13 @@ __global__ __launch_bounds__(THREADS) void dropout_kernel(const uint16_t* __rest
     for (int64_t i = (int64_t)blockIdx.x * THREADS + threadIdx.x; i < total; i += (int64_t)gridDim.x * THREADS) {
         const int64_t p = i / c8;
         const int c0 = (int)(i - p * c8) * 8;
-        const uint4 r = philox4x32_10(make_uint4((uint32_t)i, (uint32_t)((uint64_t)i >> 32), (uint32_t)offset, (uint32_t)(offset >> 32)),
-                                      make_uint2((uint32_t)seed, (uint32_t)(seed >> 32)));
+        const uint4 r = dropout_words(i, seed, offset);
         const uint32_t w[4] = {r.x, r.y, r.z, r.w};
         V8 v;
         v.q = *reinterpret_cast<const uint4*>(x + p * xps + c0);
         float f[8];
 #pragma unroll
-        for (int k = 0; k < 8; ++k) {
-            const unsigned u = (w[k >> 1] >> (16 * (k & 1))) & 0xffffu;
-            f[k] = (u >= thr) ? bf16_to_f32(v.h[k]) * scale : 0.f;
-        }
+        for (int k = 0; k < 8; ++k) f[k] = dropout_keep(w, k, thr) ? bf16_to_f32(v.h[k]) * scale : 0.f;
         *reinterpret_cast<uint4*>(y + p * yps + c0) = pack_bf16x8(f);
     }
 }
@@ -205,10 +192,14 @@ __global__ __launch_bounds__(THREADS) void aspp_pool_bn_bwd_kernel(const float* 
         dy[(size_t)b * Cout + c] = k * (g - mdb - xh * mdg);
     }
 }
-// blocks [0, nW): dW[c][k] = in_scale sum_b dy[b][c] sums[b][k];   blocks [nW, ..): dsums[b][k] = in_scale sum_c dy[b][c] w[c][k] (bf16)
+// blocks [0, nW): dW[c][k] = in_scale sum_b dy[b][c] sums[b][k];   blocks [nW, ..): dsums[b][k] = in_scale sum_c dy[b][c] w[c][k],
+// stored as T: bf16 (uint16_t, the bf16 training path) or fp32 (float, oess_aspp_pool_bwd_f32o)
+__device__ __forceinline__ void store_as(uint16_t* p, float v) { *p = f32_to_bf16(v); }
+__device__ __forceinline__ void store_as(float* p, float v) { *p = v; }
+template <typename T>
 __global__ __launch_bounds__(THREADS) void aspp_pool_gemv_bwd_kernel(const float* __restrict__ dy, const float* __restrict__ pooled,
                                                                      const float* __restrict__ w, float in_scale, int B, int Cin, int Cout,
-                                                                     int nW, float* __restrict__ dw, uint16_t* __restrict__ dpooled) {
+                                                                     int nW, float* __restrict__ dw, T* __restrict__ dpooled) {
     if ((int)blockIdx.x < nW) {
         const int64_t i = (int64_t)blockIdx.x * THREADS + threadIdx.x;
         if (i >= (int64_t)Cout * Cin) return;
@@ -222,7 +213,7 @@ __global__ __launch_bounds__(THREADS) void aspp_pool_gemv_bwd_kernel(const float
         const int b = (int)(i / Cin), k = (int)(i - (int64_t)b * Cin);
         float a = 0.f;
         for (int c = 0; c < Cout; ++c) a += dy[(size_t)b * Cout + c] * w[(size_t)c * Cin + k];
-        dpooled[i] = f32_to_bf16(a * in_scale);
+        store_as(dpooled + i, a * in_scale);
     }
 }
 
@@ -230,6 +221,25 @@ int grid_for(int64_t items) {
     int64_t g = (items + THREADS - 1) / THREADS;
     const int64_t cap = (int64_t)num_cus() * 16;
     return (int)(g < 1 ? 1 : (g > cap ? cap : g));
+}
+
+// the two launches of the branch's backward; T: the store type of the pooled vector's gradient
+template <typename T>
+int aspp_pool_bwd(const float* grad_z, const float* pooled, float in_scale, const float* w, const float* gamma, const float* y_pre,
+                  const float* stat, const float* z, int B, int Cin, int Cout, float* dy_scratch, float* grad_w, float* grad_gamma,
+                  float* grad_beta, T* grad_pooled, oess_stream_t stream) {
+    if (!grad_z || !pooled || !w || !gamma || !y_pre || !stat || !z || !dy_scratch || !grad_w || !grad_gamma || !grad_beta || B < 2 ||
+        B > AP_MAXB || Cin <= 0 || Cout <= 0)
+        return OESS_EINVAL;
+    hipStream_t st = (hipStream_t)stream;
+    hipLaunchKernelGGL(aspp_pool_bn_bwd_kernel, dim3((Cout + THREADS - 1) / THREADS), dim3(THREADS), 0, st, grad_z, y_pre, stat, z, gamma, B,
+                       Cout, dy_scratch, grad_gamma, grad_beta);
+    const int nW = (int)(((int64_t)Cout * Cin + THREADS - 1) / THREADS);
+    const int nP = grad_pooled ? (int)(((int64_t)B * Cin + THREADS - 1) / THREADS) : 0;
+    hipLaunchKernelGGL(aspp_pool_gemv_bwd_kernel<T>, dim3(nW + nP), dim3(THREADS), 0, st, (const float*)dy_scratch, pooled, w, in_scale, B, Cin,
+                       Cout, nW, grad_w, grad_pooled);
+    OESS_HIP(hipGetLastError());
+    return OESS_OK;
 }
 
 }  // namespace
@@ -265,7 +275,7 @@ int oess_dropout_nhwc_bf16(const void* x, long long x_pix_stride, void* y, long 
     if (!x || !y || P <= 0 || C <= 0 || (C & 7) || (x_pix_stride & 7) || (y_pix_stride & 7) || x_pix_stride < C || y_pix_stride < C ||
         !(p >= 0.f && p < 1.f) || ((uintptr_t)x & 15) || ((uintptr_t)y & 15))
         return OESS_EINVAL;
-    const unsigned thr = (unsigned)(p * 65536.0f + 0.5f);
+    const unsigned thr = dropout_threshold(p);
     hipLaunchKernelGGL(dropout_kernel, dim3(grid_for(P * (C >> 3))), dim3(THREADS), 0, (hipStream_t)stream, (const uint16_t*)x,
                        (int64_t)x_pix_stride, (uint16_t*)y, (int64_t)y_pix_stride, (int64_t)P, C, thr, 1.0f / (1.0f - p), seed, offset);
     OESS_HIP(hipGetLastError());
@@ -287,18 +297,15 @@ int oess_aspp_pool_fwd_f32(const float* pooled, float in_scale, const float* w, 
 int oess_aspp_pool_bwd_f32(const float* grad_z, const float* pooled, float in_scale, const float* w, const float* gamma, const float* y_pre,
                            const float* stat, const float* z, int B, int Cin, int Cout, float* dy_scratch, float* grad_w,
                            float* grad_gamma, float* grad_beta, void* grad_pooled_bf16, oess_stream_t stream) {
-    if (!grad_z || !pooled || !w || !gamma || !y_pre || !stat || !z || !dy_scratch || !grad_w || !grad_gamma || !grad_beta || B < 2 ||
-        B > AP_MAXB || Cin <= 0 || Cout <= 0)
-        return OESS_EINVAL;
-    hipStream_t st = (hipStream_t)stream;
-    hipLaunchKernelGGL(aspp_pool_bn_bwd_kernel, dim3((Cout + THREADS - 1) / THREADS), dim3(THREADS), 0, st, grad_z, y_pre, stat, z, gamma, B,
-                       Cout, dy_scratch, grad_gamma, grad_beta);
-    const int nW = (int)(((int64_t)Cout * Cin + THREADS - 1) / THREADS);
-    const int nP = grad_pooled_bf16 ? (int)(((int64_t)B * Cin + THREADS - 1) / THREADS) : 0;
-    hipLaunchKernelGGL(aspp_pool_gemv_bwd_kernel, dim3(nW + nP), dim3(THREADS), 0, st, (const float*)dy_scratch, pooled, w, in_scale, B, Cin, Cout,
-                       nW, grad_w, (uint16_t*)grad_pooled_bf16);
-    OESS_HIP(hipGetLastError());
-    return OESS_OK;
+    return aspp_pool_bwd<uint16_t>(grad_z, pooled, in_scale, w, gamma, y_pre, stat, z, B, Cin, Cout, dy_scratch, grad_w, grad_gamma,
+                                   grad_beta, (uint16_t*)grad_pooled_bf16, stream);
+}
+
+int oess_aspp_pool_bwd_f32o(const float* grad_z, const float* pooled, float in_scale, const float* w, const float* gamma, const float* y_pre,
+                            const float* stat, const float* z, int B, int Cin, int Cout, float* dy_scratch, float* grad_w,
+                            float* grad_gamma, float* grad_beta, float* grad_pooled, oess_stream_t stream) {
+    return aspp_pool_bwd<float>(grad_z, pooled, in_scale, w, gamma, y_pre, stat, z, B, Cin, Cout, dy_scratch, grad_w, grad_gamma,
+                                grad_beta, grad_pooled, stream);
 }
 
 }  // extern "C"

@@ -2653,3 +2653,140 @@ def max_pool_3x3s2_f32_train(x):
         raise ValueError("max_pool_3x3s2_f32_train takes a 4-D fp32 tensor (the bf16 training path is hip.max_pool_3x3s2)")
     _need_gpu(x)
     return _MaxPool3x3s2F32Train.apply(x)
+
+
+# ------------------------------------------------------------------------------------------ K22: fp32 DeepLabv3-R50 training
+def _dropout_f32_launch(x, p, seed, offset):
+    B, C, H, W = x.shape
+    y = _f32_out(None, B, C, H, W, x.device)
+    vx, vy = _f32_view(x, "x"), _f32_view(y, "y")
+    _lib.check(_lib.load().oess_dropout_f32(ctypes.byref(vx), ctypes.byref(vy), B, H, W, C, p, seed, offset, _stream()), "oess_dropout_f32")
+    return y
+
+
+class _DropoutF32(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, p, seed, offset):
+        ctx.meta = (p, seed, offset)
+        return _dropout_f32_launch(x, p, seed, offset)
+
+    @staticmethod
+    def backward(ctx, g):
+        if g.dtype != torch.float32:
+            g = g.float()
+        return _dropout_f32_launch(g, *ctx.meta), None, None, None
+
+
+def dropout_f32(x, p, training=True, owner=None):
+    """nn.Dropout(p) on a logical [B, C, H, W] fp32 tensor with any strides, C % 8 == 0 (K22, oess_dropout_f32): the Philox mask
+    of hip.dropout, element for element, for the same seed, counter and shape, recomputed in the backward pass instead of stored;
+    a kept value is x * float32(1 / (1 - p)).  The counter rule is hip.dropout's own (`owner`: the nn.Dropout module), so a model
+    that alternates bf16 and fp32 steps walks one mask sequence.  training=False or p <= 0 returns x itself."""
+    global _DROPOUT_CALLS
+    if not training or p <= 0.0:
+        return x
+    if x.dtype != torch.float32 or x.ndim != 4 or x.shape[1] % 8:
+        raise ValueError("dropout_f32 needs a 4-D fp32 tensor [B, C, H, W] with C % 8 == 0 (the bf16 training path is hip.dropout)")
+    if not p < 1.0:
+        raise ValueError(f"dropout_f32: p must lie in [0, 1), got {p}")
+    _need_gpu(x)
+    if owner is not None:
+        calls = getattr(owner, "_oess_dropout_calls", 0) + 1
+        owner._oess_dropout_calls = calls
+        calls += 1 << 40                                         # own sequence: never collides with the process-wide counter
+    else:
+        _DROPOUT_CALLS += 1
+        calls = _DROPOUT_CALLS
+    return _DropoutF32.apply(x, float(p), int(torch.initial_seed()) & 0xFFFFFFFFFFFFFFFF, calls)
+
+
+def _avg_pool_rows_f32(x):
+    """per-sample channel means of a logical [B, C, H, W] fp32 view -> dense fp32 [B, C] (oess_global_avg_pool_fwd_f32)"""
+    lib = _lib.load()
+    B, C, H, W = x.shape
+    need = lib.oess_global_avg_pool_f32_workspace_bytes(B, H, W, C)
+    if need == 0:
+        raise ValueError(f"aspp_pool_branch_f32: no pooling kernel for a {(B, C, H, W)} map")
+    ws = _workspace(need, x.device, tag="avgpool_f32")
+    out = torch.empty((B, C), dtype=torch.float32, device=x.device)
+    vx = _f32_view(x, "x")
+    _lib.check(lib.oess_global_avg_pool_fwd_f32(ctypes.byref(vx), B, H, W, C, _ptr(out), _ptr(ws), ws.numel(), _stream()),
+               "oess_global_avg_pool_fwd_f32")
+    return out
+
+
+class _ASPPPoolBranchF32(torch.autograd.Function):
+    """ASPPPooling (models/deeplabv3.py:305-316 of the reference) in fp32 as one node: AdaptiveAvgPool2d(1) -> 1x1 conv ->
+    BatchNorm2d(train) over the B pooled vectors -> ReLU -> the 1x1 map broadcast over H x W (bilinear from 1x1 == broadcast)."""
+
+    @staticmethod
+    def forward(ctx, x, weight, gamma, beta, run_mean, run_var, momentum, eps):
+        lib = _lib.load()
+        B, C, H, W = x.shape
+        Cout = weight.shape[0]
+        pooled = _avg_pool_rows_f32(x)                          # the means: in_scale = 1 in both directions
+        w2 = weight.detach().reshape(Cout, C)
+        if not w2.is_contiguous():
+            w2 = w2.contiguous()
+        buf = torch.empty((2 * B + 2, Cout), dtype=torch.float32, device=x.device)      # y_pre | z | mean, rstd
+        y_pre, z, stat = buf[:B], buf[B:2 * B], buf[2 * B:]
+        _lib.check(lib.oess_aspp_pool_fwd_f32(_ptr(pooled), 1.0, _ptr(w2), _ptr(gamma.detach()), _ptr(beta.detach()), _ptr(run_mean),
+                                              _ptr(run_var), float(momentum), float(eps), B, C, Cout, _ptr(y_pre), _ptr(stat), _ptr(z),
+                                              None, _stream()), "oess_aspp_pool_fwd_f32")
+        _bump(run_mean)
+        _bump(run_var)
+        ctx.save_for_backward(pooled, w2, gamma.detach(), buf)
+        ctx.geom = (B, H, W, C, Cout)
+        return z.clone().view(B, Cout, 1, 1).expand(B, Cout, H, W)
+
+    @staticmethod
+    def backward(ctx, g):
+        lib = _lib.load()
+        pooled, w2, gamma, buf = ctx.saved_tensors
+        B, H, W, C, Cout = ctx.geom
+        y_pre, z, stat = buf[:B], buf[B:2 * B], buf[2 * B:]
+        if g.dtype != torch.float32:
+            g = g.float()
+        gz = _avg_pool_rows_f32(g) * float(H * W)               # per-sample sums of the gradient slice, read where it lies
+        out = torch.empty((B * Cout + Cout * C + 2 * Cout,), dtype=torch.float32, device=g.device)
+        dy = out[:B * Cout]
+        gw = out[B * Cout:B * Cout + Cout * C].view(Cout, C, 1, 1)
+        gg = out[B * Cout + Cout * C:B * Cout + Cout * C + Cout]
+        gb = out[B * Cout + Cout * C + Cout:]
+        gp = torch.empty((B, C), dtype=torch.float32, device=g.device) if ctx.needs_input_grad[0] else None
+        if any(ctx.needs_input_grad[:4]):
+            _lib.check(lib.oess_aspp_pool_bwd_f32o(_ptr(gz), _ptr(pooled), 1.0, _ptr(w2), _ptr(gamma), _ptr(y_pre), _ptr(stat), _ptr(z),
+                                                   B, C, Cout, _ptr(dy), _ptr(gw), _ptr(gg), _ptr(gb), _ptr(gp), _stream()),
+                       "oess_aspp_pool_bwd_f32o")
+        gx = None
+        if gp is not None:                                      # d mean / d x = 1 / (H W): the quotient, expanded with stride 0
+            gx = (gp * (1.0 / (H * W))).view(B, C, 1, 1).expand(B, C, H, W)
+        need = ctx.needs_input_grad
+        return gx, (gw if need[1] else None), (gg if need[2] else None), (gb if need[3] else None), None, None, None, None
+
+
+def aspp_pool_branch_f32(x, conv, bn):
+    """ASPPPooling.forward in fp32 for a TRAIN-mode BatchNorm (K22), one autograd node: x logical [B, Cin, H, W] fp32 with any
+    strides -> the [B, Cout, 1, 1] row expanded with stride 0 over H x W.  Forward: oess_global_avg_pool_fwd_f32, then
+    oess_aspp_pool_fwd_f32 (B-row GEMV, BatchNorm over the B pooled vectors, ReLU, the running statistics moved one step, the batch
+    counted).  Backward: the per-sample sums of the incoming gradient by the same pooling kernel, oess_aspp_pool_bwd_f32o, and dx as
+    the [B, Cin, 1, 1] quotient expanded with stride 0.  2 <= B <= 16, Cin % 4 == 0; everything else raises before any launch."""
+    if x.dtype != torch.float32 or x.ndim != 4:
+        raise ValueError("aspp_pool_branch_f32 takes a 4-D fp32 tensor (the bf16 training path is hip.aspp_pool_branch)")
+    B, Cin = x.shape[0], x.shape[1]
+    if not 2 <= B <= 16:
+        raise ValueError(f"aspp_pool_branch_f32 needs 2 <= B <= 16 samples (BatchNorm over the B pooled vectors), got {B}")
+    if Cin % 4:
+        raise ValueError(f"aspp_pool_branch_f32 needs Cin % 4 == 0, got {Cin}")
+    if not bn.training:
+        raise NotImplementedError("aspp_pool_branch_f32 is the batch-statistics form: an eval-mode BatchNorm folds (conv_bn_f32)")
+    if bn.momentum is None or bn.running_mean is None or bn.weight is None:
+        raise NotImplementedError("aspp_pool_branch_f32 needs an affine BatchNorm with running statistics and a momentum")
+    w = conv.weight
+    if w.dtype != torch.float32 or tuple(w.shape[1:]) != (Cin, 1, 1) or conv.bias is not None or bn.weight.dtype != torch.float32:
+        raise ValueError(f"aspp_pool_branch_f32: a bias-free fp32 1 x 1 conv over {Cin} channels is needed, got {tuple(w.shape)}")
+    _need_gpu(x, w, bn.weight, bn.running_mean)
+    from . import engine as _engine
+    y = _ASPPPoolBranchF32.apply(x, w, bn.weight, bn.bias, bn.running_mean, bn.running_var, float(bn.momentum), float(bn.eps))
+    _engine.bump_bn_counter(bn)
+    return y

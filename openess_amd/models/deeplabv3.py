@@ -8,7 +8,7 @@ import torch.nn.functional as F
 
 from .. import engine, hip
 from . import _resnet as resnet
-from ._resnet import HipConv2d, conv_bn, conv_bn_f32
+from ._resnet import HipConv2d, conv_bn, conv_bn_f32, conv_bn_f32_autograd
 
 
 class IntermediateLayerGetter(nn.ModuleDict):
@@ -58,6 +58,25 @@ class IntermediateLayerGetter(nn.ModuleDict):
                 out[self.return_layers[name]] = x
         return out
 
+    def forward_fp32_autograd(self, x):
+        """forward() in fp32 with autograd and every BatchNorm in train mode (K22): stem, max pool and the blocks on the K21 layer
+        set; the bits of ResNet.features_fp32_autograd.  x fp32 [B, 3, H, W], any layout."""
+        out = OrderedDict()
+        with engine.defer_bn_counters():
+            for name, module in self.named_children():
+                if name == 'conv1':
+                    x = conv_bn_f32_autograd(module, self['bn1'], x, relu=True)
+                elif name in ('bn1', 'relu'):
+                    continue
+                elif name == 'maxpool':
+                    x = hip.max_pool_3x3s2_f32_train(x)
+                else:
+                    for block in module:
+                        x = block.forward_fp32_autograd(x)
+                if name in self.return_layers:
+                    out[self.return_layers[name]] = x
+        return out
+
 
 class _ConvBNReLU(nn.Sequential):
     def forward(self, x, out=None):
@@ -65,6 +84,9 @@ class _ConvBNReLU(nn.Sequential):
 
     def forward_fp32(self, x, out=None):
         return conv_bn_f32(self[0], self[1], x, relu=True, out=out)
+
+    def forward_fp32_autograd(self, x):
+        return conv_bn_f32_autograd(self[0], self[1], x, relu=True)
 
 
 class ASPPConv(_ConvBNReLU):
@@ -85,6 +107,11 @@ class ASPPPooling(nn.Sequential):
         y = conv_bn_f32(self[1], self[2], hip.global_avg_pool_f32(x), relu=True, pw=self._pw32)
         out.copy_(y.expand(-1, -1, x.shape[2], x.shape[3]))
         return out
+
+    def forward_fp32_autograd(self, x):
+        """The branch in fp32 with autograd and a train-mode BatchNorm (K22), one node: the [B, Cout, 1, 1] row expanded with
+        stride 0 over the map."""
+        return hip.aspp_pool_branch_f32(x, self[1], self[2])
 
     def forward(self, x, out=None):
         size = x.shape[-2:]
@@ -148,6 +175,15 @@ class ASPP(nn.Module):
             conv.forward_fp32(x, out=res[:, i * oc:(i + 1) * oc])
         return conv_bn_f32(self.project[0], self.project[1], res, relu=True)          # Dropout: the identity in eval mode
 
+    def forward_fp32_autograd(self, x):
+        """forward() in fp32 with autograd (K22): the five branches, one concatenation pass (along the dense channel axis of
+        the NHWC maps, so the 1280-channel map and the slices of its gradient are channels_last), the projection and the Philox
+        dropout of hip.dropout on the module's own counter."""
+        res = torch.cat([conv.forward_fp32_autograd(x).permute(0, 2, 3, 1) for conv in self.convs], dim=3).permute(0, 3, 1, 2)
+        y = conv_bn_f32_autograd(self.project[0], self.project[1], res, relu=True)
+        drop = self.project[3]
+        return hip.dropout_f32(y, drop.p, drop.training, owner=drop)
+
 
 class DeepLabHead(nn.Module):
     def __init__(self, text_embeddings_path, text_categories, in_channels, num_classes, aspp_dilate=[12, 24, 36]):
@@ -168,6 +204,7 @@ class DeepLabHead(nn.Module):
                 self.text_embeddings[:, :] = loaded[:, :]
         self._pw_text = engine.PackedWeight()
         self._pw_text32 = engine.PackedWeightF32()
+        self._pw_text32_train = engine.PackedWeightF32()      # fp32 training operands (forward_fp32_autograd)
 
     def forward_fp32(self, feature):
         feature = self.ASPP.forward_fp32(feature['out'])
@@ -175,6 +212,15 @@ class DeepLabHead(nn.Module):
         te = self.text_embeddings
         op = self._pw_text32.get_composed([te], lambda: (te.detach().double()[:, :, None, None], None))
         return hip.conv2d_f32(x, op.packed, None, te.shape[0], 1, 1), feature
+
+    def forward_fp32_autograd(self, feature):
+        """forward() in fp32 with autograd (K22): (logits, ASPP feature) at the backbone's resolution.  The text embeddings are
+        the 1 x 1 classifier's weight as they are: a Parameter gets its gradient, a buffer gets none."""
+        feature = self.ASPP.forward_fp32_autograd(feature['out'])
+        x = conv_bn_f32_autograd(self.classifier[0], self.classifier[1], feature, relu=True)
+        te = self.text_embeddings
+        logits = hip.conv2d_dilated_f32_train(x, te[:, :, None, None], None, pw=self._pw_text32_train, ver=te._version)
+        return logits, feature
 
     def forward(self, feature):
         feature = self.ASPP(feature['out'])
@@ -233,6 +279,36 @@ class deeplabv3_resnet50(nn.Module):
                                           "is in train mode (batch statistics); call .eval() first")
             if isinstance(m, nn.Dropout) and m.training and m.p > 0:
                 raise NotImplementedError(f"forward_fp32 is inference only: dropout {name} is in train mode; call .eval() first")
+
+    def check_fp32_train(self):
+        """Raises NotImplementedError for what forward_fp32_train does not run: it is the train-mode network, every BatchNorm on
+        batch statistics with a running-statistics step."""
+        for name, m in self.named_modules():
+            if isinstance(m, nn.modules.batchnorm._BatchNorm):
+                what = ("is in eval mode (running statistics): call .train() first, or use forward_fp32" if not m.training else
+                        "keeps no running statistics" if m.running_mean is None or m.running_var is None else
+                        "has momentum=None (cumulative moving average)" if m.momentum is None else None)
+                if what is not None:
+                    raise NotImplementedError(f"forward_fp32_train runs every BatchNorm on batch statistics with a momentum step: "
+                                              f"{name or 'the model'} {what}")
+
+    def forward_fp32_train(self, x, want_feats=False):
+        """forward() of the train-mode network in fp32 with autograd: (logits, feats).  logits: fp32 at the input
+        size, through the linear probe when the model has one.  feats: the ASPP feature resized to the input size, formed only
+        when asked for (256 channels at full resolution), otherwise None.  Frozen parameters record nothing: a node whose inputs
+        need no gradient keeps no graph, the first trainable convolution skips its data gradient.  No buffer, operand or state
+        is shared with forward(), except the Dropout module's mask counter (one mask sequence for both)."""
+        self.check_fp32_train()
+        if x.dtype != torch.float32 or x.ndim != 4:
+            raise ValueError("forward_fp32_train takes a float32 [B, 3, H, W] image batch")
+        input_shape = x.shape[-2:]
+        with engine.defer_bn_counters():
+            logist, feats = self.classifier.forward_fp32_autograd(self.backbone.forward_fp32_autograd(x))
+        logist = hip.bilinear_resize(logist, size=input_shape, align_corners=False)
+        feats = hip.bilinear_resize(feats, size=input_shape, align_corners=False) if want_feats else None
+        if self.if_linear_probing:
+            logist = hip.linear_probe(logist, self.linear_probe)
+        return logist, feats
 
     @torch.no_grad()
     def forward_fp32(self, x):

@@ -147,9 +147,22 @@ class SupervisedTrainer(BaseTrainer):
         rec.last_states_for_each_channel = {'grayscale': None}
         return latent
 
-    def _train_latents(self, event):
+    def _step_precision(self, precision):
+        """Arithmetic of one training step: `precision`, or the trainer's train_precision for None.  The event students in fp32
+        need the fp32 reconstructor, which only a trainer built with train_precision / eval_precision: fp32 has (the rule of
+        val_logits); frame2recon needs nothing beyond its model (deeplabv3_resnet50.forward_fp32_train)."""
+        precision = self.train_precision if precision is None else precision
+        if precision not in ('bf16', 'fp32'):
+            raise ValueError(f"precision must be 'bf16' or 'fp32', got {precision!r}")
+        if precision == 'fp32' and self.settings.config_option in ('recon2voxel', 'frame2voxel') and \
+                getattr(self, 'reconstructor_fp32', None) is None:
+            raise RuntimeError("this trainer was built without train_precision: fp32")
+        return precision
+
+    def _train_latents(self, event, precision=None):
         """Detached latents of the frozen front end in the arithmetic of the training step."""
-        latent = self._latents_fp32(event, latents_only=True) if self.train_precision == 'fp32' else self._latents(event)
+        precision = self.train_precision if precision is None else precision
+        latent = self._latents_fp32(event, latents_only=True) if precision == 'fp32' else self._latents(event)
         return {k: v.detach() for k, v in latent.items()}
 
     def _set_modes(self):
@@ -182,8 +195,14 @@ class SupervisedTrainer(BaseTrainer):
             done.record(F)
         return latent, done
 
-    def task_train_step(self, batch, front=None):
+    def task_train_step(self, batch, front=None, precision=None):
+        """Forward and loss of one step.  precision: 'bf16' / 'fp32' for this call, None for the trainer's train_precision (a
+        `front` handed in was computed by front_step in train_precision).  frame2recon takes fp32 only through this argument: the
+        YAML key still refuses it at construction."""
         s = self.settings
+        precision = self._step_precision(precision)
+        if front is not None and precision != self.train_precision:
+            raise ValueError(f"front_step computed its latents in {self.train_precision}; a {precision} step computes its own")
         losses, t_loss = {}, 0.
         self._set_modes()
         gt = batch[1]
@@ -196,8 +215,8 @@ class SupervisedTrainer(BaseTrainer):
                     if torch.is_tensor(v):
                         v.record_stream(main)
             else:
-                latent = self._train_latents(batch[0])
-            if self.train_precision == 'fp32':
+                latent = self._train_latents(batch[0], precision)
+            if precision == 'fp32':
                 pred, _ = self.task_backend.forward_fp32_train(latent)
             else:
                 pred, _ = self.task_backend(latent)
@@ -205,16 +224,20 @@ class SupervisedTrainer(BaseTrainer):
             loss = self.task_loss(pred[1], labels) * s.weight_task_loss
             losses['semseg_sensor_b_loss'] = loss.detach()
         else:
-            logits, _ = self.model_recon(batch[2])
+            if precision == 'fp32':
+                logits, _ = self.model_recon.forward_fp32_train(batch[2])
+            else:
+                logits, _ = self.model_recon(batch[2])
             loss = self.task_loss(logits, gt) * s.weight_task_loss
             losses['semseg_recon_loss'] = loss.detach()
         return t_loss + loss, losses, {}
 
-    def train_step(self, batch, front=None):
+    def train_step(self, batch, front=None, precision=None):
+        precision = self._step_precision(precision)      # refused before the gradients are cleared
         for opt in self.optimizers_dict.values():
             opt.zero_grad()
         self.grad_reducer.prepare()          # N > 1: gradients accumulate straight into the all-reduce buckets
-        t_loss, losses, outputs = self.task_train_step(batch, front=front)
+        t_loss, losses, outputs = self.task_train_step(batch, front=front, precision=precision)
         t_loss.backward()
         self.grad_reducer()
         for opt in self.optimizers_dict.values():

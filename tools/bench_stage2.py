@@ -4,7 +4,9 @@ and configs[4] "linear-probe + fine-tune"): the trainers are built through train
 the sizes raised to 440 x 640, B = 8, 20 sub-windows x 100 000 events, ONE batch is prepared on the device (voxelizer included,
 outside the timed region) and `train_step` is timed on it between synchronize fences, like bench.py's headline.
 --precision fp32: the fine-tune and linear-probe steps of the event branch (frame2voxel) with `train_precision: fp32` (K19) next
-to the bf16 step in the same run, interleaved (bf16, fp32, bf16, ... three rounds, the median of each), and their ratio.
+to the bf16 step in the same run, interleaved (bf16, fp32, bf16, ... three rounds, the median of each), and their ratio; and the
+same two steps of frame2recon (K22), where ONE trainer runs both through `train_step(batch, precision=...)` (the YAML key refuses
+frame2recon at construction).
     python tools/bench_stage2.py [--steps 20] [--precision fp32]"""
 import argparse
 import json
@@ -54,10 +56,17 @@ def build(yaml_name, option, flags, tmp, B=8, train_precision=None):
     return trainer, s
 
 
-def _stepper(trainer, batch):
+def _stepper(trainer, batch, precision=None):
     """run(n): n steps in BaseTrainer.trainEpoch's order: the frozen half of step i + 1 (trainers that have one) is enqueued before
-    the trainable half of step i"""
+    the trainable half of step i.  precision: handed to train_step (frame2recon, which has no frozen half)."""
     front_step = getattr(trainer, 'front_step', None) if PIPELINE else None
+    if precision is not None:
+        def run_precision(n):
+            out = None
+            for _ in range(n):
+                out = trainer.train_step(batch, precision=precision)
+            return out
+        return run_precision
 
     def run(n):
         prev = front_step(batch) if front_step is not None else None
@@ -74,11 +83,19 @@ def measure_precisions(steps=20, warm=3, only=None, rounds=3):
     """fp32 next to bf16: both trainers of a case are built, then timed in turn, `rounds` times; the median round of each."""
     out = {}
     for name, yml, option, flags in CASES:
-        if option != "frame2voxel" or (only and name not in only):
+        if name.startswith("openess") or (only and name not in only):
             continue
         with tempfile.TemporaryDirectory(prefix="oess_stage2_", dir="/tmp") as tmp:
             runs, sizes, loss = {}, {}, {}
-            for prec in ("bf16", "fp32"):
+            if option == "frame2recon":                          # one bf16-built trainer, the precision per call
+                trainer, s = build(yml, option, flags, tmp)
+                for m in trainer.models_dict.values():
+                    m.train()
+                batch = next(iter(trainer.device_batches(trainer.train_loader_sensor_b)))
+                for prec in ("bf16", "fp32"):
+                    runs[prec], sizes[prec] = _stepper(trainer, batch, precision=prec), s.batch_size_b
+                    runs[prec](warm)
+            for prec in ("bf16", "fp32") if option != "frame2recon" else ():
                 sub = os.path.join(tmp, prec)
                 os.makedirs(sub)
                 trainer, s = build(yml, option, flags, sub, train_precision=prec)
@@ -138,7 +155,8 @@ if __name__ == "__main__":
     ap.add_argument("--only", nargs="*")
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--precision", choices=("bf16", "fp32"), default="bf16",
-                    help="fp32: the frame2voxel fine-tune / linear-probe steps with train_precision: fp32 next to bf16, interleaved")
+                    help="fp32: the fine-tune / linear-probe steps in fp32 next to bf16, interleaved (frame2voxel: train_precision: "
+                         "fp32; frame2recon: train_step(batch, precision='fp32'))")
     ap.add_argument("--one-stream", action="store_true", help="A/B: OpenESSModel's students on one stream; no frozen-front pipelining in the fine-tune / linear-probe steps")
     a = ap.parse_args()
     if a.one_stream:
