@@ -567,6 +567,24 @@ int oess_bilinear_l2norm_pool_bwd_f32(const float* x, long long x_pix_stride, co
                                       oess_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * L1 consistency of two bilinearly upsampled fp32 maps WITHOUT a full-resolution tensor (K23; training/openess_trainer.py:497 on
+ * the two `feats` of models/deeplabv3.py:184):  loss = mean over B C Ho Wo of |up(a - b)|, a / b [B x h x w x C] fp32 NHWC with
+ * pixel strides >= C (elements), b == NULL: d = a.  `up` is the index rule of oess_resize_bilinear_nhwc_fwd, blended rows first.
+ *   fwd: workspace = oess_upsampled_l1_workspace_bytes(...) bytes, 8-byte aligned (one double per workgroup, summed in a fixed order
+ *        by one block); loss: device scalar.
+ *   bwd: grad_a = grad_out / N * up^T(sign(up(d))), sign(0) = 0, grad_b = -grad_a; either may be NULL (grad_b needs b).
+ *        Gather form, no atomics: bit-repeatable.
+ * Accepted: C % 4 == 0, C <= 1024, Ho >= h, Wo >= w, both align_corners modes, h or w of 1; anything else is OESS_EINVAL.
+ * ------------------------------------------------------------------------------------------ */
+size_t oess_upsampled_l1_workspace_bytes(int B, int h, int w, int C, int Ho, int Wo);
+int oess_upsampled_l1_fwd_f32(const float* a, long long a_pix_stride, const float* b, long long b_pix_stride, int B, int h, int w, int C,
+                              int Ho, int Wo, int align_corners, void* workspace, size_t workspace_bytes, float* loss,
+                              oess_stream_t stream);
+int oess_upsampled_l1_bwd_f32(const float* a, long long a_pix_stride, const float* b, long long b_pix_stride, int B, int h, int w, int C,
+                              int Ho, int Wo, int align_corners, const float* grad_out, float* grad_a, long long ga_pix_stride,
+                              float* grad_b, long long gb_pix_stride, oess_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * Superpixel mean of a bilinearly upsampled map through its pooling matrix (models/deeplabv3.py:184 F.interpolate(feats, size=
  * input, bilinear, align_corners=False) followed by training/pretrain_trainer.py:445-465 on it): k[s] = (sum_q M[s][q] y[q]) /
  * (n[s] + 1e-6) with M[s][q] = the summed bilinear weights of superpixel row s's pixels on low-resolution pixel q.

@@ -119,6 +119,10 @@ SIGNATURES = {
                                                   c_vp, c_sz, c_vp]),
     "oess_bilinear_l2norm_pool_bwd_f32": (c_int, [c_vp, c_ll, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_f,
                                                   c_vp, c_sz, c_vp, c_ll, c_vp]),
+    "oess_upsampled_l1_workspace_bytes": (c_sz, [c_int, c_int, c_int, c_int, c_int, c_int]),
+    "oess_upsampled_l1_fwd_f32": (c_int, [c_vp, c_ll, c_vp, c_ll, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_vp, c_sz, c_vp, c_vp]),
+    "oess_upsampled_l1_bwd_f32": (c_int, [c_vp, c_ll, c_vp, c_ll, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_vp, c_vp, c_ll, c_vp,
+                                          c_ll, c_vp]),
     "oess_pool_matrix_bytes": (c_sz, [c_int, c_int, c_int, c_int]),
     "oess_pool_matrix_build": (c_int, [c_vp, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_vp, c_sz, c_vp]),
     "oess_pool_matrix_fwd": (c_int, [c_vp, c_vp, c_ll, c_int, c_int, c_int, c_int, c_int, c_int, c_vp, c_vp, c_vp]),

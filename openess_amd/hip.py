@@ -1470,6 +1470,61 @@ class UpsampledFeature:
         return _PoolMatrixMean.apply(self.x, matrix, int(S))
 
 
+class _UpsampledL1Mean(torch.autograd.Function):
+    """mean |up(a - b)| of two fp32 low-resolution maps as ONE node: saves the two maps, forms no
+    full-resolution tensor in forward or backward."""
+
+    @staticmethod
+    def forward(ctx, a, b, Ho, Wo, align):
+        lib = _lib.load()
+        an, bn = _nhwc_any(a), _nhwc_any(b)
+        B, h, w, C = an.shape
+        nbytes = lib.oess_upsampled_l1_workspace_bytes(B, h, w, C, Ho, Wo)
+        ws = _workspace(nbytes, a.device, tag="upsampled_l1")
+        loss = torch.empty(1, dtype=torch.float32, device=a.device)
+        _lib.check(lib.oess_upsampled_l1_fwd_f32(_ptr(an), _pix_stride(an), _ptr(bn), _pix_stride(bn), B, h, w, C, Ho, Wo, align,
+                                                 _ptr(ws), ws.numel(), _ptr(loss), _stream()), "oess_upsampled_l1_fwd_f32")
+        ctx.save_for_backward(an, bn)
+        ctx.meta = (Ho, Wo, align)
+        return loss[0]
+
+    @staticmethod
+    def backward(ctx, g):
+        lib = _lib.load()
+        an, bn = ctx.saved_tensors
+        (B, h, w, C), (Ho, Wo, align) = an.shape, ctx.meta
+        ga = torch.empty((B, h, w, C), dtype=torch.float32, device=an.device) if ctx.needs_input_grad[0] else None
+        gb = torch.empty((B, h, w, C), dtype=torch.float32, device=an.device) if ctx.needs_input_grad[1] else None
+        if ga is None and gb is None:
+            return None, None, None, None, None
+        gdev = g.reshape(1).float().contiguous()
+        _lib.check(lib.oess_upsampled_l1_bwd_f32(_ptr(an), _pix_stride(an), _ptr(bn), _pix_stride(bn), B, h, w, C, Ho, Wo, align,
+                                                 _ptr(gdev), _ptr(ga), C, _ptr(gb), C, _stream()), "oess_upsampled_l1_bwd_f32")
+        return (None if ga is None else ga.permute(0, 3, 1, 2)), (None if gb is None else gb.permute(0, 3, 1, 2)), None, None, None
+
+
+def upsampled_l1_supported(C, in_hw, size):
+    """Geometry of the fused fp32 node's entries (include/oess.h, oess_upsampled_l1_*)."""
+    return C % 4 == 0 and C <= 1024 and size[0] >= in_hw[0] and size[1] >= in_hw[1]
+
+
+def upsampled_l1_mean(a, b):
+    """nn.L1Loss()(a, b) (training/openess_trainer.py:497) of two UpsampledFeature operands of equal geometry with fp32 maps, as
+    one autograd node on the low-resolution maps: |up(a) - up(b)| = |up(a - b)| is recomputed element by element in forward and
+    backward, nothing of the full-resolution size is allocated (l1_mean on the same operands writes the upsampled difference
+    and its gradient: 2.3 GB each at 8 x 256 x 440 x 640).  Geometry the entries refuse goes through l1_mean."""
+    if not (isinstance(a, UpsampledFeature) and isinstance(b, UpsampledFeature)):
+        raise TypeError("upsampled_l1_mean takes two hip.UpsampledFeature")
+    if a.size != b.size or a.align_corners != b.align_corners or a.x.shape != b.x.shape:
+        raise ValueError("upsampled_l1_mean: operands differ in geometry")
+    _need_gpu(a.x, b.x)
+    if a.x.dtype != torch.float32 or b.x.dtype != torch.float32 or a.x.ndim != 4:
+        raise ValueError("upsampled_l1_mean: the low-resolution maps must be 4-D float32")
+    if not upsampled_l1_supported(a.x.shape[1], a.x.shape[2:], a.size):
+        return l1_mean(a, b)
+    return _UpsampledL1Mean.apply(a.x, b.x, a.size[0], a.size[1], int(a.align_corners))
+
+
 def bilinear_l2norm_train(x, scale=4):
     """Differentiable form of bilinear_l2norm (normalisation on) for a channels_last bf16 tensor with C % 64 == 0."""
     _need_gpu(x)

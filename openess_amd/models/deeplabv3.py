@@ -295,7 +295,8 @@ class deeplabv3_resnet50(nn.Module):
     def forward_fp32_train(self, x, want_feats=False):
         """forward() of the train-mode network in fp32 with autograd: (logits, feats).  logits: fp32 at the input
         size, through the linear probe when the model has one.  feats: the ASPP feature resized to the input size, formed only
-        when asked for (256 channels at full resolution), otherwise None.  Frozen parameters record nothing: a node whose inputs
+        when asked for (256 channels at full resolution), otherwise None; want_feats='lazy' returns it as hip.UpsampledFeature
+        over the fp32 feature at the network's stride instead (nothing of the full resolution is formed).  Frozen parameters record nothing: a node whose inputs
         need no gradient keeps no graph, the first trainable convolution skips its data gradient.  No buffer, operand or state
         is shared with forward(), except the Dropout module's mask counter (one mask sequence for both)."""
         self.check_fp32_train()
@@ -305,7 +306,14 @@ class deeplabv3_resnet50(nn.Module):
         with engine.defer_bn_counters():
             logist, feats = self.classifier.forward_fp32_autograd(self.backbone.forward_fp32_autograd(x))
         logist = hip.bilinear_resize(logist, size=input_shape, align_corners=False)
-        feats = hip.bilinear_resize(feats, size=input_shape, align_corners=False) if want_feats else None
+        if isinstance(want_feats, str):
+            if want_feats != 'lazy':
+                raise ValueError(f"want_feats must be False, True or 'lazy', got {want_feats!r}")
+            # the consumers pool the map over superpixels and take its L1 distance to another one (OpenESSModel): both work on
+            # the map at the network's stride (hip.UpsampledFeature.pool, hip.upsampled_l1_mean)
+            feats = hip.UpsampledFeature(feats, input_shape, align_corners=False)
+        else:
+            feats = hip.bilinear_resize(feats, size=input_shape, align_corners=False) if want_feats else None
         if self.if_linear_probing:
             logist = hip.linear_probe(logist, self.linear_probe)
         return logist, feats

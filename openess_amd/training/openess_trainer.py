@@ -32,6 +32,17 @@ class OpenESSModel(BaseTrainer):
     # the default stays one stream; the switch and its bit-equality test remain.
     two_streams = False
 
+    def __init__(self, settings, train=True):
+        # `train_precision` / `eval_precision` (optional YAML keys, clip block): arithmetic of train_step / val_step, 'bf16' (storage;
+        # fp32 accumulation) or 'fp32' (the reference's); refused here, before anything is built
+        self.train_precision = getattr(settings, 'train_precision', 'bf16')
+        if self.train_precision not in ('bf16', 'fp32'):
+            raise ValueError(f"train_precision must be 'bf16' or 'fp32', got {self.train_precision!r}")
+        self.eval_precision = getattr(settings, 'eval_precision', 'bf16')
+        if self.eval_precision not in ('bf16', 'fp32'):
+            raise ValueError(f"eval_precision must be 'bf16' or 'fp32', got {self.eval_precision!r}")
+        super().__init__(settings, train)
+
     def init_fn(self):
         """openess_trainer.py:84-86: models, then optimisers, then the loss objects."""
         s = self.settings
@@ -71,12 +82,32 @@ class OpenESSModel(BaseTrainer):
             'optimizer_recon': AdamW([p for p in self.model_recon.parameters() if p.requires_grad], lr=s.lr_recon),
             'optimizer_frame': AdamW([p for p in self.model_frame.parameters() if p.requires_grad], lr=s.lr_frame)}
 
-    def task_train_step(self, batch):
+    def _step_precision(self, precision):
+        """Arithmetic of one training step: `precision`, or the trainer's train_precision for None (the rule of _supervised.py)."""
+        precision = self.train_precision if precision is None else precision
+        if precision not in ('bf16', 'fp32'):
+            raise ValueError(f"precision must be 'bf16' or 'fp32', got {precision!r}")
+        if precision == 'fp32' and self.two_streams:
+            raise NotImplementedError("two_streams with fp32: the fp32 convolution workspaces are kept per stream and the "
+                                      "combination is untested; run the fp32 step on one stream")
+        return precision
+
+    def task_train_step(self, batch, precision=None):
+        """Forward and losses of one step.  precision: 'bf16' / 'fp32' for this call, None for the trainer's train_precision.
+        fp32 (DESIGN.md K23): both students through deeplabv3_resnet50.forward_fp32_train, the same loss nodes on fp32 operands;
+        with lazy_features the L1 consistency is hip.upsampled_l1_mean on the two maps at the network's stride."""
         s = self.settings
+        precision = self._step_precision(precision)
         losses, t_loss = {}, 0.
         for m in self.models_dict.values():
             m.train()
         frame, recon, pl, superpixels = batch[0], batch[2], batch[3], batch[4]
+        if precision == 'fp32':
+            want = 'lazy' if self.lazy_features else True
+            fwd_frame = lambda x: self.model_frame.forward_fp32_train(x, want_feats=want)
+            fwd_recon = lambda x: self.model_recon.forward_fp32_train(x, want_feats=want)
+        else:
+            fwd_frame, fwd_recon = self.model_frame, self.model_recon
         side = None
         if self.two_streams and frame.is_cuda:
             # The two students share no data until the consistency losses.  Their small-map layers (OS16: 140-560 workgroups per
@@ -90,9 +121,9 @@ class OpenESSModel(BaseTrainer):
             side, main = self._side_stream, torch.cuda.current_stream(self.device)
             side.wait_stream(main)
         with torch.cuda.stream(side) if side is not None else contextlib.nullcontext():
-            logits_frame, feat_frame = self.model_frame(frame)
+            logits_frame, feat_frame = fwd_frame(frame)
             l_frame = self.task_loss(logits_frame, pl) * s.weight_task_loss
-        logits_recon, feat_recon = self.model_recon(recon)
+        logits_recon, feat_recon = fwd_recon(recon)
         l_recon = self.task_loss(logits_recon, pl) * s.weight_task_loss
         if side is not None:
             main.wait_stream(side)
@@ -103,7 +134,10 @@ class OpenESSModel(BaseTrainer):
         t_loss = t_loss + l_frame
         losses['semseg_recon_loss'] = l_recon.detach()
         t_loss = t_loss + l_recon
-        l = hip.l1_mean(feat_frame, feat_recon)                              # nn.L1Loss (:497)
+        if precision == 'fp32' and isinstance(feat_frame, hip.UpsampledFeature):
+            l = hip.upsampled_l1_mean(feat_frame, feat_recon)                # nn.L1Loss (:497) without the 2.3 GB difference
+        else:
+            l = hip.l1_mean(feat_frame, feat_recon)                          # nn.L1Loss (:497)
         losses['cons_feat_loss'] = l.detach()
         t_loss = t_loss + l
         l = hip.cosine_mean_loss(logits_frame, logits_recon)                 # mean(1 - cosine_similarity) (:501)
@@ -129,19 +163,38 @@ class OpenESSModel(BaseTrainer):
             t_loss = t_loss + l
         return t_loss, losses, {}
 
-    def train_step(self, batch):
+    def train_step(self, batch, precision=None):
+        precision = self._step_precision(precision)      # refused before the gradients are cleared
         for opt in self.optimizers_dict.values():
             opt.zero_grad()
         self.grad_reducer.prepare()
-        t_loss, losses, outputs = self.task_train_step(batch)
+        t_loss, losses, outputs = self.task_train_step(batch, precision=precision)
         t_loss.backward()
         self.grad_reducer()
         for opt in self.optimizers_dict.values():
             opt.step()
         return losses, outputs, t_loss.detach()
 
+    def val_logits(self, batch, precision=None):
+        """Class logits of one validation batch in `precision` (default: the trainer's eval_precision).  'fp32' runs
+        deeplabv3_resnet50.forward_fp32 on the eval-mode network and puts the modules' train / eval flags back (the rule of
+        SupervisedTrainer.val_logits); it shares no state with the bf16 path or the training step."""
+        precision = self.eval_precision if precision is None else precision
+        if precision not in ('bf16', 'fp32'):
+            raise ValueError(f"precision must be 'bf16' or 'fp32', got {precision!r}")
+        model = self.models_dict['model_recon']
+        if precision == 'bf16':
+            return model(batch[2])[0]
+        modes = [(m, m.training) for m in model.modules()]
+        model.eval()
+        try:
+            return model.forward_fp32(batch[2])[0]
+        finally:
+            for m, training in modes:
+                m.training = training
+
     def val_step(self, batch, sensor, i_batch, vis_reconstr_idx, file_path):
-        pred, _ = self.models_dict['model_recon'](batch[2])
+        pred = self.val_logits(batch)
         losses = {'semseg_' + sensor + '_loss': self.task_loss(pred, batch[1]).detach()}
         self.metrics_semseg_b.update_batch(pred.argmax(dim=1), batch[1])
         return losses, None

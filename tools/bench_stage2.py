@@ -6,7 +6,7 @@ outside the timed region) and `train_step` is timed on it between synchronize fe
 --precision fp32: the fine-tune and linear-probe steps of the event branch (frame2voxel) with `train_precision: fp32` (K19) next
 to the bf16 step in the same run, interleaved (bf16, fp32, bf16, ... three rounds, the median of each), and their ratio; and the
 same two steps of frame2recon (K22), where ONE trainer runs both through `train_step(batch, precision=...)` (the YAML key refuses
-frame2recon at construction).
+frame2recon at construction); and the joint stage openess_frame2recon_contrastive (K23) the same way, on one OpenESSModel.
     python tools/bench_stage2.py [--steps 20] [--precision fp32]"""
 import argparse
 import json
@@ -83,7 +83,7 @@ def measure_precisions(steps=20, warm=3, only=None, rounds=3):
     """fp32 next to bf16: both trainers of a case are built, then timed in turn, `rounds` times; the median round of each."""
     out = {}
     for name, yml, option, flags in CASES:
-        if name.startswith("openess") or (only and name not in only):
+        if only and name not in only:
             continue
         with tempfile.TemporaryDirectory(prefix="oess_stage2_", dir="/tmp") as tmp:
             runs, sizes, loss = {}, {}, {}
@@ -155,8 +155,8 @@ if __name__ == "__main__":
     ap.add_argument("--only", nargs="*")
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--precision", choices=("bf16", "fp32"), default="bf16",
-                    help="fp32: the fine-tune / linear-probe steps in fp32 next to bf16, interleaved (frame2voxel: train_precision: "
-                         "fp32; frame2recon: train_step(batch, precision='fp32'))")
+                    help="fp32: the fine-tune / linear-probe / joint steps in fp32 next to bf16, interleaved (frame2voxel: "
+                         "train_precision: fp32; frame2recon: train_step(batch, precision='fp32'))")
     ap.add_argument("--one-stream", action="store_true", help="A/B: OpenESSModel's students on one stream; no frozen-front pipelining in the fine-tune / linear-probe steps")
     a = ap.parse_args()
     if a.one_stream:
