@@ -884,6 +884,38 @@ int oess_aspp_pool_bwd_f32o(const float* grad_z, const float* pooled, float in_s
                             const float* stat, const float* z, int B, int Cin, int Cout, float* dy_scratch, float* grad_w,
                             float* grad_gamma, float* grad_beta, float* grad_pooled, oess_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------
+ * K24 SLIC superpixels (data_preparation/superpixel_segmenter_dsec_slic.py:19-24 of the reference:
+ * skimage.segmentation.slic(img, n_segments, compactness=6, sigma=3.0, start_label=0), here without the connectivity pass).
+ * Additions only: the ABI version stays.  fp32, no floating-point atomics: every result repeats bit for bit.
+ * A centre is five floats (y, x, L, a, b); centre k = i nx + j of the ny x nx lattice.
+ *
+ * oess_slic_lab_f32 (superpixel_segmenter_dsec_slic.py:19-24): frames, a B x H x W x 3 view with any strides -> lab, dense
+ *   [B, H, W, 3]: per channel a separable Gaussian blur (radius int(4 sigma + 0.5), taps exp(-x^2 / 2 sigma^2) normalised to sum
+ *   1, border rule reflect: d c b a | a b c d), skimage's sRGB -> CIELAB (D65, 2 degrees), one multiply by 1 / compactness.
+ *   centers (nullable): [B, ny nx, 5], centre (i, j) at y = floor((i + 0.5) H / ny), x = floor((j + 0.5) W / nx) with the map's
+ *   value there.  OESS_EINVAL before any launch: a null pointer, sigma <= 0 or > 6, compactness <= 0, min(H, W) < radius + 1,
+ *   H W > 2^24, with centers a lattice outside 1 <= ny <= H, 1 <= nx <= W, ny nx <= 256.
+ * oess_slic_assign_f32 (superpixel_segmenter_dsec_slic.py:19-24): one assignment pass.  Pixel (y, x) is eligible for centre k
+ *   iff int(max(cy - 2 step, 0)) <= y < int(min(cy + 2 step + 1, H)) and the same in x; its distance is
+ *   ((y - cy)^2 + (x - cx)^2) (1 / step^2) + sum_c (lab_c - colour_c)^2; the lowest wins, ties go to the lowest k, a pixel
+ *   eligible for no centre keeps prev_labels' entry.  prev_labels NULL: the index of the pixel's lattice cell,
+ *   (y ny / H) nx + x nx / W, and ny nx must be K.  labels may be prev_labels.  OESS_EINVAL: a null pointer, K outside
+ *   [1, 256], step < 1, H W > 2^24.
+ * oess_slic_update_f32 (superpixel_segmenter_dsec_slic.py:19-24): new_centers[b, k] = the mean (y, x, L, a, b) of the pixels
+ *   labelled k, centers[b, k] for a label no pixel carries (new_centers may be centers); labels outside [0, K) are skipped.
+ *   counts (nullable): int [B, K], the pixels of every centre.
+ *   Integer sums for the count, y and x, 2^-32 fixed point in 64-bit integers for L, a, b (a value is clamped to |v| <= 64
+ *   first: below 2^62 over the 2^24 pixels allowed), a mean is the float64 quotient of sum and count rounded to fp32.  workspace: B K 48 bytes,
+ *   8-byte aligned, zeroed by the call; smaller is OESS_ENOMEM.
+ * ------------------------------------------------------------------------------------------ */
+int oess_slic_lab_f32(const oess_f32_view_t* frames, int B, int H, int W, float sigma, float compactness, float* lab, int ny, int nx,
+                      float* centers, oess_stream_t stream);
+int oess_slic_assign_f32(const float* lab, const float* centers, const int64_t* prev_labels, int B, int H, int W, int K, int step, int ny,
+                         int nx, int64_t* labels, oess_stream_t stream);
+int oess_slic_update_f32(const float* lab, const int64_t* labels, const float* centers, int B, int H, int W, int K, float* new_centers,
+                         int* counts, void* workspace, size_t workspace_bytes, oess_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

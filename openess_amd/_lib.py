@@ -198,6 +198,9 @@ SIGNATURES = {
     "oess_dropout_f32": (c_int, [c_view, c_view, c_int, c_int, c_int, c_int, c_f, c_u64, c_u64, c_vp]),
     "oess_aspp_pool_bwd_f32o": (c_int, [c_vp, c_vp, c_f, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_vp,
                                         c_vp]),
+    "oess_slic_lab_f32": (c_int, [c_view, c_int, c_int, c_int, c_f, c_f, c_vp, c_int, c_int, c_vp, c_vp]),
+    "oess_slic_assign_f32": (c_int, [c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_vp, c_vp]),
+    "oess_slic_update_f32": (c_int, [c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_vp, c_vp, c_vp, c_sz, c_vp]),
 }
 
 _lib = None

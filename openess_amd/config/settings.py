@@ -6,6 +6,8 @@ OPENESS_ALLOW_MISSING_DATA=1) selects the synthetic provider instead of failing 
 (settings.py:117); `generate_log=False` creates nothing on disk, exactly like the reference.
 `eval_precision: fp32` in the `clip:` block (next to `use_amp`) validates the stage-2/3 event networks in fp32;
 `train_precision: fp32` next to it trains them in fp32 (frozen E2VID + SemSegE2VID decoder).
+`superpixel_sources: 'online_slic'` (with the optional `online_slic_segments`) computes the contrastive stage's superpixels
+from the frame on the GPU instead of reading a directory of maps.
 Quirk reproduced on purpose: `if_linear_probing` is read from the `clip:` block only (settings.py:258), so the
 reference's config/linear_probe/** files, which put it at top level, dispatch to OpenESSModel.
 """
@@ -42,6 +44,16 @@ _DATASET_BLOCK = {'DSEC_events': 'DSEC_events', 'DDD17_events': 'DDD17_events', 
 
 _OPTIM = (('batch_size_b', int), ('lr_voxel', float), ('lr_recon', float), ('lr_frame', float), ('lr_decay', float),
           ('num_epochs', int), ('val_epoch_step', int), ('weight_task_loss', float))
+
+
+ONLINE_SLIC = 'online_slic'
+
+
+def dataset_superpixel_sources(settings):
+    """What the TRAIN dataset is built with: `superpixel_sources`, or '' (the ones-map, no file is looked up) when the
+    superpixels are computed online."""
+    src = getattr(settings, 'superpixel_sources', '')
+    return '' if src == ONLINE_SLIC else src
 
 
 class Settings:
@@ -154,6 +166,11 @@ class Settings:
             for key in ('image_weights', 'if_spatial_contrastive', 'superpixel_sources', 'superpixel_size',
                         'if_dense_clip_supervision', 'pl_sources', 'if_sam_distillation'):
                 setattr(self, key, c[key])
+            # `superpixel_sources: 'online_slic'`: the superpixels are computed from the frame on the GPU in the
+            # trainer's prepare_batch; `online_slic_segments` is SLIC's n_segments (None: the trainer's pooling size)
+            self.online_slic_segments = c.get('online_slic_segments')
+            if self.online_slic_segments is not None:
+                self.online_slic_segments = int(self.online_slic_segments)
         if c.get('if_finetuning') is not None:
             self.if_finetuning = c['if_finetuning']
             for key in ('load_pretrained_weights', 'pretrained_file', 'if_switchable_train'):

@@ -5,6 +5,7 @@ calls with the reference's argument mapping (training/base_trainer_ov.py:93-160,
 from pathlib import Path
 
 from ..DSEC.dataset.provider import DatasetProvider
+from ..config.settings import dataset_superpixel_sources
 
 
 def DSECEvents(dsec_dir, nr_events_data=1, delta_t_per_data=50, nr_events_window=-1, augmentation=False, mode='train',
@@ -31,7 +32,7 @@ def build_from_settings(s):
               semseg_num_classes=s.semseg_num_classes, fixed_duration=s.fixed_duration_b, config_option=s.config_option,
               pl_sources=getattr(s, 'pl_sources', ''), device_png=getattr(s, 'device_png_decode', False))
     train = DSECEvents(augmentation=s.data_augmentation_train, mode='train', require_paired_data=s.require_paired_data_train_b,
-                       superpixel_sources=getattr(s, 'superpixel_sources', ''), skip_ratio=s.skip_ratio,
+                       superpixel_sources=dataset_superpixel_sources(s), skip_ratio=s.skip_ratio,
                        if_sam_distillation=getattr(s, 'if_sam_distillation', False), **kw)
     val = DSECEvents(augmentation=False, mode='val', require_paired_data=s.require_paired_data_val_b, superpixel_sources='',
                      skip_ratio=2, if_sam_distillation=False, **kw)

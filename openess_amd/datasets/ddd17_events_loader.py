@@ -20,6 +20,7 @@ import torch.nn.functional as f
 from torch.utils.data import Dataset
 
 from .. import hip
+from ..config.settings import dataset_superpixel_sources
 from . import _io
 
 
@@ -228,7 +229,7 @@ class DDD17Events(Dataset):
                   delta_t_per_data=s.delta_t_per_data_b, nr_bins_per_data=s.nr_temporal_bins_b, separate_pol=s.separate_pol_b,
                   normalize_event=s.normalize_event_b, fixed_duration=s.fixed_duration_b, nr_events_per_data=s.nr_events_window_b,
                   config_option=s.config_option, pl_sources=getattr(s, 'pl_sources', ''),
-                  superpixel_sources=getattr(s, 'superpixel_sources', ''), skip_ratio=s.skip_ratio,
+                  superpixel_sources=dataset_superpixel_sources(s), skip_ratio=s.skip_ratio,
                   if_sam_distillation=getattr(s, 'if_sam_distillation', False))
         train = cls(s.dataset_path_b, split=s.split_train_b, augmentation=s.data_augmentation_train,
                     require_paired_data=s.require_paired_data_train_b, **kw)

@@ -15,11 +15,13 @@ from . import _synth
 
 class SyntheticEvents(Dataset):
     def __init__(self, length=16, sensor_hw=(480, 640), crop_rows=40, nr_events_data=20, nr_events_window=100000,
-                 nr_bins=5, num_classes=11, config_option='frame2voxel', superpixel_size=100, mode='train', seed=1205, pool=0):
+                 nr_bins=5, num_classes=11, config_option='frame2voxel', superpixel_size=100, mode='train', seed=1205, pool=0,
+                 superpixel_sources=None):
         self.length, self.sensor_hw, self.crop_rows = length, tuple(sensor_hw), crop_rows
         self.nr_events_data, self.nr_events_window, self.nr_bins = nr_events_data, nr_events_window, nr_bins
         self.num_classes, self.config_option, self.superpixel_size = num_classes, config_option, superpixel_size
         self.mode, self.seed = mode, seed
+        self.superpixel_sources = superpixel_sources       # None: the g x g grid below; '': the ones-map of an empty source
         self.require_paired_data = False
         self.rectify_map = _synth.rectify_map(*self.sensor_hw)
         # pool > 0: `pool` distinct samples are generated ONCE here (before the DataLoader forks its workers: the arrays are
@@ -57,6 +59,8 @@ class SyntheticEvents(Dataset):
         yy = (np.arange(Hn) * g // Hn)[:, None]
         xx = (np.arange(W) * g // W)[None, :]
         superpixel = torch.from_numpy((yy * g + xx).astype(np.int64))
+        if self.superpixel_sources == '':
+            superpixel = torch.ones_like(label)
         sam_feat = torch.ones(256, 64, 64)
         first = events if self.config_option in ('frame2voxel', 'recon2voxel') else frame
         return first, label, frame, pl, superpixel, sam_feat, f"synthetic/{self.mode}/{index:06d}"

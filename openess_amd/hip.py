@@ -2845,3 +2845,154 @@ def aspp_pool_branch_f32(x, conv, bn):
     y = _ASPPPoolBranchF32.apply(x, w, bn.weight, bn.bias, bn.running_mean, bn.running_var, float(bn.momentum), float(bn.eps))
     _engine.bump_bn_counter(bn)
     return y
+
+
+# ------------------------------------------------------------------------------------------ K24: SLIC superpixels
+SLIC_MAX_CENTERS = 256
+
+
+def slic_lattice(H, W, n_segments):
+    """Centre lattice of hip.slic_superpixels, a pure host function: (ny, nx, step) with s = sqrt(H W / n_segments),
+    ny = max(1, floor(H / s)), nx = max(1, floor(W / s)) and step = max(ceil(H / ny), ceil(W / nx)).  K = ny nx <= n_segments
+    whenever s <= min(H, W); 440 x 640 with n = 100 gives 8 x 12 = 96 centres and step 55."""
+    import math
+    H, W, n_segments = int(H), int(W), int(n_segments)
+    if H < 1 or W < 1 or n_segments < 1:
+        raise ValueError(f"slic_lattice needs H, W, n_segments >= 1, got {(H, W, n_segments)}")
+    s = math.sqrt(H * W / n_segments)
+    ny, nx = max(1, int(math.floor(H / s))), max(1, int(math.floor(W / s)))
+    return ny, nx, max(-(-H // ny), -(-W // nx))
+
+
+def _slic_blur_radius(sigma):
+    return int(4.0 * float(sigma) + 0.5)
+
+
+def _slic_check_lab(lab, what="lab"):
+    if not torch.is_tensor(lab) or lab.dtype != torch.float32 or lab.ndim != 4 or lab.shape[-1] != 3 or not lab.is_contiguous():
+        raise ValueError(f"{what} must be a contiguous float32 tensor [B, H, W, 3]")
+    B, H, W, _ = lab.shape
+    if B < 1 or H * W < 1 or H * W > (1 << 24):
+        raise ValueError(f"{what}: B >= 1 and 1 <= H W <= 2^24 are needed, got {tuple(lab.shape)}")
+    return B, H, W
+
+
+def _slic_check_centers(centers, B, what="centers"):
+    if not torch.is_tensor(centers) or centers.dtype != torch.float32 or centers.ndim != 3 or centers.shape[0] != B \
+            or centers.shape[2] != 5 or not centers.is_contiguous():
+        raise ValueError(f"{what} must be a contiguous float32 tensor [{B}, K, 5] of (y, x, L, a, b)")
+    K = centers.shape[1]
+    if not 1 <= K <= SLIC_MAX_CENTERS:
+        raise ValueError(f"{what}: 1 <= K <= {SLIC_MAX_CENTERS} centres are served, got {K}")
+    return K
+
+
+def _slic_check_labels(labels, B, H, W, what):
+    if not torch.is_tensor(labels) or labels.dtype != torch.int64 or tuple(labels.shape) != (B, H, W) or not labels.is_contiguous():
+        raise ValueError(f"{what} must be a contiguous int64 tensor {(B, H, W)}")
+
+
+def slic_lab(frames, sigma=3.0, compactness=6.0, lattice=None):
+    """First pass of SLIC (oess_slic_lab_f32): frames, logical [B, 3, H, W] fp32 with any strides (values nominally in [0, 1]) ->
+    the blurred CIELAB map scaled by 1 / compactness, contiguous fp32 [B, H, W, 3].  Gaussian of radius int(4 sigma + 0.5), border
+    rule reflect.  lattice = (ny, nx): also returns the starting centres [B, ny nx, 5] = (y, x, L, a, b) at the lattice pixels."""
+    if not torch.is_tensor(frames) or frames.dtype != torch.float32 or frames.ndim != 4 or frames.shape[1] != 3:
+        raise ValueError("frames must be a 4-D float32 tensor [B, 3, H, W]")
+    sigma, compactness = float(sigma), float(compactness)
+    if not sigma > 0.0 or not sigma <= 6.0:
+        raise ValueError(f"slic: 0 < sigma <= 6 is needed, got {sigma}")
+    if not compactness > 0.0:
+        raise ValueError(f"slic: compactness > 0 is needed, got {compactness}")
+    B, _, H, W = frames.shape
+    R = _slic_blur_radius(sigma)
+    if min(H, W) < R + 1:
+        raise ValueError(f"slic: min(H, W) >= {R + 1} is needed (one reflection must cover the blur radius {R}), got {H} x {W}")
+    if B < 1 or H * W > (1 << 24):
+        raise ValueError(f"slic: B >= 1 and H W <= 2^24 are needed, got {tuple(frames.shape)}")
+    ny = nx = 0
+    if lattice is not None:
+        ny, nx = int(lattice[0]), int(lattice[1])
+        if not (1 <= ny <= H and 1 <= nx <= W):
+            raise ValueError(f"slic: a {ny} x {nx} lattice does not fit a {H} x {W} frame")
+        if ny * nx > SLIC_MAX_CENTERS:
+            raise ValueError(f"slic: K = {ny} x {nx} = {ny * nx} centres, at most {SLIC_MAX_CENTERS} are served")
+    _need_gpu(frames)
+    lib = _lib.load()
+    vf = _f32_view(frames, "frames")
+    lab = torch.empty((B, H, W, 3), dtype=torch.float32, device=frames.device)
+    centers = torch.empty((B, ny * nx, 5), dtype=torch.float32, device=frames.device) if lattice is not None else None
+    _lib.check(lib.oess_slic_lab_f32(ctypes.byref(vf), B, H, W, sigma, compactness, _ptr(lab), ny, nx, _ptr(centers), _stream()),
+               "oess_slic_lab_f32")
+    return lab if lattice is None else (lab, centers)
+
+
+def slic_assign(lab, centers, prev_labels, step, lattice=None, out=None):
+    """One assignment pass of SLIC (oess_slic_assign_f32): lab [B, H, W, 3] and centers [B, K, 5] fp32, prev_labels int64
+    [B, H, W] -> int64 labels [B, H, W].  A pixel is eligible for the centres within 2 step of it (the rule of include/oess.h),
+    the lowest distance wins, ties go to the lowest k and a pixel eligible for none keeps its previous label.  prev_labels None
+    with lattice = (ny, nx), ny nx = K: every pixel starts with the index of its lattice cell.  out may be prev_labels."""
+    B, H, W = _slic_check_lab(lab)
+    K = _slic_check_centers(centers, B)
+    step = int(step)
+    if step < 1:
+        raise ValueError(f"slic_assign: step >= 1 is needed, got {step}")
+    ny = nx = 0
+    if prev_labels is None:
+        if lattice is None or int(lattice[0]) * int(lattice[1]) != K or min(int(lattice[0]), int(lattice[1])) < 1:
+            raise ValueError(f"slic_assign: without prev_labels a lattice (ny, nx) with ny nx = K = {K} is needed, got {lattice}")
+        ny, nx = int(lattice[0]), int(lattice[1])
+    else:
+        _slic_check_labels(prev_labels, B, H, W, "prev_labels")
+    if out is not None:
+        _slic_check_labels(out, B, H, W, "out")
+    _need_gpu(lab, centers, prev_labels, out)
+    lib = _lib.load()
+    if out is None:
+        out = torch.empty((B, H, W), dtype=torch.int64, device=lab.device)
+    _lib.check(lib.oess_slic_assign_f32(_ptr(lab), _ptr(centers), _ptr(prev_labels), B, H, W, K, step, ny, nx, _ptr(out), _stream()),
+               "oess_slic_assign_f32")
+    _bump(out)
+    return out
+
+
+def slic_update(lab, labels, centers, out=None, return_counts=False):
+    """One update pass of SLIC (oess_slic_update_f32): each centre becomes the mean (y, x, L, a, b) of its pixels, an empty centre
+    stays.  Integer and 2^-32 fixed-point sums (no floating-point atomics): bit-repeatable; a position is
+    the float64 quotient of an exact integer sum and the count, rounded to fp32.  Returns new centres [B, K, 5] (out may be centers), with return_counts also the int32 [B, K] pixel counts."""
+    B, H, W = _slic_check_lab(lab)
+    K = _slic_check_centers(centers, B)
+    _slic_check_labels(labels, B, H, W, "labels")
+    if out is not None and _slic_check_centers(out, B, "out") != K:
+        raise ValueError(f"out must have the shape of centers {tuple(centers.shape)}")
+    _need_gpu(lab, labels, centers, out)
+    lib = _lib.load()
+    if out is None:
+        out = torch.empty_like(centers)
+    ws = _workspace(B * K * 48, lab.device, tag="slic")
+    counts = torch.empty((B, K), dtype=torch.int32, device=lab.device) if return_counts else None
+    _lib.check(lib.oess_slic_update_f32(_ptr(lab), _ptr(labels), _ptr(centers), B, H, W, K, _ptr(out), _ptr(counts), _ptr(ws), ws.numel(),
+                                        _stream()), "oess_slic_update_f32")
+    _bump(out)
+    return (out, counts) if return_counts else out
+
+
+def slic_superpixels(frames, n_segments, compactness=6.0, sigma=3.0, iters=10, return_centers=False):
+    """SLIC superpixels of a batch of frames on the GPU (K24; the reference's offline
+    skimage.segmentation.slic(img, n_segments, compactness=6, sigma=3.0, start_label=0) without its connectivity pass):
+    frames [B, 3, H, W] fp32 -> int64 labels [B, H, W] in [0, K), K = ny nx of hip.slic_lattice (K <= 256).  Exactly `iters`
+    assignment + update rounds on the current stream, no early exit and no read-back; two calls give the same bits."""
+    if not torch.is_tensor(frames) or frames.dtype != torch.float32 or frames.ndim != 4 or frames.shape[1] != 3:
+        raise ValueError("frames must be a 4-D float32 tensor [B, 3, H, W]")
+    iters = int(iters)
+    if iters < 1:
+        raise ValueError(f"slic_superpixels: iters >= 1 is needed, got {iters}")
+    H, W = frames.shape[2], frames.shape[3]
+    ny, nx, step = slic_lattice(H, W, n_segments)
+    if ny * nx > SLIC_MAX_CENTERS:
+        raise ValueError(f"slic: K = {ny} x {nx} = {ny * nx} centres, at most {SLIC_MAX_CENTERS} are served")
+    lab, centers = slic_lab(frames, sigma, compactness, lattice=(ny, nx))
+    labels = None
+    for _ in range(iters):
+        labels = slic_assign(lab, centers, labels, step, lattice=(ny, nx), out=labels)
+        centers = slic_update(lab, labels, centers, out=centers)
+    return (labels, centers) if return_centers else labels

@@ -13,17 +13,38 @@ import torch.distributed as dist
 from torch.utils.data import DataLoader, Subset
 
 from .. import hip
+from ..config.settings import ONLINE_SLIC, dataset_superpixel_sources
 from ..evaluation.metrics import MetricsSemseg
 from ..utils.saver import CheckpointSaver
 from .ddp import GradAllReduce, broadcast_module_states, shard_indices
 
 
+def online_slic_segments(settings, pool_size):
+    """`superpixel_sources: 'online_slic'`: SLIC's n_segments for this run, None for every other source.  The
+    refusals of the key: recon2voxel has no RGB frame to segment, and more segments than the pooling size would let one sample's
+    ids run into the next sample's rows."""
+    if getattr(settings, 'superpixel_sources', '') != ONLINE_SLIC:
+        return None
+    if settings.config_option == 'recon2voxel':
+        raise ValueError("superpixel_sources: online_slic needs an RGB frame in the batch (config_option frame2voxel or frame2recon); "
+                         "recon2voxel has none")
+    n = getattr(settings, 'online_slic_segments', None)
+    n = int(pool_size) if n is None else int(n)
+    if n < 1 or n > pool_size:
+        raise ValueError(f"online_slic_segments = {n} must be between 1 and the pooling size {pool_size} (superpixel_size): the "
+                         f"pooling offsets sample b's ids by b * {pool_size}")
+    return n
+
+
 class BaseTrainer(object):
     is_training = True
+    online_slic_segments = None      # SLIC's n_segments under `superpixel_sources: online_slic`, set by __init__
 
     def __init__(self, settings, train=True):
         self.settings = settings
         self.is_training = bool(train)           # reference: every trainer's __init__(settings, train=True) (pretrain_trainer.py:82-83)
+        # before anything is built: what `superpixel_sources: online_slic` cannot serve is refused here
+        self.online_slic_segments = online_slic_segments(settings, self.pooling_size())
         if not torch.cuda.is_available():
             raise RuntimeError("openess_amd trainers need the GPU (no CPU fallback in the product path)")
         self.device = torch.device('cuda', torch.cuda.current_device())
@@ -73,6 +94,10 @@ class BaseTrainer(object):
         total_steps = settings.num_epochs * len(self.train_loader_sensor_b)
         self.lr_schedulers = {k: torch.optim.lr_scheduler.CosineAnnealingLR(v, T_max=max(total_steps, 1))
                               for k, v in self.optimizers_dict.items()}
+
+    def pooling_size(self):
+        """Rows per sample of the superpixel pooling: OpenESSModel pools with its own hard-coded size."""
+        return getattr(self, 'pool_superpixel_size', None) or getattr(self.settings, 'superpixel_size', 100)
 
     @staticmethod
     def rank_hint():
@@ -230,21 +255,22 @@ class BaseTrainer(object):
                           num_classes=s.semseg_num_classes, config_option=s.config_option,
                           superpixel_size=getattr(s, 'superpixel_size', 100))
             n_train = getattr(s, 'synthetic_length', 2 * s.batch_size_b * self.world)
-            train_ds = builder(length=n_train, mode='train', pool=getattr(s, 'synthetic_pool', 0), **common)
+            train_ds = builder(length=n_train, mode='train', pool=getattr(s, 'synthetic_pool', 0),
+                               superpixel_sources='' if self.online_slic_segments else None, **common)
             val_ds = builder(length=max(s.batch_size_b, 2), mode='val', **common)
         elif s.dataset_name_b == 'DSEC_events':
             train_ds, val_ds = self.createDSECDataset(
                 s.dataset_name_b, s.dataset_path_b, s.batch_size_b, s.nr_events_data_b, s.delta_t_per_data_b, s.nr_events_window_b,
                 s.data_augmentation_train, s.event_representation_b, s.nr_temporal_bins_b, s.require_paired_data_train_b,
                 s.require_paired_data_val_b, s.separate_pol_b, s.normalize_event_b, s.semseg_num_classes, s.fixed_duration_b,
-                s.config_option, getattr(s, 'pl_sources', ''), getattr(s, 'superpixel_sources', ''), s.skip_ratio,
+                s.config_option, getattr(s, 'pl_sources', ''), dataset_superpixel_sources(s), s.skip_ratio,
                 getattr(s, 'if_sam_distillation', False))
         else:
             train_ds, val_ds = self.createDDD17EventsDataset(
                 s.dataset_name_b, s.dataset_path_b, s.split_train_b, s.batch_size_b, s.nr_events_data_b, s.delta_t_per_data_b,
                 s.nr_events_window_b, s.data_augmentation_train, s.event_representation_b, s.nr_temporal_bins_b,
                 s.require_paired_data_train_b, s.require_paired_data_val_b, s.separate_pol_b, s.normalize_event_b, s.fixed_duration_b,
-                s.config_option, getattr(s, 'pl_sources', ''), getattr(s, 'superpixel_sources', ''), s.skip_ratio,
+                s.config_option, getattr(s, 'pl_sources', ''), dataset_superpixel_sources(s), s.skip_ratio,
                 getattr(s, 'if_sam_distillation', False))
         self.sensor_geometry = (train_ds.sensor_hw, train_ds.crop_rows) if hasattr(train_ds, 'sensor_hw') else None
         self.rectify_maps = torch.from_numpy(train_ds.rectify_map[None]).to(self.device) if hasattr(train_ds, 'rectify_map') else None
@@ -345,9 +371,21 @@ class BaseTrainer(object):
             first = hip.h2d_async(first, self.device)
         sp = rest[3] if len(rest) > 3 and torch.is_tensor(rest[3]) else None
         S = None
-        if sp is not None and getattr(s, 'if_spatial_contrastive', False):
+        if self.online_slic_segments and split == 'train' and getattr(s, 'if_spatial_contrastive', False):
+            # superpixel_sources: online_slic (K24): SLIC of the frame the step sees (already flipped and augmented on the host), on
+            # this stream -- the ingest stream, under the previous step.  Labels are 0 .. K - 1 with K from the shapes alone, so
+            # the row count needs no read-back
+            frame = first if s.config_option == 'frame2recon' else rest[1]
+            sps = self.pooling_size()
+            ny, nx, _ = hip.slic_lattice(frame.shape[2], frame.shape[3], self.online_slic_segments)
+            if ny * nx > sps:
+                raise ValueError(f"online_slic: a {tuple(frame.shape[2:])} frame with {self.online_slic_segments} segments gives "
+                                 f"{ny * nx} centres, more than the pooling size {sps}")
+            rest[3] = hip.slic_superpixels(frame, self.online_slic_segments)
+            S = (frame.shape[0] - 1) * sps + ny * nx
+        elif sp is not None and getattr(s, 'if_spatial_contrastive', False):
             # host-side row count: no device sync in the step (OpenESSModel pools with its own hard-coded size)
-            sps = getattr(self, 'pool_superpixel_size', None) or getattr(s, 'superpixel_size', 100)
+            sps = self.pooling_size()
             if torch.is_tensor(sample_batched[4]):
                 S = int((sample_batched[4] + torch.arange(sample_batched[4].shape[0])[:, None, None] * sps).max()) + 1
             else:

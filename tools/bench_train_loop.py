@@ -3,7 +3,7 @@
 DataLoader worker processes -> collate (raw event columns, 13 B/event) -> pin thread -> H2D copies + batched HIP voxelizer on
 the side stream (BaseTrainer.device_batches) -> train_step.  This is the loop SURVEY 8e names as the weak-scaling limiter;
 bench.py reports its rate beside the headline (`train_loop`), never as `value`.
-    python tools/bench_train_loop.py [--batches 24] [--workers 10] [--no-prefetch] [--json]
+    python tools/bench_train_loop.py [--batches 24] [--workers 10] [--no-prefetch] [--json] [--contrastive | --online-slic]
 The synthetic dataset serves a pool of 16 pre-generated event-frames (workers copy them like a memory-mapped recording).
 A batch is 208 MB of raw columns that a worker copies, collates and hands over through shared memory: 6 workers deliver one batch
 per ~60 ms, 10 or 16 one per ~47 ms = the step time (measured: 134.6 / 168.6 / 168.6 event-frames/s), hence the default of 10."""
@@ -21,7 +21,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 
-def build(batches, workers, prefetch, B=8, contrastive=False, tmp=None, ring=True):
+def build(batches, workers, prefetch, B=8, contrastive=False, tmp=None, ring=True, online_slic=False):
     import train
     from openess_amd.config.settings import Settings
     cfg = yaml.safe_load(open(os.path.join(ROOT, "tests", "configs", "pretrain_dsec_synthetic.yaml")))
@@ -30,6 +30,8 @@ def build(batches, workers, prefetch, B=8, contrastive=False, tmp=None, ring=Tru
     cfg['optim'].update(batch_size_b=B, num_epochs=1)
     cfg['hardware']['num_cpu_workers'] = workers
     cfg['clip'].update(if_spatial_contrastive=contrastive, superpixel_size=100)
+    if online_slic:                                # the superpixels from the frame on the ingest stream
+        cfg['clip'].update(superpixel_sources='online_slic')
     cfg['checkpoint']['save_checkpoint'] = False
     cfg['dir']['log'] = tmp
     path = os.path.join(tmp, "train_loop.yaml")
@@ -46,9 +48,9 @@ def build(batches, workers, prefetch, B=8, contrastive=False, tmp=None, ring=Tru
     return trainer, s
 
 
-def measure(batches=24, workers=4, prefetch=True, warm=4, ring=True, pipeline=True):
+def measure(batches=24, workers=4, prefetch=True, warm=4, ring=True, pipeline=True, contrastive=False, online_slic=False):
     with tempfile.TemporaryDirectory(prefix="oess_loop_", dir="/tmp") as tmp:
-        trainer, s = build(batches + warm, workers, prefetch, tmp=tmp, ring=ring)
+        trainer, s = build(batches + warm, workers, prefetch, tmp=tmp, ring=ring, contrastive=contrastive or online_slic, online_slic=online_slic)
         for m in trainer.models_dict.values():
             m.train()
         B = s.batch_size_b
@@ -81,7 +83,8 @@ def measure(batches=24, workers=4, prefetch=True, warm=4, ring=True, pipeline=Tr
         if hasattr(loader, "close"):
             loader.close()
         return {"value": round(n * B / dt, 2), "unit": "event-frames/s", "ms_per_step": round(dt / n * 1e3, 3), "steps": n,
-                "loader_workers": workers, "prefetch": bool(prefetch), "loader": kind, "pipelined_steps": bool(pipeline),
+                "loader_workers": workers, "prefetch": bool(prefetch),
+                **({"contrastive": True, "superpixels": "online_slic" if online_slic else "synthetic grid"} if contrastive or online_slic else {}), "loader": kind, "pipelined_steps": bool(pipeline),
                 "note": "train.py's own loop: DataLoader workers -> collate (13 B/event raw columns, 208 MB/batch) -> pin thread -> "
                         "side-stream H2D + voxelizer (BaseTrainer.device_batches) -> OpenESSPretrainModel.train_step; 16-sample pool"}
 
@@ -93,6 +96,9 @@ if __name__ == "__main__":
     ap.add_argument("--dataloader", action="store_true", help="torch's DataLoader instead of the pinned ring loader (A/B)")
     ap.add_argument("--no-pipeline", action="store_true", help="one step after the other (no front(i+1) ahead of the back half of step i)")
     ap.add_argument("--no-prefetch", action="store_true")
+    ap.add_argument("--contrastive", action="store_true", help="with the superpixel InfoNCE loss (the synthetic grid as superpixels)")
+    ap.add_argument("--online-slic", action="store_true", help="--contrastive with superpixel_sources: online_slic (hip.slic_superpixels per batch)")
     a = ap.parse_args()
-    r = measure(a.batches, a.workers, not a.no_prefetch, ring=not a.dataloader, pipeline=not a.no_pipeline)
+    r = measure(a.batches, a.workers, not a.no_prefetch, ring=not a.dataloader, pipeline=not a.no_pipeline, contrastive=a.contrastive,
+                online_slic=a.online_slic)
     print(json.dumps(r))
