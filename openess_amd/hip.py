@@ -969,13 +969,30 @@ def conv_timing_end():
 
 
 # ------------------------------------------------------------------------------------------ ViT pieces (MaskCLIP tower)
+def _check_token_out(what, out, like, shape):
+    """A caller's `out` is written through its raw pointer: refuse anything the kernel would write outside of."""
+    if not isinstance(out, torch.Tensor) or out.dtype != torch.bfloat16 or out.device != like.device or tuple(out.shape) != tuple(shape) \
+            or out.stride(1) != 1 or (shape[0] > 1 and out.stride(0) < shape[1]):
+        raise ValueError(f"{what}: out must be bf16 {list(shape)} with dense channels on {like.device}")
+
+
+def _check_affine(what, name, p, C, like):
+    if not isinstance(p, torch.Tensor) or p.dtype != torch.float32 or p.device != like.device or tuple(p.shape) != (C,) \
+            or not p.is_contiguous():
+        raise ValueError(f"{what}: {name} must be contiguous fp32 [{C}] on {like.device}")
+
+
 def layer_norm_tokens(x, gamma, beta, eps=1e-6, out=None):
     """nn.LayerNorm over the last axis of a bf16 token matrix [rows, C] (row-strided views are fine)."""
     lib = _lib.load()
-    _need_gpu(x)
     if x.dtype != torch.bfloat16 or x.ndim != 2 or x.stride(1) != 1:
         raise ValueError("layer_norm_tokens: bf16 [rows, C] with dense channels")
     rows, C = x.shape
+    _check_affine("layer_norm_tokens", "gamma", gamma, C, x)
+    _check_affine("layer_norm_tokens", "beta", beta, C, x)
+    if out is not None:
+        _check_token_out("layer_norm_tokens", out, x, (rows, C))
+    _need_gpu(x)
     if out is None:
         out = torch.empty((rows, C), dtype=torch.bfloat16, device=x.device)
     _lib.check(lib.oess_layernorm_bf16(_ptr(x), x.stride(0), rows, C, _ptr(gamma), _ptr(beta), float(eps), _ptr(out), out.stride(0),
@@ -987,10 +1004,12 @@ def attention_d64(qkv, B, L, heads, out=None):
     """softmax(Q K^T / 8) V per head (head dim 64) from nn.MultiheadAttention's packed in_proj output [B*L, 3*heads*64]
     (bf16) -> [B*L, heads*64] (bf16), i.e. the attention output before out_proj."""
     lib = _lib.load()
-    _need_gpu(qkv)
     C = heads * 64
     if qkv.dtype != torch.bfloat16 or qkv.ndim != 2 or qkv.shape != (B * L, 3 * C) or qkv.stride(1) != 1:
         raise ValueError("attention_d64: qkv must be bf16 [B*L, 3*heads*64]")
+    if out is not None:
+        _check_token_out("attention_d64", out, qkv, (B * L, C))
+    _need_gpu(qkv)
     if out is None:
         out = torch.empty((B * L, C), dtype=torch.bfloat16, device=qkv.device)
     _lib.check(lib.oess_attention_d64_bf16(_ptr(qkv), qkv.stride(0), B, L, heads, 0.125, _ptr(out), out.stride(0), _stream()),
