@@ -916,6 +916,39 @@ int oess_slic_assign_f32(const float* lab, const float* centers, const int64_t* 
 int oess_slic_update_f32(const float* lab, const int64_t* labels, const float* centers, int B, int H, int W, int K, float* new_centers,
                          int* counts, void* workspace, size_t workspace_bytes, oess_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------
+ * K25 fp32 MaskCLIP ViT-B/16 inference (models/maskclip_model.py:448-541, 545-851 of the reference in its own arithmetic): the
+ * frozen image tower behind the dense-CLIP pseudo-labels.  Inference only.  Additions only: the ABI version stays.  Nothing here
+ * uses an atomic: every result repeats bit for bit.
+ *
+ * oess_attention_d64_f32: oess_attention_d64_bf16 on fp32 operands: qkv = packed [B L, 3 heads 64] rows (q | k | v, dense
+ *   channels), out = [B L, heads 64].  Both products run on v_mfma_f32_32x32x2_f32 (k-ordered fp32 fma chains), the online
+ *   softmax (running max over 64-key tiles, rescale, accurate expf) is fp32 and P stays fp32 between the two products; a row
+ *   is normalised by a true division by its sum.  Keys past L are masked and rows past L of a batch are never used as loaded
+ *   (zeroed), so what follows the B L rows may be anything.  Row strides in floats, multiples of 4; pointers 16-byte aligned.
+ *   OESS_EINVAL before any launch: a null pointer, B, L or heads < 1, a scale that is not positive and finite, qkv_row_stride < 3 heads 64, out_row_stride < heads 64,
+ *   a stride or pointer off that alignment, heads > 2^20, B L >= 2^31 or more than 2^31 - 1 workgroups (128 queries each).
+ * oess_layernorm_f32: nn.LayerNorm over C channels of each of `rows` fp32 token rows, 1 <= C <= 2048, eps > 0.  One wave per row,
+ *   the row held in registers, TWO passes (mean, then the centred sum of squares; biased variance), y = (x - mean) / sqrt(var +
+ *   eps) * gamma + beta.  16-byte accesses when C % 4 == 0, both row strides % 4 == 0 and x, y, gamma, beta are 16-byte aligned;
+ *   a 4-byte route otherwise.  Row strides in floats, >= C.
+ * oess_linear_tokens_f32: y = act(x W^T + b [+ residual]) for fp32 token rows x [rows, Cin] on the kernel template of
+ *   oess_conv2d_fwd_f32 (a 1 x 1 geometry over a [1, C, 1, rows] view; w_packed is the operand of
+ *   oess_conv2d_f32_packed_floats(Cout, Cin, 1, 1), 16-byte aligned).  act: 0 none, 1 exact GELU 0.5 v (1 + erff(v 0.70710678f))
+ *   (nn.GELU's default), an epilogue the convolution entries do not offer.  bias and residual are nullable; x, residual and out
+ *   have dense channels and row strides in floats >= their row.  With act 0 the result equals oess_conv2d_fwd_f32 at R = S = 1
+ *   on the same operands bit for bit (the same kernel instance, the same k order).  OESS_EINVAL: a null x, w_packed or out,
+ *   rows < 1 or >= 2^31, Cin or Cout < 1, Cin > 2^20, act outside {0, 1}, a stride below its row (res_row_stride is
+ *   read only with a residual), w_packed off 16 bytes.
+ * ------------------------------------------------------------------------------------------ */
+int oess_attention_d64_f32(const float* qkv, long long qkv_row_stride, int B, int L, int heads, float scale, float* out,
+                           long long out_row_stride, oess_stream_t stream);
+int oess_layernorm_f32(const float* x, long long x_row_stride, int64_t rows, int C, const float* gamma, const float* beta, float eps,
+                       float* y, long long y_row_stride, oess_stream_t stream);
+int oess_linear_tokens_f32(const float* x, long long x_row_stride, int64_t rows, int Cin, const float* w_packed, const float* bias,
+                           int Cout, int act, const float* residual, long long res_row_stride, float* out, long long out_row_stride,
+                           oess_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -8,6 +8,8 @@ OPENESS_ALLOW_MISSING_DATA=1) selects the synthetic provider instead of failing 
 `train_precision: fp32` next to it trains them in fp32 (frozen E2VID + SemSegE2VID decoder).
 `superpixel_sources: 'online_slic'` (with the optional `online_slic_segments`) computes the contrastive stage's superpixels
 from the frame on the GPU instead of reading a directory of maps.
+`online_teacher_precision: fp32` in the `clip:` block runs the online MaskCLIP teacher (`pl_sources: online_maskclip`) through
+its fp32 forward; the student's step is not affected.
 Quirk reproduced on purpose: `if_linear_probing` is read from the `clip:` block only (settings.py:258), so the
 reference's config/linear_probe/** files, which put it at top level, dispatch to OpenESSModel.
 """
@@ -187,3 +189,8 @@ class Settings:
         self.train_precision = c.get('train_precision', 'bf16')
         if self.train_precision not in ('bf16', 'fp32'):
             raise ValueError(f"clip.train_precision must be 'bf16' or 'fp32', got {self.train_precision!r}")
+        # arithmetic of the online MaskCLIP teacher (pl_sources: online_maskclip): 'bf16' (the tower's forward) or 'fp32' (its
+        # forward_fp32, DESIGN.md K25: pseudo-labels free of the storage format's near-tie flips).  The student's step stays bf16.
+        self.online_teacher_precision = c.get('online_teacher_precision', 'bf16')
+        if self.online_teacher_precision not in ('bf16', 'fp32'):
+            raise ValueError(f"clip.online_teacher_precision must be 'bf16' or 'fp32', got {self.online_teacher_precision!r}")

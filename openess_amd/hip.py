@@ -1017,6 +1017,102 @@ def attention_d64(qkv, B, L, heads, out=None):
     return out
 
 
+# ---- K25: the same pieces on fp32 tokens (the tower's forward_fp32)
+def _check_tokens_f32(what, name, t, shape=None, like=None):
+    """fp32 [rows, C] with dense channels, rows at least C apart and 16-byte aligned (the vector accesses of the kernels)"""
+    if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or t.ndim != 2 or (shape is not None and tuple(t.shape) != tuple(shape)):
+        want = "[rows, C]" if shape is None else str(list(shape))
+        raise ValueError(f"{what}: {name} must be fp32 {want}")
+    if like is not None and t.device != like.device:
+        raise ValueError(f"{what}: {name} must be on {like.device}")
+    if t.shape[0] < 1 or t.shape[1] < 1:
+        raise ValueError(f"{what}: {name} must not be empty")
+    if t.stride(1) != 1 or (t.shape[0] > 1 and t.stride(0) < t.shape[1]):
+        raise ValueError(f"{what}: {name} must have dense channels and a row stride >= {t.shape[1]}")
+
+
+def _token_stride(t):
+    """row stride handed to a kernel: a single row's is its width (torch reports anything for a size-1 axis)"""
+    return t.stride(0) if t.shape[0] > 1 else t.shape[1]
+
+
+def layer_norm_tokens_f32(x, gamma, beta, eps=1e-6, out=None):
+    """nn.LayerNorm over the last axis of an fp32 token matrix [rows, C], C <= 2048 (row-strided views are fine; 16-byte
+    accesses when C, the strides and the addresses allow, oess_layernorm_f32)."""
+    lib = _lib.load()
+    _check_tokens_f32("layer_norm_tokens_f32", "x", x)
+    rows, C = x.shape
+    if C > 2048:
+        raise ValueError("layer_norm_tokens_f32: x has more than 2048 channels")
+    _check_affine("layer_norm_tokens_f32", "gamma", gamma, C, x)
+    _check_affine("layer_norm_tokens_f32", "beta", beta, C, x)
+    if not eps > 0:
+        raise ValueError("layer_norm_tokens_f32: eps must be positive")
+    if out is not None:
+        _check_tokens_f32("layer_norm_tokens_f32", "out", out, (rows, C), x)
+    _need_gpu(x)
+    if out is None:
+        out = torch.empty((rows, C), dtype=torch.float32, device=x.device)
+    _lib.check(lib.oess_layernorm_f32(_ptr(x), _token_stride(x), rows, C, _ptr(gamma), _ptr(beta), float(eps), _ptr(out),
+                                      _token_stride(out), _stream()), "oess_layernorm_f32")
+    return out
+
+
+def attention_d64_f32(qkv, B, L, heads, out=None):
+    """softmax(Q K^T / 8) V per head (head dim 64) from the packed in_proj output [B*L, 3*heads*64] in fp32 -> [B*L, heads*64]
+    fp32 on the f32-input MFMA (oess_attention_d64_f32): fp32 products, fp32 softmax, no rounding in between."""
+    lib = _lib.load()
+    if not all(isinstance(v, int) and v >= 1 for v in (B, L, heads)):
+        raise ValueError("attention_d64_f32: B, L and heads must be positive integers")
+    C = heads * 64
+    _check_tokens_f32("attention_d64_f32", "qkv", qkv, (B * L, 3 * C))
+    if _token_stride(qkv) % 4 or qkv.data_ptr() % 16:
+        raise ValueError("attention_d64_f32: qkv rows must be 16-byte aligned (row stride a multiple of 4 floats)")
+    if out is not None:
+        _check_tokens_f32("attention_d64_f32", "out", out, (B * L, C), qkv)
+        if _token_stride(out) % 4 or out.data_ptr() % 16:
+            raise ValueError("attention_d64_f32: out rows must be 16-byte aligned (row stride a multiple of 4 floats)")
+    _need_gpu(qkv)
+    if out is None:
+        out = torch.empty((B * L, C), dtype=torch.float32, device=qkv.device)
+    _lib.check(lib.oess_attention_d64_f32(_ptr(qkv), _token_stride(qkv), B, L, heads, 0.125, _ptr(out), _token_stride(out), _stream()),
+               "oess_attention_d64_f32")
+    return out
+
+
+_F32_TOKEN_ACT = {None: 0, 'gelu': 1}
+
+
+def linear_tokens_f32(x, packed, bias, Cout, act=None, residual=None, out=None):
+    """y = act(x W^T + b [+ residual]) for fp32 tokens x [rows, Cin] on the fp32 conv kernel (oess_linear_tokens_f32).  packed:
+    pack_conv_weight_f32(W[:, :, None, None]); act: None or 'gelu' (exact, nn.GELU's default); bias [Cout] and residual
+    [rows, Cout] optional; x, residual and out may be row-strided.  act None gives conv2d_f32(..., R=S=1)'s bits."""
+    lib = _lib.load()
+    _check_tokens_f32("linear_tokens_f32", "x", x)
+    rows, Cin = x.shape
+    if not isinstance(Cout, int) or Cout < 1:
+        raise ValueError("linear_tokens_f32: Cout must be a positive integer")
+    need = lib.oess_conv2d_f32_packed_floats(Cout, Cin, 1, 1)
+    if not isinstance(packed, torch.Tensor) or packed.dtype != torch.float32 or packed.device != x.device or not packed.is_contiguous() \
+            or need == 0 or packed.numel() < need:
+        raise ValueError(f"linear_tokens_f32: packed must be a contiguous fp32 tensor of at least {need} floats on {x.device}")
+    if bias is not None:
+        _check_affine("linear_tokens_f32", "bias", bias, Cout, x)
+    if act not in _F32_TOKEN_ACT:
+        raise ValueError(f"linear_tokens_f32: act must be one of {list(_F32_TOKEN_ACT)}")
+    if residual is not None:
+        _check_tokens_f32("linear_tokens_f32", "residual", residual, (rows, Cout), x)
+    if out is not None:
+        _check_tokens_f32("linear_tokens_f32", "out", out, (rows, Cout), x)
+    _need_gpu(x)
+    if out is None:
+        out = torch.empty((rows, Cout), dtype=torch.float32, device=x.device)
+    _lib.check(lib.oess_linear_tokens_f32(_ptr(x), _token_stride(x), rows, Cin, _ptr(packed), _ptr(bias), Cout, _F32_TOKEN_ACT[act],
+                                          _ptr(residual), 0 if residual is None else _token_stride(residual), _ptr(out),
+                                          _token_stride(out), _stream()), "oess_linear_tokens_f32")
+    return out
+
+
 # scratch of oess_norm_reduce_finalize_tile_stats (per-slice double sums + last-block tickets; tickets are kept zero by the kernel)
 _STATS_SCRATCH = {}
 

@@ -13,6 +13,10 @@ unchanged; the forward runs on liboess kernels:
   head                      -> proj (1x1 conv) -> oess_l2norm -> text-embedding classifier (1x1 conv, fp32 logits)
                                -> bilinear resize to the image, align_corners=False            :157-222, 903-908
 
+Every module also has `forward_fp32` (K25): the same graph in the reference's arithmetic on the fp32 token kernels
+(oess_layernorm_f32, oess_attention_d64_f32, oess_linear_tokens_f32 on the f32-input MFMA), fp32 operands in caches of their
+own; the patch embedding there is a re-layout of the corner-padded image into [B hp wp, 3 * 16 * 16] rows and a token GEMM.
+
 Frozen (the reference sets requires_grad=False on encoder and decoder, :888-891): inference only.
 The reference trainers construct this model but never call it; here it is callable as an online
 teacher: `maskClipFeatureExtractor(img) -> logits [B, K, H, W]`."""
@@ -34,6 +38,13 @@ def _linear_tokens(x2d, weight, bias, pw, act=0, residual=None, rows=None, out_f
     r4 = None if residual is None else residual.view(1, 1, residual.shape[0], residual.shape[1])
     y = hip.conv2d_nhwc(x4, pw.packed, pw.bias, weight.shape[0], 1, 1, 1, 0, 1, relu=act, residual=r4, out_f32=out_f32)
     return y.view(x2d.shape[0], weight.shape[0])
+
+
+def _linear_tokens_f32(x2d, weight, bias, pw, act=None, residual=None):
+    """y = act(x @ W^T + b [+ residual]) for fp32 tokens [rows, Cin] on the fp32 conv kernel.  `weight` / `bias` may be row
+    slices of a parameter (a view carries its base's version counter; every cache serves one fixed slice)."""
+    pw.get(weight.detach()[:, :, None, None], None if bias is None else bias.detach())
+    return hip.linear_tokens_f32(x2d, pw.packed, pw.bias, weight.shape[0], act=act, residual=residual)
 
 
 class _Attn(nn.Module):
@@ -60,6 +71,31 @@ class TransformerEncoderLayer(nn.Module):
         self.ln2 = nn.LayerNorm(embed_dims, eps=1e-6)
         self.ffn = _FFN(embed_dims, feedforward_channels)
         self._pw = {k: engine.PackedWeight() for k in ('qkv', 'v', 'out', 'fc1', 'fc2')}
+        self._pw32 = {k: engine.PackedWeightF32() for k in ('qkv', 'v', 'out', 'fc1', 'fc2')}
+
+    def _ffn_fp32(self, x):
+        y = hip.layer_norm_tokens_f32(x, self.ln2.weight, self.ln2.bias, self.ln2.eps)
+        fc1, fc2 = self.ffn.layers[0][0], self.ffn.layers[1]
+        h = _linear_tokens_f32(y, fc1.weight, fc1.bias, self._pw32['fc1'], act='gelu')
+        return _linear_tokens_f32(h, fc2.weight, fc2.bias, self._pw32['fc2'], residual=x)
+
+    def forward_fp32(self, x, B, L):
+        """x: fp32 tokens [B*L, C] -> same shape (full block)."""
+        a = self.attn.attn
+        y = hip.layer_norm_tokens_f32(x, self.ln1.weight, self.ln1.bias, self.ln1.eps)
+        qkv = _linear_tokens_f32(y, a.in_proj_weight, a.in_proj_bias, self._pw32['qkv'])
+        o = hip.attention_d64_f32(qkv, B, L, self.num_heads)
+        x = _linear_tokens_f32(o, a.out_proj.weight, a.out_proj.bias, self._pw32['out'], residual=x)
+        return self._ffn_fp32(x)
+
+    def forward_value_path_fp32(self, x):
+        """forward_value_path on fp32 tokens."""
+        a = self.attn.attn
+        C = x.shape[1]
+        y = hip.layer_norm_tokens_f32(x, self.ln1.weight, self.ln1.bias, self.ln1.eps)
+        v = _linear_tokens_f32(y, a.in_proj_weight[2 * C:], a.in_proj_bias[2 * C:], self._pw32['v'])
+        v = _linear_tokens_f32(v, a.out_proj.weight, a.out_proj.bias, self._pw32['out'], residual=x)
+        return self._ffn_fp32(v)
 
     def _ffn(self, x):
         y = hip.layer_norm_tokens(x, self.ln2.weight, self.ln2.bias, self.ln2.eps)
@@ -106,6 +142,7 @@ class VisionTransformer(nn.Module):
         self.ln0 = nn.LayerNorm(embed_dims, eps=1e-6)
         self.ln1 = nn.LayerNorm(embed_dims, eps=1e-6)
         self._pw_patch = engine.PackedWeight()
+        self._pw_patch32 = engine.PackedWeightF32()
         self._pos_cache = {}
 
     def _pos(self, hw):
@@ -144,6 +181,31 @@ class VisionTransformer(nn.Module):
         return v.view(B, L, C)[:, 1:].reshape(B, hp, wp, C).permute(0, 3, 1, 2)         # logical NCHW, NHWC memory
 
 
+    @torch.no_grad()
+    def forward_fp32(self, img):
+        """forward in fp32: v_map [B, 768, H/16, W/16] fp32.  Stride equals kernel in the patch embedding, so it is a re-layout
+        of the corner-padded image into one row per patch, (c, dy, dx) order like the flattened weight, and a token GEMM."""
+        B, Cin, H, W = img.shape
+        p, C = self.patch_size, self.embed_dims
+        hp, wp = (H + p - 1) // p, (W + p - 1) // p
+        xp = torch.zeros((B, Cin, hp * p, wp * p), dtype=torch.float32, device=img.device)
+        xp[:, :, :H, :W] = img
+        rows = xp.view(B, Cin, hp, p, wp, p).permute(0, 2, 4, 1, 3, 5).reshape(B * hp * wp, Cin * p * p)
+        w = self.patch_embed.projection.weight
+        patches = _linear_tokens_f32(rows, w.view(w.shape[0], -1), None, self._pw_patch32)
+        L = hp * wp + 1
+        tok = torch.empty((B, L, C), dtype=torch.float32, device=img.device)
+        tok[:, 0] = self.cls_token.detach()[0, 0]
+        tok[:, 1:] = patches.view(B, hp * wp, C)
+        tok += self._pos((hp, wp))
+        x = hip.layer_norm_tokens_f32(tok.view(B * L, C), self.ln0.weight, self.ln0.bias, self.ln0.eps)
+        for layer in self.layers[:-1]:
+            x = layer.forward_fp32(x, B, L)
+        v = self.layers[-1].forward_value_path_fp32(x)
+        v = hip.layer_norm_tokens_f32(v, self.ln1.weight, self.ln1.bias, self.ln1.eps)
+        return v.view(B, L, C)[:, 1:].reshape(B, hp, wp, C).permute(0, 3, 1, 2)         # logical NCHW, NHWC memory
+
+
 class MaskClipHead(nn.Module):
     """maskclip_model.py:52-222 (vit=True): logits = conv2d(normalize(proj(v)), text_embeddings)."""
 
@@ -155,6 +217,7 @@ class MaskClipHead(nn.Module):
         self.proj = nn.Conv2d(in_channels, text_channels, 1, bias=False)
         self.image_mapping_local = nn.Conv2d(in_channels, 512, 1)           # constructed by the reference, never used (:125)
         self._pw_proj, self._pw_text = engine.PackedWeight(), engine.PackedWeight()
+        self._pw_proj32, self._pw_text32 = engine.PackedWeightF32(), engine.PackedWeightF32()
 
     @torch.no_grad()
     def forward(self, v_map):
@@ -164,6 +227,18 @@ class MaskClipHead(nn.Module):
         feat = hip.l2_normalize(feat.view(B, hp, wp, -1).permute(0, 3, 1, 2), eps=1e-30)    # feat / feat.norm(dim=1) (:217)
         f2 = engine.nhwc(feat).reshape(B * hp * wp, -1)
         logits = _linear_tokens(f2, self.text_embeddings, None, self._pw_text, out_f32=True)
+        return v_map, logits.view(B, hp, wp, -1).permute(0, 3, 1, 2)
+
+
+    @torch.no_grad()
+    def forward_fp32(self, v_map):
+        """forward on an fp32 v_map: (v_map, fp32 logits [B, K, hp, wp])."""
+        B, C, hp, wp = v_map.shape
+        v2 = engine.nhwc(v_map).reshape(B * hp * wp, C)
+        feat = _linear_tokens_f32(v2, self.proj.weight[:, :, 0, 0], None, self._pw_proj32)
+        feat = hip.l2_normalize(feat.view(B, hp, wp, -1).permute(0, 3, 1, 2), eps=1e-30)
+        f2 = engine.nhwc(feat).reshape(B * hp * wp, -1)
+        logits = _linear_tokens_f32(f2, self.text_embeddings, None, self._pw_text32)
         return v_map, logits.view(B, hp, wp, -1).permute(0, 3, 1, 2)
 
 
@@ -201,3 +276,11 @@ class maskClipFeatureExtractor(nn.Module):
         v_map = self.encoder(img)
         _, logits = self.decoder(v_map)
         return hip.bilinear_resize(logits.float(), size=(img.shape[2], img.shape[3]), align_corners=self.align_corners)
+
+    @torch.no_grad()
+    def forward_fp32(self, img):
+        """The tower in the reference's arithmetic: fp32 logits [B, K, H, W] (the online teacher of
+        `online_teacher_precision: fp32`; its argmax is the dense-CLIP pseudo-label map)."""
+        v_map = self.encoder.forward_fp32(img.float())
+        _, logits = self.decoder.forward_fp32(v_map)
+        return hip.bilinear_resize(logits, size=(img.shape[2], img.shape[3]), align_corners=self.align_corners)

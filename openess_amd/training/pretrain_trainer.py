@@ -47,6 +47,13 @@ class OpenESSPretrainModel(BaseTrainer):
             from ..models.maskclip_model import maskClipFeatureExtractor
             kw = {k: getattr(s, k) for k in ('text_embeddings_path', 'visual_projs_path', 'maskclip_checkpoint') if getattr(s, k, None)}
             online = maskClipFeatureExtractor(text_categories=s.semseg_num_classes, **kw).to(self.device).eval()
+            # `online_teacher_precision: fp32` (optional YAML key, clip block): the labels are the argmax of the
+            # tower's fp32 forward.  PretrainStep takes any callable; the student's step stays bf16.
+            precision = getattr(s, 'online_teacher_precision', 'bf16')
+            if precision not in ('bf16', 'fp32'):
+                raise ValueError(f"online_teacher_precision must be 'bf16' or 'fp32', got {precision!r}")
+            if precision == 'fp32':
+                online = online.forward_fp32
         self.step = PretrainStep(config_option=s.config_option, online_teacher=online, num_classes=s.semseg_num_classes, img_size=tuple(s.img_size_b),
                                  nr_events_data=s.nr_events_data_b, nr_temporal_bins=s.nr_temporal_bins_b,
                                  if_spatial_contrastive=s.if_spatial_contrastive,
