@@ -886,7 +886,7 @@ int oess_aspp_pool_bwd_f32o(const float* grad_z, const float* pooled, float in_s
 
 /* ------------------------------------------------------------------------------------------
  * K24 SLIC superpixels (data_preparation/superpixel_segmenter_dsec_slic.py:19-24 of the reference:
- * skimage.segmentation.slic(img, n_segments, compactness=6, sigma=3.0, start_label=0), here without the connectivity pass).
+ * skimage.segmentation.slic(img, n_segments, compactness=6, sigma=3.0, start_label=0); its connectivity pass is the block below).
  * Additions only: the ABI version stays.  fp32, no floating-point atomics: every result repeats bit for bit.
  * A centre is five floats (y, x, L, a, b); centre k = i nx + j of the ny x nx lattice.
  *
@@ -915,6 +915,33 @@ int oess_slic_assign_f32(const float* lab, const float* centers, const int64_t* 
                          int nx, int64_t* labels, oess_stream_t stream);
 int oess_slic_update_f32(const float* lab, const int64_t* labels, const float* centers, int B, int H, int W, int K, float* new_centers,
                          int* counts, void* workspace, size_t workspace_bytes, oess_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
+ * K24 SLIC connectivity pass (data_preparation/superpixel_segmenter_dsec_slic.py:19-24 of the reference: skimage's slic runs
+ * with its default enforce_connectivity=True).  Additions only: the ABI version stays.  Integer atomics only: every result is a
+ * function of the input partition and repeats bit for bit.
+ *
+ * oess_slic_connectivity_i64 (superpixel_segmenter_dsec_slic.py:19-24): labels, out: dense int64 [B, H, W]; labels are compared
+ *   for equality only, any values.  A component is a 4-connected set of equal labels, its root its lowest raster index y W + x.
+ *   Components of at least min_size pixels are kept and numbered 0 .. n - 1 in the order of their roots; a smaller one takes the
+ *   final label of its donor: walking it breadth first from its root (neighbours right, left, down, up), the LAST neighbour
+ *   pixel seen that lies in a component with a smaller root; 0 when there is none.  This is skimage's
+ *   _enforce_label_connectivity_cython with one deliberate difference: skimage cuts a flood fill at max_size pixels (the cut
+ *   depends on the fill order); here a component of max_size pixels or more stays whole, and there is no max_size.
+ *   n_labels (nullable): int [B], the kept components of every sample (0: every pixel of the sample is 0).
+ *   workspace: oess_slic_connectivity_workspace_bytes(B, H, W) bytes (five int planes and the chunk counts; 0 for a geometry
+ *   that is refused), 4-byte aligned, initialised by the call.  Launches on `stream` only, no read-back.
+ *   OESS_EINVAL before any launch: a null labels, out or workspace, out == labels, min_size < 0, B, H or W < 1, H W > 2^24,
+ *   more than 2^31 - 1 chunks of 256 pixels, a workspace off 4 bytes; OESS_ENOMEM: a short workspace.
+ * oess_slic_connectivity_phase_ms (superpixel_segmenter_dsec_slic.py:19-24): a measurement aid (tools/bench_slic.py).  The same
+ *   launches with an event around each of the five phases (components | flatten + sizes | ranks | donors | resolve + write);
+ *   waits for the last one and fills phase_ms[5] (host memory) with the milliseconds between them.
+ * ------------------------------------------------------------------------------------------ */
+size_t oess_slic_connectivity_workspace_bytes(int B, int H, int W);
+int oess_slic_connectivity_i64(const int64_t* labels, int B, int H, int W, int min_size, int64_t* out, int* n_labels /* nullable, [B] */,
+                               void* workspace, size_t workspace_bytes, oess_stream_t stream);
+int oess_slic_connectivity_phase_ms(const int64_t* labels, int B, int H, int W, int min_size, int64_t* out, void* workspace,
+                                    size_t workspace_bytes, float* phase_ms, oess_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
  * K25 fp32 MaskCLIP ViT-B/16 inference (models/maskclip_model.py:448-541, 545-851 of the reference in its own arithmetic): the

@@ -201,6 +201,9 @@ SIGNATURES = {
     "oess_slic_lab_f32": (c_int, [c_view, c_int, c_int, c_int, c_f, c_f, c_vp, c_int, c_int, c_vp, c_vp]),
     "oess_slic_assign_f32": (c_int, [c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_vp, c_vp]),
     "oess_slic_update_f32": (c_int, [c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_vp, c_vp, c_vp, c_sz, c_vp]),
+    "oess_slic_connectivity_workspace_bytes": (c_sz, [c_int, c_int, c_int]),
+    "oess_slic_connectivity_i64": (c_int, [c_vp, c_int, c_int, c_int, c_int, c_vp, c_vp, c_vp, c_sz, c_vp]),
+    "oess_slic_connectivity_phase_ms": (c_int, [c_vp, c_int, c_int, c_int, c_int, c_vp, c_vp, c_sz, c_vp, c_vp]),
     "oess_attention_d64_f32": (c_int, [c_vp, c_ll, c_int, c_int, c_int, c_f, c_vp, c_ll, c_vp]),
     "oess_layernorm_f32": (c_int, [c_vp, c_ll, c_i64, c_int, c_vp, c_vp, c_f, c_vp, c_ll, c_vp]),
     "oess_linear_tokens_f32": (c_int, [c_vp, c_ll, c_i64, c_int, c_vp, c_vp, c_int, c_int, c_vp, c_ll, c_vp, c_ll, c_vp]),

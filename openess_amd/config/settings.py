@@ -7,7 +7,8 @@ OPENESS_ALLOW_MISSING_DATA=1) selects the synthetic provider instead of failing 
 `eval_precision: fp32` in the `clip:` block (next to `use_amp`) validates the stage-2/3 event networks in fp32;
 `train_precision: fp32` next to it trains them in fp32 (frozen E2VID + SemSegE2VID decoder).
 `superpixel_sources: 'online_slic'` (with the optional `online_slic_segments`) computes the contrastive stage's superpixels
-from the frame on the GPU instead of reading a directory of maps.
+from the frame on the GPU instead of reading a directory of maps; `online_slic_connectivity: True` next to it
+appends SLIC's connectivity pass, and `online_slic_segments` must then be about half the pooling size.
 `online_teacher_precision: fp32` in the `clip:` block runs the online MaskCLIP teacher (`pl_sources: online_maskclip`) through
 its fp32 forward; the student's step is not affected.
 Quirk reproduced on purpose: `if_linear_probing` is read from the `clip:` block only (settings.py:258), so the
@@ -173,6 +174,9 @@ class Settings:
             self.online_slic_segments = c.get('online_slic_segments')
             if self.online_slic_segments is not None:
                 self.online_slic_segments = int(self.online_slic_segments)
+            # `online_slic_connectivity: True` appends SLIC's connectivity pass (skimage's default, what the reference's files
+            # were written with); only with `superpixel_sources: 'online_slic'`, which the trainers check
+            self.online_slic_connectivity = bool(c.get('online_slic_connectivity', False))
         if c.get('if_finetuning') is not None:
             self.if_finetuning = c['if_finetuning']
             for key in ('load_pretrained_weights', 'pretrained_file', 'if_switchable_train'):

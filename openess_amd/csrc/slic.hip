@@ -1,5 +1,5 @@
 // K24: SLIC superpixels on the GPU (data_preparation/superpixel_segmenter_dsec_slic.py:19-24 of the reference:
-//   skimage.segmentation.slic(img, n_segments, compactness=6, sigma=3.0, start_label=0), without its connectivity pass).
+//   skimage.segmentation.slic(img, n_segments, compactness=6, sigma=3.0, start_label=0); its connectivity pass is slic_connectivity.hip).
 // Three passes, all fp32, all bit-repeatable:
 //
 // slic_lab_kernel: separable Gaussian blur (radius int(4 sigma + 0.5), border rule `reflect`: d c b a | a b c d) of each colour

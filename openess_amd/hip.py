@@ -5,6 +5,7 @@ bookkeeping.  Every function enqueues hand-written HIP kernels on the CURRENT to
 raises if the library is missing or a tensor is not on the GPU -- there is no CPU/eager fallback.
 """
 import ctypes
+import operator
 
 import torch
 
@@ -3091,11 +3092,84 @@ def slic_update(lab, labels, centers, out=None, return_counts=False):
     return (out, counts) if return_counts else out
 
 
-def slic_superpixels(frames, n_segments, compactness=6.0, sigma=3.0, iters=10, return_centers=False):
+def slic_connectivity_sizes(H, W, K):
+    """skimage's thresholds of the connectivity pass for an H x W map with K placed centres, a pure host function:
+    (min_size, max_size, bound) with segment_size = H W / K, min_size = int(0.5 segment_size), max_size = int(3 segment_size)
+    and bound = H W // max(min_size, 1), the most labels a sample can hold after the pass (every kept component has at least
+    min_size pixels): about 2 K.  The GPU pass takes min_size only: a component of max_size pixels or more stays whole
+    (skimage cuts it, by a rule that depends on its fill order); max_size is returned so that a caller can tell."""
+    H, W, K = int(H), int(W), int(K)
+    if H < 1 or W < 1 or K < 1:
+        raise ValueError(f"slic_connectivity_sizes needs H, W, K >= 1, got {(H, W, K)}")
+    segment = H * W / K
+    min_size = int(0.5 * segment)
+    return min_size, int(3 * segment), H * W // max(min_size, 1)
+
+
+def _slic_check_connectivity(labels, min_size, out):
+    if not torch.is_tensor(labels) or labels.dtype != torch.int64 or labels.ndim != 3 or not labels.is_contiguous():
+        raise ValueError("labels must be a contiguous int64 tensor [B, H, W]")
+    B, H, W = labels.shape
+    if B < 1 or H * W < 1 or H * W > (1 << 24):
+        raise ValueError(f"labels: B >= 1 and 1 <= H W <= 2^24 are needed, got {tuple(labels.shape)}")
+    try:
+        min_size = None if isinstance(min_size, bool) else operator.index(min_size)
+    except TypeError:
+        min_size = None
+    if min_size is None or not 0 <= min_size <= 0x7fffffff:
+        raise ValueError("slic_enforce_connectivity: min_size must be an integer in [0, 2^31)")
+    if out is not None:
+        _slic_check_labels(out, B, H, W, "out")
+        if out.data_ptr() < labels.data_ptr() + labels.numel() * 8 and labels.data_ptr() < out.data_ptr() + out.numel() * 8:
+            raise ValueError("slic_enforce_connectivity: out must not alias labels (every pixel reads its neighbours' labels)")
+    return B, H, W, min_size
+
+
+def slic_enforce_connectivity(labels, min_size, out=None, return_counts=False):
+    """The connectivity pass of SLIC (oess_slic_connectivity_i64; skimage's enforce_connectivity=True): contiguous int64 labels
+    [B, H, W] on the GPU (any values, compared for equality only) -> int64 [B, H, W].  4-connected components of equal labels with
+    at least min_size pixels are numbered 0 .. n - 1 by their first pixel in raster order; a smaller one takes the label of the
+    last earlier-rooted neighbour its breadth-first walk (right, left, down, up) sees, or 0 without one.  A component of
+    max_size pixels or more stays whole: skimage's order-dependent cut is not made, and there is no max_size.
+    out must not alias labels.  return_counts: also the int32 [B] number of kept components n (0: the sample is all 0).
+    Launches on the current stream, no read-back; two calls give the same bits."""
+    B, H, W, min_size = _slic_check_connectivity(labels, min_size, out)
+    _need_gpu(labels, out)
+    lib = _lib.load()
+    if out is None:
+        out = torch.empty_like(labels)
+    need = lib.oess_slic_connectivity_workspace_bytes(B, H, W)
+    ws = _workspace(need, labels.device, tag="slic_connectivity")
+    counts = torch.empty((B,), dtype=torch.int32, device=labels.device) if return_counts else None
+    _lib.check(lib.oess_slic_connectivity_i64(_ptr(labels), B, H, W, min_size, _ptr(out), _ptr(counts), _ptr(ws), ws.numel(), _stream()),
+               "oess_slic_connectivity_i64")
+    _bump(out)
+    return (out, counts) if return_counts else out
+
+
+def slic_connectivity_phase_ms(labels, min_size):
+    """Milliseconds of the five phases of one hip.slic_enforce_connectivity call (components | flatten + sizes | ranks | donors |
+    resolve + write), HIP events between the same launches (oess_slic_connectivity_phase_ms).  Synchronises: a measurement aid."""
+    B, H, W, min_size = _slic_check_connectivity(labels, min_size, None)
+    _need_gpu(labels)
+    lib = _lib.load()
+    out = torch.empty_like(labels)
+    ws = _workspace(lib.oess_slic_connectivity_workspace_bytes(B, H, W), labels.device, tag="slic_connectivity")
+    ms = (ctypes.c_float * 5)()
+    _lib.check(lib.oess_slic_connectivity_phase_ms(_ptr(labels), B, H, W, min_size, _ptr(out), _ptr(ws), ws.numel(), ms, _stream()),
+               "oess_slic_connectivity_phase_ms")
+    return dict(zip(("components", "sizes", "ranks", "donors", "write"), (float(v) for v in ms)))
+
+
+def slic_superpixels(frames, n_segments, compactness=6.0, sigma=3.0, iters=10, return_centers=False, enforce_connectivity=False):
     """SLIC superpixels of a batch of frames on the GPU (K24; the reference's offline
-    skimage.segmentation.slic(img, n_segments, compactness=6, sigma=3.0, start_label=0) without its connectivity pass):
+    skimage.segmentation.slic(img, n_segments, compactness=6, sigma=3.0, start_label=0)):
     frames [B, 3, H, W] fp32 -> int64 labels [B, H, W] in [0, K), K = ny nx of hip.slic_lattice (K <= 256).  Exactly `iters`
-    assignment + update rounds on the current stream, no early exit and no read-back; two calls give the same bits."""
+    assignment + update rounds on the current stream, no early exit and no read-back; two calls give the same bits.
+    enforce_connectivity=False (the default) stops there: skimage's enforce_connectivity=False.  True appends the connectivity
+    pass (hip.slic_enforce_connectivity) with min_size of hip.slic_connectivity_sizes(H, W, K), as skimage's default does: the
+    labels are then in [0, bound), bound = H W // max(min_size, 1) of that function (about 2 K), numbered by first pixel, and
+    no longer index the returned centres.  Unlike skimage a component of max_size pixels or more stays whole."""
     if not torch.is_tensor(frames) or frames.dtype != torch.float32 or frames.ndim != 4 or frames.shape[1] != 3:
         raise ValueError("frames must be a 4-D float32 tensor [B, 3, H, W]")
     iters = int(iters)
@@ -3110,4 +3184,6 @@ def slic_superpixels(frames, n_segments, compactness=6.0, sigma=3.0, iters=10, r
     for _ in range(iters):
         labels = slic_assign(lab, centers, labels, step, lattice=(ny, nx), out=labels)
         centers = slic_update(lab, labels, centers, out=centers)
+    if enforce_connectivity:
+        labels = slic_enforce_connectivity(labels, slic_connectivity_sizes(H, W, ny * nx)[0])
     return (labels, centers) if return_centers else labels

@@ -24,6 +24,9 @@ def online_slic_segments(settings, pool_size):
     refusals of the key: recon2voxel has no RGB frame to segment, and more segments than the pooling size would let one sample's
     ids run into the next sample's rows."""
     if getattr(settings, 'superpixel_sources', '') != ONLINE_SLIC:
+        if getattr(settings, 'online_slic_connectivity', False):
+            raise ValueError("online_slic_connectivity: True needs superpixel_sources: online_slic, got "
+                             f"{getattr(settings, 'superpixel_sources', '')!r}")
         return None
     if settings.config_option == 'recon2voxel':
         raise ValueError("superpixel_sources: online_slic needs an RGB frame in the batch (config_option frame2voxel or frame2recon); "
@@ -34,6 +37,25 @@ def online_slic_segments(settings, pool_size):
         raise ValueError(f"online_slic_segments = {n} must be between 1 and the pooling size {pool_size} (superpixel_size): the "
                          f"pooling offsets sample b's ids by b * {pool_size}")
     return n
+
+
+def online_slic_rows(H, W, n_segments, pool_size, connectivity):
+    """Rows a sample's online SLIC labels can reach on an H x W frame, from the shapes alone: the K = ny nx centres, or with the
+    connectivity pass its label bound (hip.slic_connectivity_sizes, about 2 K).  More than the pooling size is refused: sample
+    b's ids are offset by b * pool_size."""
+    ny, nx, _ = hip.slic_lattice(H, W, n_segments)
+    K = ny * nx
+    if not connectivity:
+        if K > pool_size:
+            raise ValueError(f"online_slic: a {(H, W)} frame with {n_segments} segments gives {K} centres, more than the pooling size "
+                             f"{pool_size}")
+        return K
+    bound = hip.slic_connectivity_sizes(H, W, K)[2]
+    if bound > pool_size:
+        raise ValueError(f"online_slic_connectivity: a {(H, W)} frame with {n_segments} segments ({K} centres) can give {bound} labels "
+                         f"after the connectivity pass, more than the pooling size {pool_size}: online_slic_segments must be about "
+                         f"half the pooling size")
+    return bound
 
 
 class BaseTrainer(object):
@@ -373,16 +395,14 @@ class BaseTrainer(object):
         S = None
         if self.online_slic_segments and split == 'train' and getattr(s, 'if_spatial_contrastive', False):
             # superpixel_sources: online_slic (K24): SLIC of the frame the step sees (already flipped and augmented on the host), on
-            # this stream -- the ingest stream, under the previous step.  Labels are 0 .. K - 1 with K from the shapes alone, so
-            # the row count needs no read-back
+            # this stream -- the ingest stream, under the previous step.  Labels are 0 .. K - 1 with K from the shapes alone (with
+            # online_slic_connectivity below the pass's label bound, from the shapes too), so the row count needs no read-back
             frame = first if s.config_option == 'frame2recon' else rest[1]
             sps = self.pooling_size()
-            ny, nx, _ = hip.slic_lattice(frame.shape[2], frame.shape[3], self.online_slic_segments)
-            if ny * nx > sps:
-                raise ValueError(f"online_slic: a {tuple(frame.shape[2:])} frame with {self.online_slic_segments} segments gives "
-                                 f"{ny * nx} centres, more than the pooling size {sps}")
-            rest[3] = hip.slic_superpixels(frame, self.online_slic_segments)
-            S = (frame.shape[0] - 1) * sps + ny * nx
+            connected = bool(getattr(s, 'online_slic_connectivity', False))
+            rows = online_slic_rows(frame.shape[2], frame.shape[3], self.online_slic_segments, sps, connected)
+            rest[3] = hip.slic_superpixels(frame, self.online_slic_segments, enforce_connectivity=connected)
+            S = (frame.shape[0] - 1) * sps + rows
         elif sp is not None and getattr(s, 'if_spatial_contrastive', False):
             # host-side row count: no device sync in the step (OpenESSModel pools with its own hard-coded size)
             sps = self.pooling_size()

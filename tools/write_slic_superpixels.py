@@ -1,13 +1,16 @@
 """Offline SLIC superpixels through the GPU kernels, in the on-disk format of the reference's
 data_preparation/superpixel_segmenter_dsec_slic.py:
 
-    python tools/write_slic_superpixels.py --root DATA --num_segments 100 [--dataset DSEC|DDD17] [--batch 8]
+    python tools/write_slic_superpixels.py --root DATA --num_segments 100 [--dataset DSEC|DDD17] [--batch 8] [--enforce-connectivity]
 
 DSEC:  every <seq>/images_aligned/left/<name>.png under DATA -> <seq>/sp_slic_rgb/left/<name>_slic_<n>.png
 DDD17: every <dir>/images_aligned/<name>.png under DATA      -> <dir>/sp_slic_rgb/<name>_slic_<n>.png
 uint8 grayscale PNGs of the cluster indices; files that exist are skipped.  The file-based `superpixel_sources: sp_slic_rgb` of
 this project and of the reference read them.  Frames are read with Pillow and go to the GPU in batches of one size.
-Not skimage bit for bit: there is no connectivity pass (hip.slic_superpixels)."""
+--enforce-connectivity appends SLIC's connectivity pass (skimage's default, which the reference's files were written with): the
+labels then run up to hip.slic_connectivity_sizes' bound, about twice the centres, and a frame size whose bound exceeds the
+256 values of a uint8 map is refused.  Not skimage bit for bit: fp32 arithmetic, and a component of max_size pixels or more
+stays whole (hip.slic_superpixels)."""
 import argparse
 import os
 import sys
@@ -40,6 +43,7 @@ def main(argv=None):
     ap.add_argument("--num_segments", type=int, default=100)
     ap.add_argument("--dataset", choices=("DSEC", "DDD17"), default="DSEC")
     ap.add_argument("--batch", type=int, default=8)
+    ap.add_argument("--enforce-connectivity", action="store_true", help="append SLIC's connectivity pass (skimage's default)")
     args = ap.parse_args(argv)
     import torch
     from PIL import Image
@@ -55,9 +59,17 @@ def main(argv=None):
     written = 0
 
     def flush(batch):
+        if args.enforce_connectivity:
+            H, W = batch[0][0].shape[:2]
+            ny, nx, _ = hip.slic_lattice(H, W, args.num_segments)
+            bound = hip.slic_connectivity_sizes(H, W, ny * nx)[2]
+            if bound > hip.SLIC_MAX_CENTERS:
+                raise SystemExit(f"{batch[0][1]}: a {H} x {W} frame with {args.num_segments} segments can give {bound} labels after the "
+                                 f"connectivity pass, more than the {hip.SLIC_MAX_CENTERS} values of a uint8 map")
         frames = torch.from_numpy(np.stack([b[0] for b in batch])).cuda(non_blocking=True)
         frames = frames.permute(0, 3, 1, 2).float() * (1.0 / 255.0)                 # a channels-last view: the kernel takes strides
-        labels = hip.slic_superpixels(frames, args.num_segments).to(torch.uint8).cpu().numpy()
+        labels = hip.slic_superpixels(frames, args.num_segments, enforce_connectivity=args.enforce_connectivity)
+        labels = labels.to(torch.uint8).cpu().numpy()
         for (_, out), seg in zip(batch, labels):
             os.makedirs(os.path.dirname(out), exist_ok=True)
             Image.fromarray(seg).save(out)
