@@ -976,6 +976,47 @@ int oess_linear_tokens_f32(const float* x, long long x_row_stride, int64_t rows,
                            int Cout, int act, const float* residual, long long res_row_stride, float* out, long long out_row_stride,
                            oess_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------
+ * K26 MaskCLIP refinement of the class logits (MaskClipHead.refine_output, models/maskclip_model.py:224-250 of the reference):
+ * prompt denoising and key smoothing.  Additions only: the ABI version stays.  fp32 arithmetic whatever the tower's precision,
+ * no floating-point atomic, fixed summation order: every result repeats bit for bit.
+ *
+ * oess_maskclip_refine_f32: logits, out: fp32 [B, K, H, W] by element strides (sb, sc, sy, sx; any layout, out's elements
+ *   distinct and apart from logits); L = H W tokens in raster order.
+ *   pd_thresh > 0: conf[b, c] = max_l softmax_c(100 logits)[b, c, l]; a class with conf < pd_thresh gets the logit -100 on every
+ *   pixel of that image.
+ *   k non-null and ks_thresh > 0: P = softmax_c(100 denoised logits); k: [B, L, C] keys of the last encoder layer, fp32
+ *   (OESS_MASKCLIP_K_F32) or bf16 (OESS_MASKCLIP_K_BF16), dense channels, k[b, l, c] at k + b k_img_stride + l k_row_stride + c
+ *   (element strides: the tower's [B (L + 1), C] token matrix is read in place past its class-token rows); every channel is
+ *   divided by max(its 2-norm over the L tokens, 1e-12) (F.normalize's default dim 1); a pixel with max_c P < ks_thresh takes
+ *   its row of (k^ k^T) P, evaluated as k (k^T P / n^2) so that no L x L matrix exists, every other pixel keeps P.  out then
+ *   holds probabilities.  Otherwise out is the logits with the -100 rows, untouched values copied bit for bit.
+ *   The softmax subtracts the row maximum first (100 x reaches 1e4).  Sums over tokens: per 128-token chunk a wave adds every
+ *   fourth token in ascending order with fmaf, the four waves and then the chunks are added in order; sums over channels: a
+ *   lane adds channels lane, lane + 64, ... with fmaf, the 64 lanes join by a fixed butterfly.
+ *   Served: 1 <= K <= 32, 1 <= H W <= 4096, C % 64 == 0 and 64 <= C <= 1024 (read only with k), 1 <= B <= 65535.
+ *   workspace: oess_maskclip_refine_workspace_bytes(B, K, H, W, C) bytes (C = 0: a call without k; 0 for a geometry that is
+ *   refused), 16-byte aligned, written by the call.  Launches on `stream` only, no read-back.
+ *   OESS_EINVAL before any launch: a null logits, out or workspace, a geometry outside the above, a threshold that is negative,
+ *   infinite or NaN, a negative stride or one of 2^40 or more, out elements that overlap, an unknown k_dtype, k_row_stride < C,
+ *   k_img_stride below the extent of one image's keys (B > 1), a pointer off its element's alignment, a workspace off 16 bytes;
+ *   OESS_ENOMEM: a short workspace.
+ * oess_maskclip_refine_phase_ms (models/maskclip_model.py:224-250): a measurement aid (tools/bench_maskclip_refine.py).  The same
+ *   launches with an event around each of the five kernels (confidence | mask + softmax | k^T P per chunk | chunk sum + norms |
+ *   k Hm + select); waits for the last one and fills phase_ms[5] (host memory) with the milliseconds between them.
+ * ------------------------------------------------------------------------------------------ */
+#define OESS_MASKCLIP_K_F32 0
+#define OESS_MASKCLIP_K_BF16 1
+size_t oess_maskclip_refine_workspace_bytes(int B, int K, int H, int W, int C);
+int oess_maskclip_refine_f32(const float* logits, long long sb, long long sc, long long sy, long long sx, int B, int K, int H, int W,
+                             const void* k /* nullable */, int k_dtype, long long k_row_stride, long long k_img_stride, int C,
+                             float pd_thresh, float ks_thresh, float* out, long long ob, long long oc, long long oy, long long ox,
+                             void* workspace, size_t workspace_bytes, oess_stream_t stream);
+int oess_maskclip_refine_phase_ms(const float* logits, long long sb, long long sc, long long sy, long long sx, int B, int K, int H, int W,
+                                  const void* k /* nullable */, int k_dtype, long long k_row_stride, long long k_img_stride, int C,
+                                  float pd_thresh, float ks_thresh, float* out, long long ob, long long oc, long long oy, long long ox,
+                                  void* workspace, size_t workspace_bytes, float* phase_ms, oess_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -207,6 +207,11 @@ SIGNATURES = {
     "oess_attention_d64_f32": (c_int, [c_vp, c_ll, c_int, c_int, c_int, c_f, c_vp, c_ll, c_vp]),
     "oess_layernorm_f32": (c_int, [c_vp, c_ll, c_i64, c_int, c_vp, c_vp, c_f, c_vp, c_ll, c_vp]),
     "oess_linear_tokens_f32": (c_int, [c_vp, c_ll, c_i64, c_int, c_vp, c_vp, c_int, c_int, c_vp, c_ll, c_vp, c_ll, c_vp]),
+    "oess_maskclip_refine_workspace_bytes": (c_sz, [c_int, c_int, c_int, c_int, c_int]),
+    "oess_maskclip_refine_f32": (c_int, [c_vp, c_ll, c_ll, c_ll, c_ll, c_int, c_int, c_int, c_int, c_vp, c_int, c_ll, c_ll, c_int, c_f,
+                                         c_f, c_vp, c_ll, c_ll, c_ll, c_ll, c_vp, c_sz, c_vp]),
+    "oess_maskclip_refine_phase_ms": (c_int, [c_vp, c_ll, c_ll, c_ll, c_ll, c_int, c_int, c_int, c_int, c_vp, c_int, c_ll, c_ll, c_int,
+                                              c_f, c_f, c_vp, c_ll, c_ll, c_ll, c_ll, c_vp, c_sz, c_vp, c_vp]),
 }
 
 _lib = None

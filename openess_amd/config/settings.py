@@ -11,6 +11,8 @@ from the frame on the GPU instead of reading a directory of maps
 appends SLIC's connectivity pass, and `online_slic_segments` must then be about half the pooling size.
 `online_teacher_precision: fp32` in the `clip:` block runs the online MaskCLIP teacher (`pl_sources: online_maskclip`) through
 its fp32 forward; the student's step is not affected.
+`online_maskclip_refine: True` there (with the optional `online_maskclip_pd_thresh` 0.5 / `online_maskclip_ks_thresh` 1.0) takes
+that teacher's labels from MaskCLIP's refined output: prompt denoising and key smoothing.
 Quirk reproduced on purpose: `if_linear_probing` is read from the `clip:` block only (settings.py:258), so the
 reference's config/linear_probe/** files, which put it at top level, dispatch to OpenESSModel.
 """
@@ -198,3 +200,15 @@ class Settings:
         self.online_teacher_precision = c.get('online_teacher_precision', 'bf16')
         if self.online_teacher_precision not in ('bf16', 'fp32'):
             raise ValueError(f"clip.online_teacher_precision must be 'bf16' or 'fp32', got {self.online_teacher_precision!r}")
+        # MaskCLIP's test-time refinement of the online teacher's logits: prompt denoising at pd_thresh and key
+        # smoothing at ks_thresh before the resize and the argmax, in either teacher precision.  Only with `pl_sources:
+        # online_maskclip`, which the trainers check; the thresholds are MaskClipHead's defaults in the reference.
+        self.online_maskclip_refine = c.get('online_maskclip_refine', False)
+        if not isinstance(self.online_maskclip_refine, bool):
+            raise ValueError(f"clip.online_maskclip_refine must be True or False, got {self.online_maskclip_refine!r}")
+        self.online_maskclip_pd_thresh = c.get('online_maskclip_pd_thresh', 0.5)
+        self.online_maskclip_ks_thresh = c.get('online_maskclip_ks_thresh', 1.0)
+        for key in ('online_maskclip_pd_thresh', 'online_maskclip_ks_thresh'):
+            v = getattr(self, key)
+            if isinstance(v, bool) or not isinstance(v, (int, float)) or not 0 <= v < float('inf'):
+                raise ValueError(f"clip.{key} must be a finite number >= 0, got {v!r}")

@@ -1114,6 +1114,104 @@ def linear_tokens_f32(x, packed, bias, Cout, act=None, residual=None, out=None):
     return out
 
 
+# ---- K26: MaskCLIP's refinement of the class logits (prompt denoising + key smoothing)
+MASKCLIP_REFINE_MAX_K, MASKCLIP_REFINE_MAX_L, MASKCLIP_REFINE_MAX_C = 32, 4096, 1024
+_REFINE_K_DTYPE = {torch.float32: 0, torch.bfloat16: 1}        # OESS_MASKCLIP_K_F32 / OESS_MASKCLIP_K_BF16
+
+
+def _distinct_elements(t):
+    """no two index tuples of `t` share an address: sorted by stride, every stride clears the span of the smaller ones"""
+    span = 0
+    for size, stride in sorted(((s, st) for s, st in zip(t.shape, t.stride()) if s > 1), key=lambda p: p[1]):
+        if stride <= span:
+            return False
+        span += (size - 1) * stride
+    return True
+
+
+def _byte_range(t):
+    lo = t.data_ptr()
+    return lo, lo + (sum((s - 1) * st for s, st in zip(t.shape, t.stride())) + 1) * t.element_size()
+
+
+def _maskclip_refine_check(logits, k, pd_thresh, ks_thresh, out):
+    what = "maskclip_refine"
+    if not isinstance(logits, torch.Tensor) or logits.dtype != torch.float32 or logits.ndim != 4:
+        raise ValueError(f"{what}: logits must be fp32 [B, K, H, W]")
+    B, K, H, W = logits.shape
+    if B < 1 or not 1 <= K <= MASKCLIP_REFINE_MAX_K or H < 1 or W < 1 or H * W > MASKCLIP_REFINE_MAX_L:
+        raise ValueError(f"{what}: logits {tuple(logits.shape)} outside B >= 1, 1 <= K <= {MASKCLIP_REFINE_MAX_K}, "
+                         f"1 <= H W <= {MASKCLIP_REFINE_MAX_L}")
+    if any(s < 0 for s in logits.stride()):
+        raise ValueError(f"{what}: logits must not have negative strides")
+    for name, v in (("pd_thresh", pd_thresh), ("ks_thresh", ks_thresh)):
+        if isinstance(v, bool) or not isinstance(v, (int, float)) or not 0 <= v < float("inf"):
+            raise ValueError(f"{what}: {name} must be a finite number >= 0, got {v!r}")
+    C = 0
+    if k is not None:
+        if not isinstance(k, torch.Tensor) or k.dtype not in _REFINE_K_DTYPE or k.ndim != 3 or k.device != logits.device:
+            raise ValueError(f"{what}: k must be fp32 or bf16 [B, H W, C] on {logits.device}")
+        C = k.shape[2]
+        if tuple(k.shape[:2]) != (B, H * W) or C < 64 or C % 64 or C > MASKCLIP_REFINE_MAX_C:
+            raise ValueError(f"{what}: k {tuple(k.shape)} must be [{B}, {H * W}, C] with C a multiple of 64 up to {MASKCLIP_REFINE_MAX_C}")
+        if k.stride(2) != 1 or (H * W > 1 and k.stride(1) < C) or (B > 1 and k.stride(0) < (H * W - 1) * k.stride(1) + C):
+            raise ValueError(f"{what}: k must have dense channels, a row stride >= {C} and images that do not overlap")
+    if out is not None:
+        if not isinstance(out, torch.Tensor) or out.dtype != torch.float32 or out.device != logits.device \
+                or tuple(out.shape) != (B, K, H, W) or any(s < 0 for s in out.stride()) or not _distinct_elements(out):
+            raise ValueError(f"{what}: out must be fp32 {[B, K, H, W]} on {logits.device} with distinct elements")
+        (a0, a1), (b0, b1) = _byte_range(out), _byte_range(logits)
+        if a0 < b1 and b0 < a1:
+            raise ValueError(f"{what}: out must not overlap logits")
+    return B, K, H, W, C
+
+
+def _maskclip_refine_args(logits, k, out, C):
+    B, K, H, W = logits.shape
+    L = H * W
+    krs = kis = 0
+    if k is not None:
+        krs = k.stride(1) if L > 1 else C
+        kis = k.stride(0) if B > 1 else L * krs
+    return (_ptr(logits), *logits.stride(), B, K, H, W, _ptr(k), _REFINE_K_DTYPE[k.dtype] if k is not None else 0, krs, kis, C)
+
+
+def maskclip_refine(logits, k, pd_thresh=0.5, ks_thresh=1.0, out=None):
+    """MaskCLIP's test-time refinement (MaskClipHead.refine_output of the reference, oess_maskclip_refine_f32).
+    logits: fp32 [B, K, H, W], any strides.  Prompt denoising (pd_thresh > 0): a class whose softmax(100 logits) confidence stays
+    below pd_thresh on every pixel of an image gets the logit -100 there.  Key smoothing (k given and ks_thresh > 0): P =
+    softmax(100 denoised logits); k: the last layer's keys [B, H W, C] in fp32 or bf16 as a strided view (dense channels), each
+    channel divided by max(its norm over the tokens, 1e-12); a pixel with max P < ks_thresh takes its row of (k^ k^T) P.
+    Returns probabilities [B, K, H, W] in the logits' layout when smoothing runs, the denoised logits otherwise.  The input is
+    not modified (the reference writes the -100 rows into it).  fp32 arithmetic, no atomics: two calls give the same bits."""
+    B, K, H, W, C = _maskclip_refine_check(logits, k, pd_thresh, ks_thresh, out)
+    _need_gpu(logits, k, out)
+    lib = _lib.load()
+    if out is None:
+        out = torch.empty_like(logits)
+        if not _distinct_elements(out):                  # a broadcast input: empty_like keeps its zero strides
+            out = torch.empty(logits.shape, dtype=torch.float32, device=logits.device)
+    ws = _workspace(lib.oess_maskclip_refine_workspace_bytes(B, K, H, W, C), logits.device, tag="maskclip_refine")
+    _lib.check(lib.oess_maskclip_refine_f32(*_maskclip_refine_args(logits, k, out, C), float(pd_thresh), float(ks_thresh), _ptr(out),
+                                            *out.stride(), _ptr(ws), ws.numel(), _stream()), "oess_maskclip_refine_f32")
+    _bump(out)
+    return out
+
+
+def maskclip_refine_phase_ms(logits, k, pd_thresh=0.5, ks_thresh=1.0):
+    """Milliseconds of the five kernels of one hip.maskclip_refine call (confidence | mask + softmax | k^T P per chunk | chunk sum
+    + norms | k Hm + select), HIP events between the same launches.  Synchronises: a measurement aid."""
+    B, K, H, W, C = _maskclip_refine_check(logits, k, pd_thresh, ks_thresh, None)
+    _need_gpu(logits, k)
+    lib = _lib.load()
+    out = torch.empty(logits.shape, dtype=torch.float32, device=logits.device)
+    ws = _workspace(lib.oess_maskclip_refine_workspace_bytes(B, K, H, W, C), logits.device, tag="maskclip_refine")
+    ms = (ctypes.c_float * 5)()
+    _lib.check(lib.oess_maskclip_refine_phase_ms(*_maskclip_refine_args(logits, k, out, C), float(pd_thresh), float(ks_thresh), _ptr(out),
+                                                 *out.stride(), _ptr(ws), ws.numel(), ms, _stream()), "oess_maskclip_refine_phase_ms")
+    return dict(zip(("conf", "prob", "gram", "hm", "apply"), (float(v) for v in ms)))
+
+
 # scratch of oess_norm_reduce_finalize_tile_stats (per-slice double sums + last-block tickets; tickets are kept zero by the kernel)
 _STATS_SCRATCH = {}
 

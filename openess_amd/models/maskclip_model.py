@@ -17,6 +17,11 @@ Every module also has `forward_fp32` (K25): the same graph in the reference's ar
 (oess_layernorm_f32, oess_attention_d64_f32, oess_linear_tokens_f32 on the f32-input MFMA), fp32 operands in caches of their
 own; the patch embedding there is a re-layout of the corner-padded image into [B hp wp, 3 * 16 * 16] rows and a token GEMM.
 
+MaskCLIP's test-time refinement (K26; MaskClipHead.refine_output, :224-250, whose call the reference comments out at :213-214):
+`forward(img, refine=True)` / `forward_fp32(img, refine=True)` run cls_seg -> refine_output -> resize, with the last layer's keys
+(:519-533; forward_key_path) and prompt denoising + key smoothing on hip.maskclip_refine (oess_maskclip_refine_f32).  Off by
+default: refine=False runs no key GEMM and returns what it always returned.
+
 Frozen (the reference sets requires_grad=False on encoder and decoder, :888-891): inference only.
 The reference trainers construct this model but never call it; here it is callable as an online
 teacher: `maskClipFeatureExtractor(img) -> logits [B, K, H, W]`."""
@@ -70,8 +75,8 @@ class TransformerEncoderLayer(nn.Module):
         self.attn = _Attn(embed_dims, num_heads)
         self.ln2 = nn.LayerNorm(embed_dims, eps=1e-6)
         self.ffn = _FFN(embed_dims, feedforward_channels)
-        self._pw = {k: engine.PackedWeight() for k in ('qkv', 'v', 'out', 'fc1', 'fc2')}
-        self._pw32 = {k: engine.PackedWeightF32() for k in ('qkv', 'v', 'out', 'fc1', 'fc2')}
+        self._pw = {k: engine.PackedWeight() for k in ('qkv', 'v', 'out', 'fc1', 'fc2', 'k', 'k_out')}
+        self._pw32 = {k: engine.PackedWeightF32() for k in ('qkv', 'v', 'out', 'fc1', 'fc2', 'k', 'k_out')}
 
     def _ffn_fp32(self, x):
         y = hip.layer_norm_tokens_f32(x, self.ln2.weight, self.ln2.bias, self.ln2.eps)
@@ -97,6 +102,14 @@ class TransformerEncoderLayer(nn.Module):
         v = _linear_tokens_f32(v, a.out_proj.weight, a.out_proj.bias, self._pw32['out'], residual=x)
         return self._ffn_fp32(v)
 
+    def forward_key_path_fp32(self, x):
+        """forward_key_path on fp32 tokens."""
+        a = self.attn.attn
+        C = x.shape[1]
+        y = hip.layer_norm_tokens_f32(x, self.ln1.weight, self.ln1.bias, self.ln1.eps)
+        k = _linear_tokens_f32(y, a.in_proj_weight[C:2 * C], a.in_proj_bias[C:2 * C], self._pw32['k'])
+        return _linear_tokens_f32(k, a.out_proj.weight, a.out_proj.bias, self._pw32['k_out'])
+
     def _ffn(self, x):
         y = hip.layer_norm_tokens(x, self.ln2.weight, self.ln2.bias, self.ln2.eps)
         fc1, fc2 = self.ffn.layers[0][0], self.ffn.layers[1]
@@ -120,6 +133,15 @@ class TransformerEncoderLayer(nn.Module):
         v = _linear_tokens(y, a.in_proj_weight[2 * C:], a.in_proj_bias[2 * C:], self._pw['v'])
         v = _linear_tokens(v, a.out_proj.weight, a.out_proj.bias, self._pw['out'], residual=x)
         return self._ffn(v)
+
+    def forward_key_path(self, x):
+        """:519-533 with return_qkv, the k of q, k, v: k = out_proj(in_proj_k(ln1(x))), rows C:2C of in_proj; no residual (only v
+        gets `+= x`) and no FFN.  The keys MaskClipHead.refine_output smooths with (K26); packed operands of its own."""
+        a = self.attn.attn
+        C = x.shape[1]
+        y = hip.layer_norm_tokens(x, self.ln1.weight, self.ln1.bias, self.ln1.eps)
+        k = _linear_tokens(y, a.in_proj_weight[C:2 * C], a.in_proj_bias[C:2 * C], self._pw['k'])
+        return _linear_tokens(k, a.out_proj.weight, a.out_proj.bias, self._pw['k_out'])
 
 
 class VisionTransformer(nn.Module):
@@ -159,7 +181,9 @@ class VisionTransformer(nn.Module):
         return self._pos_cache[key]
 
     @torch.no_grad()
-    def forward(self, img):
+    def forward(self, img, return_k=False):
+        """return_k: (v_map, k) with k the last layer's keys [B, hp wp, C] (:841-848; forward_key_path), a view of the token
+        matrix past its class-token rows, not normalised by ln1 of the encoder (only v is, :846)."""
         B, Cin, H, W = img.shape
         p, C = self.patch_size, self.embed_dims
         Hp, Wp = (H + p - 1) // p * p, (W + p - 1) // p * p
@@ -178,12 +202,15 @@ class VisionTransformer(nn.Module):
             x = layer(x, B, L)
         v = self.layers[-1].forward_value_path(x)
         v = hip.layer_norm_tokens(v, self.ln1.weight, self.ln1.bias, self.ln1.eps)
-        return v.view(B, L, C)[:, 1:].reshape(B, hp, wp, C).permute(0, 3, 1, 2)         # logical NCHW, NHWC memory
+        v_map = v.view(B, L, C)[:, 1:].reshape(B, hp, wp, C).permute(0, 3, 1, 2)        # logical NCHW, NHWC memory
+        if return_k:
+            return v_map, self.layers[-1].forward_key_path(x).view(B, L, C)[:, 1:]
+        return v_map
 
 
     @torch.no_grad()
-    def forward_fp32(self, img):
-        """forward in fp32: v_map [B, 768, H/16, W/16] fp32.  Stride equals kernel in the patch embedding, so it is a re-layout
+    def forward_fp32(self, img, return_k=False):
+        """forward in fp32: v_map [B, 768, H/16, W/16] fp32 (return_k: and the fp32 keys, as in forward).  Stride equals kernel in the patch embedding, so it is a re-layout
         of the corner-padded image into one row per patch, (c, dy, dx) order like the flattened weight, and a token GEMM."""
         B, Cin, H, W = img.shape
         p, C = self.patch_size, self.embed_dims
@@ -203,14 +230,20 @@ class VisionTransformer(nn.Module):
             x = layer.forward_fp32(x, B, L)
         v = self.layers[-1].forward_value_path_fp32(x)
         v = hip.layer_norm_tokens_f32(v, self.ln1.weight, self.ln1.bias, self.ln1.eps)
-        return v.view(B, L, C)[:, 1:].reshape(B, hp, wp, C).permute(0, 3, 1, 2)         # logical NCHW, NHWC memory
+        v_map = v.view(B, L, C)[:, 1:].reshape(B, hp, wp, C).permute(0, 3, 1, 2)        # logical NCHW, NHWC memory
+        if return_k:
+            return v_map, self.layers[-1].forward_key_path_fp32(x).view(B, L, C)[:, 1:]
+        return v_map
 
 
 class MaskClipHead(nn.Module):
     """maskclip_model.py:52-222 (vit=True): logits = conv2d(normalize(proj(v)), text_embeddings)."""
 
-    def __init__(self, text_categories=16, text_channels=512, in_channels=768):
+    def __init__(self, text_categories=16, text_channels=512, in_channels=768, ks_thresh=1, pd_thresh=0.5):
         super().__init__()
+        if not 0 <= ks_thresh < float('inf') or not 0 <= pd_thresh < float('inf'):
+            raise ValueError(f"ks_thresh and pd_thresh must be finite and >= 0, got {ks_thresh!r}, {pd_thresh!r}")
+        self.ks_thresh, self.pd_thresh = ks_thresh, pd_thresh            # :72-73, :124-125
         self.align_corners = False
         self.num_classes = text_categories
         self.register_buffer('text_embeddings', torch.randn(text_categories, text_channels))
@@ -241,16 +274,23 @@ class MaskClipHead(nn.Module):
         logits = _linear_tokens_f32(f2, self.text_embeddings, None, self._pw_text32)
         return v_map, logits.view(B, hp, wp, -1).permute(0, 3, 1, 2)
 
+    @torch.no_grad()
+    def refine_output(self, output, k):
+        """:224-250: prompt denoising (pd_thresh) and key smoothing (ks_thresh, k [B, hp wp, C] or None) of the fp32 logits
+        [B, K, hp, wp] on hip.maskclip_refine.  Returns a new tensor (the reference writes the -100 rows into `output`):
+        probabilities when smoothing runs, the denoised logits otherwise."""
+        return hip.maskclip_refine(output, k, pd_thresh=self.pd_thresh, ks_thresh=self.ks_thresh)
+
 
 class maskClipFeatureExtractor(nn.Module):
     """maskclip_model.py:854-915.  Checkpoint / text-embedding / projection files are optional here (the reference
     requires them): pass paths to load them with the reference's key mapping, or load a state_dict afterwards."""
 
     def __init__(self, text_embeddings_path=None, visual_projs_path=None, text_categories=16, maskclip_checkpoint=None,
-                 preprocessing=None, test_cfg=dict(mode='whole'), img_size=(224, 224)):
+                 preprocessing=None, test_cfg=dict(mode='whole'), img_size=(224, 224), ks_thresh=1, pd_thresh=0.5):
         super().__init__()
         self.encoder = VisionTransformer(img_size=img_size)
-        self.decoder = MaskClipHead(text_categories=text_categories)
+        self.decoder = MaskClipHead(text_categories=text_categories, ks_thresh=ks_thresh, pd_thresh=pd_thresh)
         self.align_corners = self.decoder.align_corners
         self.num_classes = self.decoder.num_classes
         self.test_cfg = test_cfg
@@ -272,15 +312,27 @@ class maskClipFeatureExtractor(nn.Module):
     # (Two half batches on two HIP streams -- the tower couples no samples, and its token GEMMs leave 15-20 % of their last round of
     #  tiles empty -- were measured in round 5: 4.17 vs 4.22 ms, bit-identical; not kept.)
     @torch.no_grad()
-    def forward(self, img):
-        v_map = self.encoder(img)
+    def forward(self, img, refine=False):
+        """refine=True (K26): MaskCLIP's order cls_seg -> refine_output -> resize -> (argmax), with the decoder's thresholds; the
+        result then holds resized probabilities (ks_thresh > 0) instead of logits.  refine=False runs no key GEMM."""
+        if not refine:
+            v_map = self.encoder(img)
+            _, logits = self.decoder(v_map)
+            return hip.bilinear_resize(logits.float(), size=(img.shape[2], img.shape[3]), align_corners=self.align_corners)
+        v_map, k = self.encoder(img, return_k=True)
         _, logits = self.decoder(v_map)
-        return hip.bilinear_resize(logits.float(), size=(img.shape[2], img.shape[3]), align_corners=self.align_corners)
+        refined = self.decoder.refine_output(logits.float(), k)
+        return hip.bilinear_resize(refined, size=(img.shape[2], img.shape[3]), align_corners=self.align_corners)
 
     @torch.no_grad()
-    def forward_fp32(self, img):
+    def forward_fp32(self, img, refine=False):
         """The tower in the reference's arithmetic: fp32 logits [B, K, H, W] (the online teacher of
-        `online_teacher_precision: fp32`; its argmax is the dense-CLIP pseudo-label map)."""
-        v_map = self.encoder.forward_fp32(img.float())
+        `online_teacher_precision: fp32`; its argmax is the dense-CLIP pseudo-label map).  refine: as in forward, on fp32 keys."""
+        if not refine:
+            v_map = self.encoder.forward_fp32(img.float())
+            _, logits = self.decoder.forward_fp32(v_map)
+            return hip.bilinear_resize(logits, size=(img.shape[2], img.shape[3]), align_corners=self.align_corners)
+        v_map, k = self.encoder.forward_fp32(img.float(), return_k=True)
         _, logits = self.decoder.forward_fp32(v_map)
-        return hip.bilinear_resize(logits, size=(img.shape[2], img.shape[3]), align_corners=self.align_corners)
+        refined = self.decoder.refine_output(logits, k)
+        return hip.bilinear_resize(refined, size=(img.shape[2], img.shape[3]), align_corners=self.align_corners)

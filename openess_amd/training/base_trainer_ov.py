@@ -58,6 +58,17 @@ def online_slic_rows(H, W, n_segments, pool_size, connectivity):
     return bound
 
 
+def online_maskclip_refine(settings):
+    """`online_maskclip_refine: True` (clip block): the online MaskCLIP teacher's labels come from the refined
+    forward.  None when the key is off, else the tower's {'pd_thresh', 'ks_thresh'} (validated by Settings and again by
+    MaskClipHead).  Refused without `pl_sources: online_maskclip`: there is no teacher to refine."""
+    if not getattr(settings, 'online_maskclip_refine', False):
+        return None
+    if getattr(settings, 'pl_sources', '') != 'online_maskclip':
+        raise ValueError(f"online_maskclip_refine: True needs pl_sources: online_maskclip, got {getattr(settings, 'pl_sources', '')!r}")
+    return {'pd_thresh': getattr(settings, 'online_maskclip_pd_thresh', 0.5), 'ks_thresh': getattr(settings, 'online_maskclip_ks_thresh', 1.0)}
+
+
 class BaseTrainer(object):
     is_training = True
     online_slic_segments = None      # SLIC's n_segments under `superpixel_sources: online_slic`, set by __init__
@@ -67,6 +78,7 @@ class BaseTrainer(object):
         self.is_training = bool(train)           # reference: every trainer's __init__(settings, train=True) (pretrain_trainer.py:82-83)
         # before anything is built: what `superpixel_sources: online_slic` cannot serve is refused here
         self.online_slic_segments = online_slic_segments(settings, self.pooling_size())
+        online_maskclip_refine(settings)         # `online_maskclip_refine: True` without its teacher is refused here too
         if not torch.cuda.is_available():
             raise RuntimeError("openess_amd trainers need the GPU (no CPU fallback in the product path)")
         self.device = torch.device('cuda', torch.cuda.current_device())

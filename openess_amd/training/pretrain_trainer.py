@@ -1,8 +1,10 @@
 """OpenESSPretrainModel (training/pretrain_trainer.py:81-667): stage-1 trainer, F2E contrastive + T2E
 pseudo-label distillation.  The step itself lives in pretrain_step.PretrainStep."""
+import functools
+
 import torch
 
-from .base_trainer_ov import BaseTrainer
+from .base_trainer_ov import BaseTrainer, online_maskclip_refine
 from .pretrain_step import PretrainStep
 
 
@@ -46,7 +48,10 @@ class OpenESSPretrainModel(BaseTrainer):
         if getattr(s, 'pl_sources', '') == 'online_maskclip':          # extension: labels from the frozen tower, in the step
             from ..models.maskclip_model import maskClipFeatureExtractor
             kw = {k: getattr(s, k) for k in ('text_embeddings_path', 'visual_projs_path', 'maskclip_checkpoint') if getattr(s, k, None)}
-            online = maskClipFeatureExtractor(text_categories=s.semseg_num_classes, **kw).to(self.device).eval()
+            # `online_maskclip_refine: True` (optional YAML keys, clip block): the labels are the argmax of the
+            # refined forward (prompt denoising + key smoothing at the two thresholds), in either precision
+            refine = online_maskclip_refine(s)
+            online = maskClipFeatureExtractor(text_categories=s.semseg_num_classes, **kw, **(refine or {})).to(self.device).eval()
             # `online_teacher_precision: fp32` (optional YAML key, clip block): the labels are the argmax of the
             # tower's fp32 forward.  PretrainStep takes any callable; the student's step stays bf16.
             precision = getattr(s, 'online_teacher_precision', 'bf16')
@@ -54,6 +59,8 @@ class OpenESSPretrainModel(BaseTrainer):
                 raise ValueError(f"online_teacher_precision must be 'bf16' or 'fp32', got {precision!r}")
             if precision == 'fp32':
                 online = online.forward_fp32
+            if refine is not None:
+                online = functools.partial(online, refine=True)
         self.step = PretrainStep(config_option=s.config_option, online_teacher=online, num_classes=s.semseg_num_classes, img_size=tuple(s.img_size_b),
                                  nr_events_data=s.nr_events_data_b, nr_temporal_bins=s.nr_temporal_bins_b,
                                  if_spatial_contrastive=s.if_spatial_contrastive,

@@ -2,10 +2,11 @@
 """How far the bf16 MaskCLIP tower's pseudo-labels sit from the fp32 tower's (K25): both forwards of the same weights on the same
 images, one JSON line: the argmax agreement (the fraction of pixels whose dense-CLIP label is the same), the relative RMS of the
 bf16 logits against the fp32 ones, and the milliseconds of each.  Without --checkpoint the weights are the seeded random fill of
-the tests (tests/vit_f32_cases.py tower_pair's); with the three files of a MaskCLIP checkpoint they are the real tower's.
+the tests (tests/vit_f32_cases.py tower_pair's); with the three files of a MaskCLIP checkpoint they are the real tower's.  --refine adds the share of labels MaskCLIP's refinement (K26, forward(img, refine=True)) changes in each
+precision, the agreement of the two refined label maps and the milliseconds of the refined forwards.
 
     python tools/eval_maskclip_precision.py [--batch 8] [--height 440] [--width 640] [--classes 11] [--seed 0]
-        [--checkpoint CKPT --text-embeddings PT --visual-projs PT]"""
+        [--checkpoint CKPT --text-embeddings PT --visual-projs PT] [--refine [--pd-thresh 0.5] [--ks-thresh 1.0]]"""
 import argparse
 import json
 import os
@@ -57,6 +58,9 @@ def main():
     ap.add_argument("--checkpoint")
     ap.add_argument("--text-embeddings")
     ap.add_argument("--visual-projs")
+    ap.add_argument("--refine", action="store_true", help="also the share of labels MaskCLIP's refinement changes (K26)")
+    ap.add_argument("--pd-thresh", type=float, default=0.5)
+    ap.add_argument("--ks-thresh", type=float, default=1.0)
     a = ap.parse_args()
     m = maskClipFeatureExtractor(text_embeddings_path=a.text_embeddings, visual_projs_path=a.visual_projs,
                                  text_categories=a.classes, maskclip_checkpoint=a.checkpoint)
@@ -72,6 +76,17 @@ def main():
            "weights": "checkpoint" if a.checkpoint else f"seeded fill {a.seed}", "argmax_agreement": round(agree, 6),
            "logits_rel_rms": float(f"{rel_rms:.4e}"), "bf16_ms": round(timed(lambda: m(img), a.iters, a.warmup), 3),
            "fp32_ms": round(timed(lambda: m.forward_fp32(img), a.iters, a.warmup), 3)}
+    if a.refine:
+        # K26: MaskCLIP's refinement (prompt denoising + key smoothing) at the decoder's thresholds: the share of the labels it
+        # changes in each precision, and how far the two refined label maps agree
+        m.decoder.pd_thresh, m.decoder.ks_thresh = a.pd_thresh, a.ks_thresh
+        rlo, rhi = m(img, refine=True), m.forward_fp32(img, refine=True)
+        res.update({"pd_thresh": a.pd_thresh, "ks_thresh": a.ks_thresh,
+                    "refine_changed_bf16": round(float((rlo.argmax(1) != lo.argmax(1)).double().mean()), 6),
+                    "refine_changed_fp32": round(float((rhi.argmax(1) != hi.argmax(1)).double().mean()), 6),
+                    "refined_argmax_agreement": round(float((rlo.argmax(1) == rhi.argmax(1)).double().mean()), 6),
+                    "bf16_refine_ms": round(timed(lambda: m(img, refine=True), a.iters, a.warmup), 3),
+                    "fp32_refine_ms": round(timed(lambda: m.forward_fp32(img, refine=True), a.iters, a.warmup), 3)})
     print(json.dumps(res))
 
 
