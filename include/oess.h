@@ -501,7 +501,27 @@ int oess_attention_d64_bf16(const void* qkv, long long qkv_row_stride, int B, in
 int oess_conv2d_wgrad_bf16(const void* x, long long x_pix_stride, int B, int H, int W, int Cin_x, const void* dy,
                            long long dy_pix_stride, int Cout, int Cin, int R, int S, int stride, int pad, int dil,
                            float* dw_oihw, void* workspace, size_t workspace_bytes, oess_stream_t stream);
-/* workspace: split-K partial tiles; any size >= one padded tile set works, 64 MiB lets the kernel use full parallelism */
+/* workspace: split-K partial tiles; any size >= one padded tile set works (a smaller one is OESS_ENOMEM), 64 MiB lets the
+ * kernel use full parallelism.  Nothing beyond workspace_bytes is touched, and what the workspace held before does not matter:
+ * every partial that is read was stored by this call. */
+/* Which kernel a call takes.  oess_conv2d_wgrad_bf16 is one entry point over the eight gradient kernels below and two reduce
+ * kernels; the choice depends on the geometry, on the byte extent of both tensors (pixel strides included) and on the workspace
+ * on offer.  oess_conv2d_wgrad_route makes the plan the launch itself executes (wgrad_plan, conv_wgrad.hip) and returns
+ * kernel | slices << 8 instead of launching: slices = partial tiles summed per element (>= 16: wgrad_reduce_wide_kernel,
+ * fewer: wgrad_reduce_kernel).  Negative = the OESS_E* the launch returns for these numbers (the launch also refuses null
+ * pointers).  Host only: no launch, no allocation, no runtime call, no device query. */
+#define OESS_WGRAD_REG_32 1            /* conv_wgrad_kernel<32>: register-staged, a tensor's byte extent reaches 2 GiB       */
+#define OESS_WGRAD_REG_64 2            /* conv_wgrad_kernel<64>                                                            */
+#define OESS_WGRAD_REG_128 3           /* conv_wgrad_kernel<128>                                                           */
+#define OESS_WGRAD_DMA_32 4            /* conv_wgrad_dma_kernel<32>: LDS-DMA, the general case (Cout <= 32)                */
+#define OESS_WGRAD_DMA_64 5            /* conv_wgrad_dma_kernel<64>: Cout <= 64                                            */
+#define OESS_WGRAD_DMA_128 6           /* conv_wgrad_dma_kernel<128>                                                       */
+#define OESS_WGRAD_STRIP_32 7          /* conv_wgrad_strip_kernel<32>: narrow full-resolution 3x3 'same' layers            */
+#define OESS_WGRAD_STRIP_64 8          /* conv_wgrad_strip_kernel<64>                                                      */
+#define OESS_WGRAD_KERNEL(route) ((route) & 0xff)
+#define OESS_WGRAD_SLICES(route) ((route) >> 8)
+int oess_conv2d_wgrad_route(int B, int H, int W, int Cin_x, int Cout, int Cin, int R, int S, int stride, int pad, int dil,
+                            long long x_pix_stride, long long dy_pix_stride, size_t workspace_bytes);
 
 /* ------------------------------------------------------------------------------------------
  * GPU-side decode of 8-bit single-channel PNG maps: pseudo-labels, superpixel ids, ground-truth labels.

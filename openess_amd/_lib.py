@@ -112,6 +112,7 @@ SIGNATURES = {
     "oess_bilinear_l2norm_nhwc_bf16": (c_int, [c_vp, c_ll, c_int, c_int, c_int, c_int, c_int, c_int, c_vp, c_ll, c_vp, c_vp]),
     "oess_conv2d_wgrad_bf16": (c_int, [c_vp, c_ll, c_int, c_int, c_int, c_int, c_vp, c_ll, c_int, c_int, c_int, c_int,
                                        c_int, c_int, c_int, c_vp, c_vp, c_sz, c_vp]),
+    "oess_conv2d_wgrad_route": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_ll, c_ll, c_sz]),
     "oess_bilinear_l2norm_pool_bwd_workspace_bytes": (c_sz, [c_int, c_int, c_int, c_int, c_int]),
     "oess_bilinear_l2norm_pool_bwd_bf16": (c_int, [c_vp, c_ll, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
                                                    c_f, c_vp, c_sz, c_vp, c_ll, c_vp]),

@@ -11,7 +11,8 @@
 // LDS tiles keep the natural [pixel][channel] order (row pitch 320 B = 64 mod 256: conflict-free tr reads).
 //
 // Workgroup: 128 (co) x 128 (kk) tile, 4 waves of 64x64, K-step = 64 output pixels of ONE output row
-// (no per-pixel div/mod), split-K over output rows, fp32 atomics into the OIHW gradient (pre-zeroed).
+// (no per-pixel div/mod), split-K over output rows: every workgroup stores its partial tile with plain stores into the
+// workspace and a reduce kernel sums the slices and WRITES every element of the OIHW gradient (no atomics, no pre-zeroing).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdlib.h>
@@ -637,35 +638,40 @@ __global__ __launch_bounds__(256) void wgrad_reduce_wide_kernel(const float* __r
     }
 }
 
-static inline size_t per_split_bytes(const WgradArgs& a, int tmv) { return (size_t)a.tiles_m * tmv * a.tiles_n * TN * sizeof(float); }
+// What wgrad_plan decides: the kernel (OESS_WGRAD_*), its launch shape and the reduce kernel.  Pure: a function of the call's
+// numbers alone (no pointer, no device query, no runtime call), so oess_conv2d_wgrad_route answers on any machine, and
+// oess_conv2d_wgrad_bf16 launches exactly what the query reports: one function, two callers.
+struct WgradPlan {
+    int kernel;                             // OESS_WGRAD_*
+    int tmv;                                // output channels per tile: 32 / 64 / 128
+    bool dma;                               // 32-bit buffer offsets reach both tensors
+    int Ho, Wo, Kdim, tiles_m, tiles_n;
+    int slices;                             // partial tiles summed per element (grid.y of the gradient kernel)
+    int rows_per_split;                     // tiled kernels: output rows (of B * Ho) per slice
+    int chunks, rsplit, rows_per;           // strip kernel: 64-channel chunks, row ranges per strip, rows per range
+    bool wide_reduce;                       // wgrad_reduce_wide_kernel (>= 16 slices) instead of wgrad_reduce_kernel
+};
 
-}  // namespace
-
-extern "C" {
-
-int oess_conv2d_wgrad_bf16(const void* x, long long x_pix_stride, int B, int H, int W, int Cin_x, const void* dy,
-                           long long dy_pix_stride, int Cout, int Cin, int R, int S, int stride, int pad, int dil,
-                           float* dw_oihw, void* workspace, size_t workspace_bytes, oess_stream_t stream) {
-    if (!x || !dy || !dw_oihw || !workspace || B <= 0 || H <= 0 || W <= 0 || Cin <= 0 || Cin_x < Cin || (Cin_x & 7) || Cout <= 0 ||
-        (Cout & 7) || R <= 0 || S <= 0 || stride <= 0 || pad < 0 || dil <= 0 || (x_pix_stride & 7) || (dy_pix_stride & 7))
+int wgrad_plan(int B, int H, int W, int Cin_x, int Cout, int Cin, int R, int S, int stride, int pad, int dil,
+               long long x_pix_stride, long long dy_pix_stride, size_t workspace_bytes, WgradPlan* p) {
+    if (B <= 0 || H <= 0 || W <= 0 || Cin <= 0 || Cin_x < Cin || (Cin_x & 7) || Cout <= 0 || (Cout & 7) || R <= 0 || S <= 0 ||
+        stride <= 0 || pad < 0 || dil <= 0 || (x_pix_stride & 7) || (dy_pix_stride & 7))
         return OESS_EINVAL;
-    WgradArgs a;
-    a.x = (const uint16_t*)x; a.xps = x_pix_stride; a.dy = (const uint16_t*)dy; a.dps = dy_pix_stride; a.part = (float*)workspace;
-    a.B = B; a.H = H; a.W = W; a.Cin = Cin; a.Cin_x = Cin_x; a.Cout = Cout;
-    a.R = R; a.S = S; a.stride = stride; a.pad = pad; a.dil = dil;
-    a.Ho = (H + 2 * pad - dil * (R - 1) - 1) / stride + 1;
-    a.Wo = (W + 2 * pad - dil * (S - 1) - 1) / stride + 1;
-    if (a.Ho <= 0 || a.Wo <= 0) return OESS_EINVAL;
-    a.Kdim = R * S * Cin_x;
+    p->Ho = (H + 2 * pad - dil * (R - 1) - 1) / stride + 1;
+    p->Wo = (W + 2 * pad - dil * (S - 1) - 1) / stride + 1;
+    if (p->Ho <= 0 || p->Wo <= 0) return OESS_EINVAL;
+    p->Kdim = R * S * Cin_x;
     const int tmv = Cout <= 32 ? 32 : (Cout <= 64 ? 64 : TM);      // narrow layers: 32- / 64-row tiles (-10 % on the decoder's 32/64-channel layers)
-    a.tiles_m = (Cout + tmv - 1) / tmv;
-    a.tiles_n = (a.Kdim + TN - 1) / TN;
-    a.rows_total = B * a.Ho;
-    const int tiles = a.tiles_m * a.tiles_n;
+    p->tmv = tmv;
+    p->tiles_m = (Cout + tmv - 1) / tmv;
+    p->tiles_n = (p->Kdim + TN - 1) / TN;
+    const int rows_total = B * p->Ho;
+    const int tiles = p->tiles_m * p->tiles_n;
     const int target = 512;
     const long long x_bytes = (((long long)B * H * W - 1) * x_pix_stride + Cin_x) * 2;
-    const long long d_bytes = (((long long)B * a.Ho * a.Wo - 1) * dy_pix_stride + Cout) * 2;
+    const long long d_bytes = (((long long)B * p->Ho * p->Wo - 1) * dy_pix_stride + Cout) * 2;
     const bool dma = x_bytes < 0x7ffffff0ll && d_bytes < 0x7ffffff0ll;      // 32-bit buffer offsets reach both tensors
+    p->dma = dma;
     // split-K over output rows.  Register-staged form: ~512 workgroups (1024: +3 % step time on frame2recon from the larger
     // partial-sum traffic).  LDS-DMA form (64 KB of LDS: exactly two workgroups per CU = 512 slots): whichever of floor / ceil
     // (512 / tiles) needs fewer rounds per split -- 36 tiles x 15 splits = 540 workgroups was a 1.05-round launch
@@ -675,43 +681,74 @@ int oess_conv2d_wgrad_bf16(const void* x, long long x_pix_stride, int B, int H, 
         auto cost = [&](int sp) { return (double)(((long long)tiles * sp + target - 1) / target) / (double)sp; };
         splits = cost(lo) < cost(hi) ? lo : hi;
     }
-    const size_t per_split = (size_t)a.tiles_m * tmv * a.tiles_n * TN * sizeof(float);
+    const size_t per_split = (size_t)p->tiles_m * tmv * p->tiles_n * TN * sizeof(float);
     if (per_split > workspace_bytes) return OESS_ENOMEM;
     if ((size_t)splits * per_split > workspace_bytes) splits = (int)(workspace_bytes / per_split);
-    if (splits > a.rows_total) splits = a.rows_total;
+    if (splits > rows_total) splits = rows_total;
     if (splits < 1) splits = 1;
-    a.rows_per_split = (a.rows_total + splits - 1) / splits;
-    splits = (a.rows_total + a.rows_per_split - 1) / a.rows_per_split;
-    hipStream_t st = (hipStream_t)stream;
+    p->rows_per_split = (rows_total + splits - 1) / splits;
+    splits = (rows_total + p->rows_per_split - 1) / p->rows_per_split;
+    p->kernel = (dma ? OESS_WGRAD_DMA_32 : OESS_WGRAD_REG_32) + (tmv == 32 ? 0 : (tmv == 64 ? 1 : 2));
+    p->slices = splits;
+    p->chunks = p->rsplit = p->rows_per = 0;
     // narrow full-resolution 3x3 layers: the whole (Cout x 9 x 64-channel) gradient per workgroup, X fetched once as a halo
     // (measured against the 128-wide tiling: 440x640 64->32 390 -> 342 us, 220x320 128->64 267 -> 182; 220x320 64->64 118 -> 131:
     //  one 64-channel chunk with 64 output channels stays on the generic form)
-    if (dma && R == 3 && S == 3 && stride == 1 && pad == 1 && dil == 1 && Cout <= 64 && (Cin_x % 64) == 0 && a.Wo >= KP &&
-        (long long)a.rows_total * a.Wo >= 100000) {
+    if (dma && R == 3 && S == 3 && stride == 1 && pad == 1 && dil == 1 && Cout <= 64 && (Cin_x % 64) == 0 && p->Wo >= KP &&
+        (long long)rows_total * p->Wo >= 100000) {
         const int chunks = Cin_x / 64;
-        const int spr = (a.Wo + KP - 1) / KP, strips = B * spr;
+        const int spr = (p->Wo + KP - 1) / KP, strips = B * spr;
         int rsplit = (target / chunks) / strips;                     // row ranges per strip: at most 512 workgroups in all (one round)
         if (rsplit < 1) rsplit = 1;
-        if (rsplit > a.Ho) rsplit = a.Ho;
-        int rows_per = (a.Ho + rsplit - 1) / rsplit;
-        rsplit = (a.Ho + rows_per - 1) / rows_per;
+        if (rsplit > p->Ho) rsplit = p->Ho;
+        const int rows_per = (p->Ho + rsplit - 1) / rsplit;
+        rsplit = (p->Ho + rows_per - 1) / rows_per;
         const long long units = (long long)strips * rsplit;
-        if (units * per_split_bytes(a, tmv) <= workspace_bytes && units <= 65535) {
-            static bool attr2 = false;
-            if (!attr2) {
-                (void)hipFuncSetAttribute((const void*)&conv_wgrad_strip_kernel<32>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-                (void)hipFuncSetAttribute((const void*)&conv_wgrad_strip_kernel<64>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-                attr2 = true;
-            }
-            if (tmv == 32) hipLaunchKernelGGL(conv_wgrad_strip_kernel<32>, dim3(chunks, (unsigned)units), dim3(WG), ST_LDS, st, a, rsplit, rows_per);
-            else hipLaunchKernelGGL(conv_wgrad_strip_kernel<64>, dim3(chunks, (unsigned)units), dim3(WG), ST_LDS, st, a, rsplit, rows_per);
-            splits = (int)units;
-            goto reduce;
+        if ((unsigned long long)units * per_split <= workspace_bytes && units <= 65535) {      // otherwise: the tiled kernel above
+            p->kernel = tmv == 32 ? OESS_WGRAD_STRIP_32 : OESS_WGRAD_STRIP_64;
+            p->slices = (int)units;
+            p->chunks = chunks; p->rsplit = rsplit; p->rows_per = rows_per;
         }
     }
-    {
-    const dim3 grid(tiles, splits);
-    if (dma) {
+    p->wide_reduce = p->slices >= 16;       // many slices: 8 split lanes per element (fixed-order combine)
+    return OESS_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int oess_conv2d_wgrad_route(int B, int H, int W, int Cin_x, int Cout, int Cin, int R, int S, int stride, int pad, int dil,
+                            long long x_pix_stride, long long dy_pix_stride, size_t workspace_bytes) {
+    WgradPlan p;
+    const int rc = wgrad_plan(B, H, W, Cin_x, Cout, Cin, R, S, stride, pad, dil, x_pix_stride, dy_pix_stride, workspace_bytes, &p);
+    return rc != OESS_OK ? rc : (p.kernel | p.slices << 8);
+}
+
+int oess_conv2d_wgrad_bf16(const void* x, long long x_pix_stride, int B, int H, int W, int Cin_x, const void* dy,
+                           long long dy_pix_stride, int Cout, int Cin, int R, int S, int stride, int pad, int dil,
+                           float* dw_oihw, void* workspace, size_t workspace_bytes, oess_stream_t stream) {
+    if (!x || !dy || !dw_oihw || !workspace) return OESS_EINVAL;
+    WgradPlan p;
+    const int rc = wgrad_plan(B, H, W, Cin_x, Cout, Cin, R, S, stride, pad, dil, x_pix_stride, dy_pix_stride, workspace_bytes, &p);
+    if (rc != OESS_OK) return rc;
+    WgradArgs a;
+    a.x = (const uint16_t*)x; a.xps = x_pix_stride; a.dy = (const uint16_t*)dy; a.dps = dy_pix_stride; a.part = (float*)workspace;
+    a.B = B; a.H = H; a.W = W; a.Cin = Cin; a.Cin_x = Cin_x; a.Cout = Cout;
+    a.R = R; a.S = S; a.stride = stride; a.pad = pad; a.dil = dil;
+    a.Ho = p.Ho; a.Wo = p.Wo; a.Kdim = p.Kdim;
+    a.tiles_m = p.tiles_m; a.tiles_n = p.tiles_n;
+    a.rows_total = B * p.Ho; a.rows_per_split = p.rows_per_split;
+    hipStream_t st = (hipStream_t)stream;
+    const dim3 grid(p.tiles_m * p.tiles_n, p.slices);              // the tiled kernels
+    if (p.kernel == OESS_WGRAD_STRIP_32 || p.kernel == OESS_WGRAD_STRIP_64) {
+        static bool attr2 = false;
+        if (!attr2) {
+            (void)hipFuncSetAttribute((const void*)&conv_wgrad_strip_kernel<32>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+            (void)hipFuncSetAttribute((const void*)&conv_wgrad_strip_kernel<64>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+            attr2 = true;
+        }
+    } else if (p.dma) {
         static bool attr = false;
         if (!attr) {
             (void)hipFuncSetAttribute((const void*)&conv_wgrad_dma_kernel<128>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
@@ -719,28 +756,34 @@ int oess_conv2d_wgrad_bf16(const void* x, long long x_pix_stride, int B, int H, 
             (void)hipFuncSetAttribute((const void*)&conv_wgrad_dma_kernel<32>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
             attr = true;
         }
-        const size_t lds = (size_t)2 * 2 * KP * 256;
-        if (tmv == 32) hipLaunchKernelGGL(conv_wgrad_dma_kernel<32>, grid, dim3(WG), lds, st, a);
-        else if (tmv == 64) hipLaunchKernelGGL(conv_wgrad_dma_kernel<64>, grid, dim3(WG), lds, st, a);
-        else hipLaunchKernelGGL(conv_wgrad_dma_kernel<128>, grid, dim3(WG), lds, st, a);
-    } else {
-        if (tmv == 32) hipLaunchKernelGGL(conv_wgrad_kernel<32>, grid, dim3(WG), 0, st, a);
-        else if (tmv == 64) hipLaunchKernelGGL(conv_wgrad_kernel<64>, grid, dim3(WG), 0, st, a);
-        else hipLaunchKernelGGL(conv_wgrad_kernel<128>, grid, dim3(WG), 0, st, a);
     }
+    const size_t lds = (size_t)2 * 2 * KP * 256;                   // the LDS-DMA kernels' 2-stage ring
+    switch (p.kernel) {
+    case OESS_WGRAD_STRIP_32:
+        hipLaunchKernelGGL(conv_wgrad_strip_kernel<32>, dim3(p.chunks, (unsigned)p.slices), dim3(WG), ST_LDS, st, a, p.rsplit, p.rows_per);
+        break;
+    case OESS_WGRAD_STRIP_64:
+        hipLaunchKernelGGL(conv_wgrad_strip_kernel<64>, dim3(p.chunks, (unsigned)p.slices), dim3(WG), ST_LDS, st, a, p.rsplit, p.rows_per);
+        break;
+    case OESS_WGRAD_DMA_32: hipLaunchKernelGGL(conv_wgrad_dma_kernel<32>, grid, dim3(WG), lds, st, a); break;
+    case OESS_WGRAD_DMA_64: hipLaunchKernelGGL(conv_wgrad_dma_kernel<64>, grid, dim3(WG), lds, st, a); break;
+    case OESS_WGRAD_DMA_128: hipLaunchKernelGGL(conv_wgrad_dma_kernel<128>, grid, dim3(WG), lds, st, a); break;
+    case OESS_WGRAD_REG_32: hipLaunchKernelGGL(conv_wgrad_kernel<32>, grid, dim3(WG), 0, st, a); break;
+    case OESS_WGRAD_REG_64: hipLaunchKernelGGL(conv_wgrad_kernel<64>, grid, dim3(WG), 0, st, a); break;
+    case OESS_WGRAD_REG_128: hipLaunchKernelGGL(conv_wgrad_kernel<128>, grid, dim3(WG), 0, st, a); break;
+    default: return OESS_EINVAL;
     }
-reduce:
-    const long long total = (long long)Cout * a.Kdim;
-    if (splits >= 16) {         // many slices: 8 split lanes per element (fixed-order combine)
+    const long long total = (long long)Cout * p.Kdim;
+    if (p.wide_reduce) {
         long long rg = (total + 31) / 32;
         if (rg > 8192) rg = 8192;
-        hipLaunchKernelGGL(wgrad_reduce_wide_kernel, dim3((unsigned)rg), dim3(256), 0, (hipStream_t)stream, (const float*)workspace,
-                           splits, a.tiles_m * tmv, a.tiles_n * TN, Cout, Cin, Cin_x, R * S, dw_oihw);
+        hipLaunchKernelGGL(wgrad_reduce_wide_kernel, dim3((unsigned)rg), dim3(256), 0, st, (const float*)workspace,
+                           p.slices, p.tiles_m * p.tmv, p.tiles_n * TN, Cout, Cin, Cin_x, R * S, dw_oihw);
     } else {
         long long rg = (total + 255) / 256;
         if (rg > 4096) rg = 4096;
-        hipLaunchKernelGGL(wgrad_reduce_kernel, dim3((unsigned)rg), dim3(256), 0, (hipStream_t)stream, (const float*)workspace, splits,
-                           a.tiles_m * tmv, a.tiles_n * TN, Cout, Cin, Cin_x, R * S, dw_oihw);
+        hipLaunchKernelGGL(wgrad_reduce_kernel, dim3((unsigned)rg), dim3(256), 0, st, (const float*)workspace, p.slices,
+                           p.tiles_m * p.tmv, p.tiles_n * TN, Cout, Cin, Cin_x, R * S, dw_oihw);
     }
     OESS_HIP(hipGetLastError());
     return OESS_OK;

@@ -1828,19 +1828,64 @@ def l2_normalize(x, eps=1e-12):
     return _L2Normalize.apply(x, float(eps))
 
 
-def conv2d_wgrad(x, gy, Cout, Cin, R, S, stride=1, pad=0, dil=1):
-    """dW (OIHW fp32) of conv2d_nhwc from NHWC bf16 views x [B,H,W,Cin_x>=Cin] and gy [B,Ho,Wo,Cout]."""
+_WGRAD_WS_BYTES = 256 << 20
+
+
+def _wgrad_workspace_check(workspace):
+    if workspace.dtype != torch.uint8 or not workspace.is_cuda or not workspace.is_contiguous():
+        raise ValueError("workspace must be a contiguous uint8 CUDA tensor")
+
+
+def conv2d_wgrad(x, gy, Cout, Cin, R, S, stride=1, pad=0, dil=1, workspace=None, out=None):
+    """dW (OIHW fp32) of conv2d_nhwc from NHWC bf16 views x [B,H,W,Cin_x>=Cin] and gy [B,Ho,Wo,Cout].
+    workspace: a caller-owned uint8 CUDA tensor for the split-K partial tiles (all of it is on offer, nothing beyond it is
+    touched); default: the wrapper's cached 256 MiB buffer.  out: a dense fp32 (Cout, Cin, R, S) tensor to write into."""
     lib = _lib.load()
     _need_gpu(x, gy)
     B, H, W, Cin_x, xps = _nhwc_geom(x)
     _, Ho, Wo, Cg, gps = _nhwc_geom(gy)
     if Cg != Cout:
         raise ValueError("gy channel count != Cout")
-    dw = torch.empty((Cout, Cin, R, S), dtype=torch.float32, device=x.device)
-    ws = _workspace(256 << 20, x.device, tag="wgrad")
+    if out is None:
+        dw = torch.empty((Cout, Cin, R, S), dtype=torch.float32, device=x.device)
+    else:
+        if out.dtype != torch.float32 or not out.is_cuda or not out.is_contiguous() or tuple(out.shape) != (Cout, Cin, R, S):
+            raise ValueError(f"out must be a dense fp32 CUDA tensor of shape {(Cout, Cin, R, S)}")
+        dw = out
+    if workspace is None:
+        ws = _workspace(_WGRAD_WS_BYTES, x.device, tag="wgrad")
+    else:
+        _wgrad_workspace_check(workspace)
+        ws = workspace
     _lib.check(lib.oess_conv2d_wgrad_bf16(_ptr(x), xps, B, H, W, Cin_x, _ptr(gy), gps, Cout, Cin, R, S, stride, pad, dil,
                                           _ptr(dw), _ptr(ws), ws.numel(), _stream()), "oess_conv2d_wgrad_bf16")
     return dw
+
+
+def conv2d_wgrad_route(x, gy, Cout, Cin, R, S, stride=1, pad=0, dil=1, workspace=None, x_pix_stride=None, dy_pix_stride=None):
+    """The kernel conv2d_wgrad would launch for these arguments: OESS_WGRAD_* of include/oess.h | slices << 8 (route & 0xff is
+    the kernel, route >> 8 the number of partial tiles the reduce kernel sums per element); raises where the call would.  Host
+    only, needs no GPU.  With x a tensor the arguments are conv2d_wgrad's own: strides from the views, the workspace's size (the
+    default buffer's without one).  With x a (B, H, W, Cin_x) shape gy is not looked at, *_pix_stride stand in for the views
+    (default: dense) and workspace is a byte count."""
+    lib = _lib.load()
+    if torch.is_tensor(x):
+        B, H, W, Cin_x, xps = _nhwc_geom(x)
+        Cg, gps = _nhwc_geom(gy)[3:]
+        if Cg != Cout:
+            raise ValueError("gy channel count != Cout")
+        if workspace is not None:
+            _wgrad_workspace_check(workspace)
+        nbytes = _WGRAD_WS_BYTES if workspace is None else workspace.numel()
+    else:
+        B, H, W, Cin_x = x
+        xps = Cin_x if x_pix_stride is None else x_pix_stride
+        gps = Cout if dy_pix_stride is None else dy_pix_stride
+        nbytes = _WGRAD_WS_BYTES if workspace is None else int(workspace)
+    r = lib.oess_conv2d_wgrad_route(B, H, W, Cin_x, Cout, Cin, R, S, stride, pad, dil, xps, gps, nbytes)
+    if r < 0:
+        _lib.check(r, "oess_conv2d_wgrad_route")
+    return r
 
 
 class _GlobalAvgPool(torch.autograd.Function):
