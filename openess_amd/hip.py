@@ -2286,6 +2286,27 @@ def _f32_out(out, B, Cout, Ho, Wo, device):
     return out
 
 
+def _f32_residual(residual, shape):
+    """The view of a residual, which must have `shape`; None stays None."""
+    if residual is None:
+        return None
+    if tuple(residual.shape) != shape:
+        raise ValueError(f"residual shape {tuple(residual.shape)} != {shape}")
+    return _f32_view(residual, "residual")
+
+
+def _f32_workspace(need, what, shape, device, tag):
+    """The `tag` workspace for the `need` bytes a query answered; 0 bytes: `what` has no kernel for a map of `shape`."""
+    if need == 0:
+        raise ValueError(f"{what}: no kernel for a {shape} map")
+    return _workspace(need, device, tag=tag)
+
+
+def _f32_grad(g):
+    """An incoming gradient in fp32 (autograd may hand over another dtype)."""
+    return g if g.dtype == torch.float32 else g.float()
+
+
 def pack_conv_weight_f32(w):
     """Conv2d weight [Cout, Cin, R, S] -> the fp32 operand of oess_conv2d_fwd_f32: [ceil16(R S Cin)][ceil32(Cout)], row
     (r S + s) Cin + ci (include/oess.h).  Parameter preparation, once per weight version (engine.PackedWeightF32)."""
@@ -2335,12 +2356,8 @@ def conv2d_f32(x, packed, bias, Cout, R, S, stride=1, pad=0, act=None, x2=None, 
         raise ValueError(f"conv2d_f32: no output for a {Hl} x {Wl} map, {R} x {S} taps, pad {pad}, dilation {dilation}")
     Ho, Wo = (Hl + 2 * pad - dilation * (R - 1) - 1) // stride + 1, (Wl + 2 * pad - dilation * (S - 1) - 1) // stride + 1
     out = _f32_out(out, B, Cout, Ho, Wo, x.device)
-    vr = None
-    if residual is not None:
-        _need_gpu(residual)
-        if tuple(residual.shape) != (B, Cout, Ho, Wo):
-            raise ValueError(f"residual shape {tuple(residual.shape)} != {(B, Cout, Ho, Wo)}")
-        vr = _f32_view(residual, "residual")
+    _need_gpu(residual)
+    vr = _f32_residual(residual, (B, Cout, Ho, Wo))
     vo = _f32_view(out, "out")
     if dilation == 1 and R * S <= 25 and pad < R and pad < S:
         _lib.check(lib.oess_conv2d_fwd_f32(ctypes.byref(vx), _f32_ref(v2), B, H, W, Cin, int(bool(upsample2x)), _ptr(packed), _ptr(bias),
@@ -2403,17 +2420,11 @@ def instance_norm_f32(x, relu=False, residual=None, eps=1e-5, out=None):
         raise NotImplementedError("ReLU after the residual add is not a pattern of the reference")
     vx = _f32_view(x, "x")
     B, C, H, W = x.shape
-    vr = None
-    if residual is not None:
-        if tuple(residual.shape) != (B, C, H, W):
-            raise ValueError(f"residual shape {tuple(residual.shape)} != {(B, C, H, W)}")
-        vr = _f32_view(residual, "residual")
+    vr = _f32_residual(residual, (B, C, H, W))
     out = _f32_out(out, B, C, H, W, x.device)
     vo = _f32_view(out, "out")
-    need = lib.oess_instance_norm_f32_workspace_bytes(B, H, W, C)
-    if need == 0:
-        raise ValueError(f"instance_norm_f32: no kernel for a {(B, C, H, W)} map")
-    ws = _workspace(need, x.device, tag="instnorm_f32")
+    ws = _f32_workspace(lib.oess_instance_norm_f32_workspace_bytes(B, H, W, C), "instance_norm_f32", (B, C, H, W), x.device,
+                        "instnorm_f32")
     _lib.check(lib.oess_instance_norm_fwd_f32(ctypes.byref(vx), B, H, W, C, float(eps), int(bool(relu)), _f32_ref(vr), ctypes.byref(vo),
                                               _ptr(ws), ws.numel(), _stream()), "oess_instance_norm_fwd_f32")
     _bump(out)
@@ -2463,10 +2474,8 @@ def global_avg_pool_f32(x):
     _need_gpu(x)
     vx = _f32_view(x, "x")
     B, C, H, W = x.shape
-    need = lib.oess_global_avg_pool_f32_workspace_bytes(B, H, W, C)
-    if need == 0:
-        raise ValueError(f"global_avg_pool_f32: no kernel for a {(B, C, H, W)} map")
-    ws = _workspace(need, x.device, tag="avgpool_f32")
+    ws = _f32_workspace(lib.oess_global_avg_pool_f32_workspace_bytes(B, H, W, C), "global_avg_pool_f32", (B, C, H, W), x.device,
+                        "avgpool_f32")
     out = torch.empty((B, 1, 1, C), dtype=torch.float32, device=x.device).permute(0, 3, 1, 2)     # NHWC: the 1 x 1 conv's vector loads
     _lib.check(lib.oess_global_avg_pool_fwd_f32(ctypes.byref(vx), B, H, W, C, _ptr(out), _ptr(ws), ws.numel(), _stream()),
                "oess_global_avg_pool_fwd_f32")
@@ -2499,19 +2508,13 @@ def batch_norm_train_f32(x, bn, relu=False, residual=None, out=None, return_stat
     for name, t in (('weight', gamma), ('bias', beta), ('running_mean', rm), ('running_var', rv)):
         if t is not None and (t.dtype != torch.float32 or not t.is_contiguous() or t.numel() != C):
             raise ValueError(f"batch_norm_train_f32: {name} must be a contiguous fp32 tensor of {C} elements")
-    vr = None
-    if residual is not None:
-        if tuple(residual.shape) != (B, C, H, W):
-            raise ValueError(f"residual shape {tuple(residual.shape)} != {(B, C, H, W)}")
-        vr = _f32_view(residual, "residual")
+    vr = _f32_residual(residual, (B, C, H, W))
     if B * H * W < 2:
         raise ValueError(f"Expected more than 1 value per channel when training, got input size {tuple(x.shape)}")
     out = _f32_out(out, B, C, H, W, x.device)
     vo = _f32_view(out, "out")
-    need = lib.oess_batch_norm_train_f32_workspace_bytes(B, H, W, C)
-    if need == 0:
-        raise ValueError(f"batch_norm_train_f32: no kernel for a {(B, C, H, W)} map")
-    ws = _workspace(need, x.device, tag="batchnorm_f32")
+    ws = _f32_workspace(lib.oess_batch_norm_train_f32_workspace_bytes(B, H, W, C), "batch_norm_train_f32", (B, C, H, W), x.device,
+                        "batchnorm_f32")
     stats = torch.empty((2, C), dtype=torch.float32, device=x.device) if return_stats else None
     _lib.check(lib.oess_batch_norm_train_fwd_f32(ctypes.byref(vx), B, H, W, C, _ptr(gamma), _ptr(beta), float(p.get('eps', 1e-5)),
                                                  float(p.get('momentum', 0.1)), _ptr(rm), _ptr(rv),
@@ -2551,6 +2554,25 @@ def _wgrad_f32_check(x, dy, R, stride, pad, dilation):
         raise ValueError(f"conv2d_wgrad_f32: x {tuple(x.shape)} and dy {tuple(dy.shape)} must share B, H, W")
 
 
+def _wgrad_f32_launch(name, x, dy, R, stride, pad, dilation, want_db):
+    """What conv2d_wgrad_f32 and conv2d_dilated_wgrad_f32 (`name`) do after their own checks: the workspace of the C entry
+    oess_<name>, (dw, db) and the launch."""
+    _need_gpu(x, dy)
+    lib = _lib.load()
+    B, Cin, H, W = x.shape
+    Cout = dy.shape[1]
+    need = getattr(lib, f"oess_{name}_workspace_bytes")(B, H, W, Cin, Cout, R, R, stride, pad, dilation)
+    if need == 0:
+        raise ValueError(f"{name}: no kernel for x {tuple(x.shape)}, dy {tuple(dy.shape)}, {R} x {R}")
+    ws = _workspace(need, x.device, tag="wgrad_f32")
+    dw = torch.empty((Cout, Cin, R, R), dtype=torch.float32, device=x.device)
+    db = torch.empty((Cout,), dtype=torch.float32, device=x.device) if want_db else None
+    vx, vg = _f32_view(x, "x"), _f32_view(dy, "dy")
+    _lib.check(getattr(lib, f"oess_{name}")(ctypes.byref(vx), ctypes.byref(vg), B, H, W, Cin, Cout, R, R, stride, pad, dilation, _ptr(dw),
+                                            _ptr(db), _ptr(ws), ws.numel(), _stream()), f"oess_{name}")
+    return dw, db
+
+
 def conv2d_wgrad_f32_splits(B, H, W, Cin, Cout, R):
     """Number of pixel ranges oess_conv2d_wgrad_f32 splits its reduction into for these shapes (a function of the shapes alone),
     read off the workspace query: n (R R Cin Cout + Cout) floats."""
@@ -2564,53 +2586,7 @@ def conv2d_wgrad_f32(x, dy, R, stride=1, pad=None, dilation=1, want_db=True):
     they lie (channels_last and channel slices of it take the vector loads).  Fixed summation order: bit-repeatable."""
     pad = (R - 1) // 2 if pad is None else pad
     _wgrad_f32_check(x, dy, R, stride, pad, dilation)
-    _need_gpu(x, dy)
-    lib = _lib.load()
-    B, Cin, H, W = x.shape
-    Cout = dy.shape[1]
-    need = lib.oess_conv2d_wgrad_f32_workspace_bytes(B, H, W, Cin, Cout, R, R, stride, pad, dilation)
-    if need == 0:
-        raise ValueError(f"conv2d_wgrad_f32: no kernel for x {tuple(x.shape)}, dy {tuple(dy.shape)}, {R} x {R}")
-    ws = _workspace(need, x.device, tag="wgrad_f32")
-    dw = torch.empty((Cout, Cin, R, R), dtype=torch.float32, device=x.device)
-    db = torch.empty((Cout,), dtype=torch.float32, device=x.device) if want_db else None
-    vx, vg = _f32_view(x, "x"), _f32_view(dy, "dy")
-    _lib.check(lib.oess_conv2d_wgrad_f32(ctypes.byref(vx), ctypes.byref(vg), B, H, W, Cin, Cout, R, R, stride, pad, dilation, _ptr(dw),
-                                         _ptr(db), _ptr(ws), ws.numel(), _stream()), "oess_conv2d_wgrad_f32")
-    return dw, db
-
-
-class _Conv2dF32Train(torch.autograd.Function):
-    """conv(x, weight, stride 1, 'same' pad) + bias in fp32: forward oess_conv2d_fwd_f32, backward oess_conv2d_wgrad_f32 and, when
-    x needs a gradient, oess_conv2d_fwd_f32 on the rotated, transposed weight."""
-
-    @staticmethod
-    def forward(ctx, x, weight, bias, pad, pw, ver):
-        Cout, _, R, _ = weight.shape
-        op = pw.get_train(weight, bias, ver)
-        y = conv2d_f32(x, op.packed, op.bias, Cout, R, R, 1, pad)
-        ctx.save_for_backward(x, weight)
-        ctx.meta = (pad, op, op.key, bias is not None)
-        return y
-
-    @staticmethod
-    def backward(ctx, gy):
-        x, weight = ctx.saved_tensors
-        pad, op, key, has_bias = ctx.meta
-        Cout, Cin, R, _ = weight.shape
-        if gy.dtype != torch.float32:
-            gy = gy.float()
-        gx = gw = gb = None
-        need_gb = has_bias and ctx.needs_input_grad[2]
-        if ctx.needs_input_grad[1] or need_gb:
-            gw, gb = conv2d_wgrad_f32(x, gy, R, 1, pad, 1, want_db=need_gb)
-            if not ctx.needs_input_grad[1]:
-                gw = None
-        if ctx.needs_input_grad[0]:
-            # the operand of the forward's weight version; a holder that moved on since is not this node's
-            wd = op.dgrad() if op.key == key else pack_conv_weight_f32_dgrad(weight)
-            gx = conv2d_f32(gy, wd, None, Cin, R, R, 1, R - 1 - pad)
-        return gx, gw, gb, None, None, None
+    return _wgrad_f32_launch("conv2d_wgrad_f32", x, dy, R, stride, pad, dilation, want_db)
 
 
 def conv2d_f32_train(x, weight, bias=None, stride=1, pad=None, dilation=1, act=None, pw=None, ver=None):
@@ -2635,7 +2611,7 @@ def conv2d_f32_train(x, weight, bias=None, stride=1, pad=None, dilation=1, act=N
     if pw is None:
         from . import engine as _engine
         pw = _engine.PackedWeightF32()
-    return _Conv2dF32Train.apply(x, weight, bias, pad, pw, ver)
+    return _Conv2dDilatedF32Train.apply(x, weight, bias, 1, pad, 1, conv2d_wgrad_f32, pw, ver)
 
 
 class _InstanceNormF32Train(torch.autograd.Function):
@@ -2648,10 +2624,8 @@ class _InstanceNormF32Train(torch.autograd.Function):
         out = _f32_out(None, B, C, H, W, x.device)
         vo = _f32_view(out, "out")
         stats = torch.empty((2, B, C), dtype=torch.float32, device=x.device)
-        need = lib.oess_instance_norm_f32_workspace_bytes(B, H, W, C)
-        if need == 0:
-            raise ValueError(f"instance_norm_f32_train: no kernel for a {(B, C, H, W)} map")
-        ws = _workspace(need, x.device, tag="instnorm_f32")
+        ws = _f32_workspace(lib.oess_instance_norm_f32_workspace_bytes(B, H, W, C), "instance_norm_f32_train", (B, C, H, W), x.device,
+                            "instnorm_f32")
         _lib.check(lib.oess_instance_norm_train_fwd_f32(ctypes.byref(vx), B, H, W, C, float(eps), int(relu), _f32_ref(vr),
                                                         ctypes.byref(vo), _ptr(stats[0]), _ptr(stats[1]), _ptr(ws), ws.numel(),
                                                         _stream()), "oess_instance_norm_train_fwd_f32")
@@ -2664,8 +2638,7 @@ class _InstanceNormF32Train(torch.autograd.Function):
         lib = _lib.load()
         x, stats = ctx.saved_tensors
         B, C, H, W = x.shape
-        if gy.dtype != torch.float32:
-            gy = gy.float()
+        gy = _f32_grad(gy)
         dx = None
         if ctx.needs_input_grad[0]:
             dx = _f32_out(None, B, C, H, W, x.device)
@@ -2702,8 +2675,7 @@ class _UpsampleConcatF32Train(torch.autograd.Function):
     def backward(ctx, g):
         lib = _lib.load()
         C = ctx.C
-        if g.dtype != torch.float32:
-            g = g.float()
+        g = _f32_grad(g)
         B, _, Ho, Wo = g.shape
         gx = None
         if ctx.needs_input_grad[0]:
@@ -2766,24 +2738,12 @@ def conv2d_dilated_wgrad_f32(x, dy, R, stride, pad, dilation, want_db=True):
     for name, t in (("x", x), ("dy", dy)):
         if t.dtype != torch.float32 or t.ndim != 4:
             raise ValueError(f"conv2d_dilated_wgrad_f32: {name} must be a 4-D fp32 tensor [B, C, H, W]")
-    B, Cin, H, W = x.shape
+    B, _, H, W = x.shape
     _dilated_geometry_check("conv2d_dilated_wgrad_f32", R, stride, pad, dilation, H, W)
-    Cout = dy.shape[1]
     if (dy.shape[0], dy.shape[2], dy.shape[3]) != (B,) + _conv_out_hw(H, W, R, stride, pad, dilation):
         raise ValueError(f"conv2d_dilated_wgrad_f32: dy {tuple(dy.shape)} is not the output of x {tuple(x.shape)} under {R} x {R}, "
                          f"stride {stride}, pad {pad}, dilation {dilation}")
-    _need_gpu(x, dy)
-    lib = _lib.load()
-    need = lib.oess_conv2d_dilated_wgrad_f32_workspace_bytes(B, H, W, Cin, Cout, R, R, stride, pad, dilation)
-    if need == 0:
-        raise ValueError(f"conv2d_dilated_wgrad_f32: no kernel for x {tuple(x.shape)}, dy {tuple(dy.shape)}, {R} x {R}")
-    ws = _workspace(need, x.device, tag="wgrad_f32")
-    dw = torch.empty((Cout, Cin, R, R), dtype=torch.float32, device=x.device)
-    db = torch.empty((Cout,), dtype=torch.float32, device=x.device) if want_db else None
-    vx, vg = _f32_view(x, "x"), _f32_view(dy, "dy")
-    _lib.check(lib.oess_conv2d_dilated_wgrad_f32(ctypes.byref(vx), ctypes.byref(vg), B, H, W, Cin, Cout, R, R, stride, pad, dilation,
-                                                 _ptr(dw), _ptr(db), _ptr(ws), ws.numel(), _stream()), "oess_conv2d_dilated_wgrad_f32")
-    return dw, db
+    return _wgrad_f32_launch("conv2d_dilated_wgrad_f32", x, dy, R, stride, pad, dilation, want_db)
 
 
 def conv2d_dgrad_s2_f32(dy, packed, Cin, H, W, R, pad, out=None):
@@ -2810,29 +2770,30 @@ def conv2d_dgrad_s2_f32(dy, packed, Cin, H, W, R, pad, out=None):
 
 
 class _Conv2dDilatedF32Train(torch.autograd.Function):
-    """conv(x, weight, stride, pad, dilation) + bias in fp32: forward hip.conv2d_f32, backward oess_conv2d_dilated_wgrad_f32 and,
-    when x needs a gradient, oess_conv2d_dgrad_s2_f32 (stride 2) or the dilated forward on the rotated, transposed weight."""
+    """conv(x, weight, stride, pad, dilation) + bias in fp32, the one fp32 training convolution (conv2d_f32_train is its stride 1,
+    dilation 1, 'same' padding case): forward hip.conv2d_f32, backward `wgrad` (conv2d_wgrad_f32 or conv2d_dilated_wgrad_f32, as
+    the public entry hands over) and, when x needs a gradient, oess_conv2d_dgrad_s2_f32 (stride 2) or the dilated forward on the
+    rotated, transposed weight."""
 
     @staticmethod
-    def forward(ctx, x, weight, bias, stride, pad, dilation, pw, ver):
+    def forward(ctx, x, weight, bias, stride, pad, dilation, wgrad, pw, ver):
         Cout, _, R, _ = weight.shape
         op = pw.get_train(weight, bias, ver)
         y = conv2d_f32(x, op.packed, op.bias, Cout, R, R, stride, pad, dilation=dilation)
         ctx.save_for_backward(x, weight)
-        ctx.meta = (stride, pad, dilation, op, op.key, bias is not None)
+        ctx.meta = (stride, pad, dilation, wgrad, op, op.key, bias is not None)
         return y
 
     @staticmethod
     def backward(ctx, gy):
         x, weight = ctx.saved_tensors
-        stride, pad, dilation, op, key, has_bias = ctx.meta
+        stride, pad, dilation, wgrad, op, key, has_bias = ctx.meta
         Cout, Cin, R, _ = weight.shape
-        if gy.dtype != torch.float32:
-            gy = gy.float()
+        gy = _f32_grad(gy)
         gx = gw = gb = None
         need_gb = has_bias and ctx.needs_input_grad[2]
         if ctx.needs_input_grad[1] or need_gb:
-            gw, gb = conv2d_dilated_wgrad_f32(x, gy, R, stride, pad, dilation, want_db=need_gb)
+            gw, gb = wgrad(x, gy, R, stride, pad, dilation, want_db=need_gb)
             if not ctx.needs_input_grad[1]:
                 gw = None
         if ctx.needs_input_grad[0]:
@@ -2843,7 +2804,7 @@ class _Conv2dDilatedF32Train(torch.autograd.Function):
             else:
                 wd = op.dgrad() if same else pack_conv_weight_f32_dgrad(weight)
                 gx = conv2d_f32(gy, wd, None, Cin, R, R, 1, dilation * (R - 1) - pad, dilation=dilation)
-        return gx, gw, gb, None, None, None, None, None
+        return gx, gw, gb, None, None, None, None, None, None
 
 
 def conv2d_dilated_f32_train(x, weight, bias=None, stride=1, pad=0, dilation=1, pw=None, ver=None):
@@ -2872,7 +2833,7 @@ def conv2d_dilated_f32_train(x, weight, bias=None, stride=1, pad=0, dilation=1, 
     if pw is None:
         from . import engine as _engine
         pw = _engine.PackedWeightF32()
-    return _Conv2dDilatedF32Train.apply(x, weight, bias, stride, pad, dilation, pw, ver)
+    return _Conv2dDilatedF32Train.apply(x, weight, bias, stride, pad, dilation, conv2d_dilated_wgrad_f32, pw, ver)
 
 
 class _BatchNormF32Train(torch.autograd.Function):
@@ -2889,8 +2850,7 @@ class _BatchNormF32Train(torch.autograd.Function):
         lib = _lib.load()
         x, out, mean, var, gamma = ctx.saved_tensors
         B, C, H, W = x.shape
-        if gy.dtype != torch.float32:
-            gy = gy.float()
+        gy = _f32_grad(gy)
         need_dx = ctx.needs_input_grad[0]
         need_dg = gamma is not None and ctx.needs_input_grad[1]
         need_db = ctx.has_beta and ctx.needs_input_grad[2]
@@ -2950,8 +2910,7 @@ class _MaxPool3x3s2F32Train(torch.autograd.Function):
     def backward(ctx, g):
         x, = ctx.saved_tensors
         B, C, H, W = x.shape
-        if g.dtype != torch.float32:
-            g = g.float()
+        g = _f32_grad(g)
         dx = _f32_out(None, B, C, H, W, x.device)
         vx, vg, vd = _f32_view(x, "x"), _f32_view(g, "dy"), _f32_view(dx, "dx")
         _lib.check(_lib.load().oess_maxpool3x3s2_bwd_f32(ctypes.byref(vx), ctypes.byref(vg), B, H, W, C, ctypes.byref(vd), _stream()),
@@ -2986,8 +2945,7 @@ class _DropoutF32(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g):
-        if g.dtype != torch.float32:
-            g = g.float()
+        g = _f32_grad(g)
         return _dropout_f32_launch(g, *ctx.meta), None, None, None
 
 
@@ -3059,8 +3017,7 @@ class _ASPPPoolBranchF32(torch.autograd.Function):
         pooled, w2, gamma, buf = ctx.saved_tensors
         B, H, W, C, Cout = ctx.geom
         y_pre, z, stat = buf[:B], buf[B:2 * B], buf[2 * B:]
-        if g.dtype != torch.float32:
-            g = g.float()
+        g = _f32_grad(g)
         gz = _avg_pool_rows_f32(g) * float(H * W)               # per-sample sums of the gradient slice, read where it lies
         out = torch.empty((B * Cout + Cout * C + 2 * Cout,), dtype=torch.float32, device=g.device)
         dy = out[:B * Cout]

@@ -1,5 +1,8 @@
 """Mirror of models/_resnet.py (ResNet :117-209, Bottleneck :74-114, resnet50) with the convolutions
 on the HIP MFMA kernel.  state_dict keys equal torchvision's / the reference's."""
+from collections import OrderedDict
+from typing import Callable, NamedTuple
+
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
@@ -134,6 +137,40 @@ def conv_bn_f32_autograd(conv, bn, x, relu=False, residual=None):
     return hip.batch_norm_f32_train(y, bn, relu=relu, residual=residual)
 
 
+class F32Layers(NamedTuple):
+    """The per-layer functions of one mode of the fp32 network: what walk_f32 and Bottleneck.forward_f32 call."""
+    conv_bn: Callable      # (conv, bn, x, relu=False, residual=None) -> y
+    max_pool: Callable     # (x) -> y
+
+
+F32_EVAL = F32Layers(conv_bn_f32, hip.max_pool_3x3s2_f32)                           # BatchNorm folded; no autograd
+F32_AS_FLAGGED = F32Layers(conv_bn_any_f32, hip.max_pool_3x3s2_f32)                 # per BatchNorm as bn.training says; no autograd
+F32_AUTOGRAD = F32Layers(conv_bn_f32_autograd, hip.max_pool_3x3s2_f32_train)        # train-mode BatchNorm with autograd (K21)
+
+
+def walk_f32(net, x, layers, return_layers=()):
+    """THE fp32 walk over a ResNet, or over the IntermediateLayerGetter that holds its first children: stem conv + BatchNorm +
+    ReLU, max pool, then every block of layer1-4; ends at the classification head.  x fp32 [B, 3, H, W], any layout.  Returns
+    (the last fp32 channels_last map, OrderedDict of the maps after the children named in return_layers, under their new names)."""
+    out = OrderedDict()
+    with engine.defer_bn_counters():                 # nothing is pending in eval mode: a no-op there
+        for name, module in net.named_children():
+            if name == 'conv1':
+                x = layers.conv_bn(module, net.bn1, x, relu=True)
+            elif name in ('bn1', 'relu'):
+                continue
+            elif name == 'maxpool':
+                x = layers.max_pool(x)
+            elif name in ('avgpool', 'fc'):
+                break
+            else:
+                for block in module:
+                    x = block.forward_f32(x, layers)
+            if name in return_layers:
+                out[return_layers[name]] = x
+    return x, out
+
+
 def conv3x3(in_planes, out_planes, stride=1, groups=1, dilation=1):
     assert groups == 1
     return HipConv2d(in_planes, out_planes, kernel_size=3, stride=stride, padding=dilation, bias=False, dilation=dilation)
@@ -190,29 +227,26 @@ class Bottleneck(nn.Module):
             identity = conv_bn(self.downsample[0], self.downsample[1], x)
         return conv_bn(self.conv3, self.bn3, out, relu=True, residual=identity, skip_out=skip)
 
+    def forward_f32(self, x, layers):
+        """The block in fp32 on one F32Layers set: three conv + BatchNorm steps, four with a downsample conv (the residual's
+        producer); the residual add and the last ReLU ride in conv3's step."""
+        out = layers.conv_bn(self.conv1, self.bn1, x, relu=True)
+        out = layers.conv_bn(self.conv2, self.bn2, out, relu=True)
+        identity = x if self.downsample is None else layers.conv_bn(self.downsample[0], self.downsample[1], x)
+        return layers.conv_bn(self.conv3, self.bn3, out, relu=True, residual=identity)
+
     def forward_fp32(self, x):
-        """The block in fp32 (eval mode): three launches, four with a downsample conv; the residual add and the last ReLU ride in
-        conv3's epilogue, the downsample conv is the residual's producer."""
-        out = conv_bn_f32(self.conv1, self.bn1, x, relu=True)
-        out = conv_bn_f32(self.conv2, self.bn2, out, relu=True)
-        identity = x if self.downsample is None else conv_bn_f32(self.downsample[0], self.downsample[1], x)
-        return conv_bn_f32(self.conv3, self.bn3, out, relu=True, residual=identity)
+        """Eval mode: every BatchNorm folded, one launch per conv."""
+        return self.forward_f32(x, F32_EVAL)
 
     def forward_train_fp32(self, x):
-        """The block in fp32 with every BatchNorm in the form its own `training` flag asks for (conv_bn_any_f32): batch statistics
-        and a running-statistics step in train mode (conv + the BatchNorm's three launches), the folded conv in eval mode."""
-        out = conv_bn_any_f32(self.conv1, self.bn1, x, relu=True)
-        out = conv_bn_any_f32(self.conv2, self.bn2, out, relu=True)
-        identity = x if self.downsample is None else conv_bn_any_f32(self.downsample[0], self.downsample[1], x)
-        return conv_bn_any_f32(self.conv3, self.bn3, out, relu=True, residual=identity)
+        """Every BatchNorm in the form its own `training` flag asks for (conv_bn_any_f32).  No autograd."""
+        return self.forward_f32(x, F32_AS_FLAGGED)
 
     def forward_fp32_autograd(self, x):
         """forward_train_fp32 with autograd (K21): the same bits forward, every BatchNorm in train mode; backward on the fp32
         kernels (weight, BatchNorm and data gradients)."""
-        out = conv_bn_f32_autograd(self.conv1, self.bn1, x, relu=True)
-        out = conv_bn_f32_autograd(self.conv2, self.bn2, out, relu=True)
-        identity = x if self.downsample is None else conv_bn_f32_autograd(self.downsample[0], self.downsample[1], x)
-        return conv_bn_f32_autograd(self.conv3, self.bn3, out, relu=True, residual=identity)
+        return self.forward_f32(x, F32_AUTOGRAD)
 
 
 class ResNet(nn.Module):
@@ -282,24 +316,12 @@ class ResNet(nn.Module):
     def features_fp32(self, x):
         """features() in fp32: x fp32 [B, 3, H, W], any layout -> the fp32 channels_last layer4 map.  Per BatchNorm the folded
         (eval) or the batch-statistics (train) form.  No autograd."""
-        with engine.defer_bn_counters():
-            x = conv_bn_any_f32(self.conv1, self.bn1, x, relu=True)
-            x = hip.max_pool_3x3s2_f32(x)
-            for layer in (self.layer1, self.layer2, self.layer3, self.layer4):
-                for block in layer:
-                    x = block.forward_train_fp32(x)
-            return x
+        return walk_f32(self, x, F32_AS_FLAGGED)[0]
 
     def features_fp32_autograd(self, x):
-        """features_fp32 with autograd (K21): stem, max pool and layer1-4 in fp32 with every BatchNorm in train mode; the same
-        bits forward, the gradients of every parameter on the fp32 backward kernels."""
-        with engine.defer_bn_counters():
-            x = conv_bn_f32_autograd(self.conv1, self.bn1, x, relu=True)
-            x = hip.max_pool_3x3s2_f32_train(x)
-            for layer in (self.layer1, self.layer2, self.layer3, self.layer4):
-                for block in layer:
-                    x = block.forward_fp32_autograd(x)
-            return x
+        """features_fp32 with autograd (K21): every BatchNorm in train mode; the same bits forward, the gradients of every
+        parameter on the fp32 backward kernels."""
+        return walk_f32(self, x, F32_AUTOGRAD)[0]
 
     def forward(self, x):
         x = self.features(x)

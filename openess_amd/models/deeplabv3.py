@@ -43,50 +43,27 @@ class IntermediateLayerGetter(nn.ModuleDict):
 
     def forward_fp32(self, x):
         """forward() in fp32 (eval mode): x fp32 [B, 3, H, W], any layout; the same OrderedDict of fp32 channels_last maps."""
-        out = OrderedDict()
-        for name, module in self.named_children():
-            if name == 'conv1':
-                x = conv_bn_f32(module, self['bn1'], x, relu=True)
-            elif name in ('bn1', 'relu'):
-                continue
-            elif name == 'maxpool':
-                x = hip.max_pool_3x3s2_f32(x)
-            else:
-                for block in module:
-                    x = block.forward_fp32(x)
-            if name in self.return_layers:
-                out[self.return_layers[name]] = x
-        return out
+        return resnet.walk_f32(self, x, resnet.F32_EVAL, self.return_layers)[1]
 
     def forward_fp32_autograd(self, x):
-        """forward() in fp32 with autograd and every BatchNorm in train mode (K22): stem, max pool and the blocks on the K21 layer
-        set; the bits of ResNet.features_fp32_autograd.  x fp32 [B, 3, H, W], any layout."""
-        out = OrderedDict()
-        with engine.defer_bn_counters():
-            for name, module in self.named_children():
-                if name == 'conv1':
-                    x = conv_bn_f32_autograd(module, self['bn1'], x, relu=True)
-                elif name in ('bn1', 'relu'):
-                    continue
-                elif name == 'maxpool':
-                    x = hip.max_pool_3x3s2_f32_train(x)
-                else:
-                    for block in module:
-                        x = block.forward_fp32_autograd(x)
-                if name in self.return_layers:
-                    out[self.return_layers[name]] = x
-        return out
+        """forward() in fp32 with autograd and every BatchNorm in train mode (K22): ResNet.features_fp32_autograd's own walk, so
+        its bits.  x fp32 [B, 3, H, W], any layout."""
+        return resnet.walk_f32(self, x, resnet.F32_AUTOGRAD, self.return_layers)[1]
 
 
 class _ConvBNReLU(nn.Sequential):
     def forward(self, x, out=None):
         return conv_bn(self[0], self[1], x, relu=True, out=out)
 
+    def forward_f32(self, x, layers, **kw):
+        """kw: out=, for the eval set only (a branch's channel slice of ASPP's concat buffer)."""
+        return layers.conv_bn(self[0], self[1], x, relu=True, **kw)
+
     def forward_fp32(self, x, out=None):
-        return conv_bn_f32(self[0], self[1], x, relu=True, out=out)
+        return self.forward_f32(x, resnet.F32_EVAL, out=out)
 
     def forward_fp32_autograd(self, x):
-        return conv_bn_f32_autograd(self[0], self[1], x, relu=True)
+        return self.forward_f32(x, resnet.F32_AUTOGRAD)
 
 
 class ASPPConv(_ConvBNReLU):
@@ -300,11 +277,26 @@ class deeplabv3_resnet50(nn.Module):
         need no gradient keeps no graph, the first trainable convolution skips its data gradient.  No buffer, operand or state
         is shared with forward(), except the Dropout module's mask counter (one mask sequence for both)."""
         self.check_fp32_train()
+        return self._forward_fp32('forward_fp32_train', x, True, want_feats)
+
+    @torch.no_grad()
+    def forward_fp32(self, x):
+        """forward() of the eval-mode network in fp32 on the f32-input MFMA kernels (DESIGN.md K16): (logits, feats), both fp32 at
+        the input size.  No buffer, operand or state is shared with forward()."""
+        self.check_fp32()
+        return self._forward_fp32('forward_fp32', x, False, True)
+
+    def _forward_fp32(self, name, x, train, want_feats):
+        """What forward_fp32 (`name`, train=False) and forward_fp32_train share: the input check, the network in its mode, the two
+        resizes to the input size and the linear probe."""
         if x.dtype != torch.float32 or x.ndim != 4:
-            raise ValueError("forward_fp32_train takes a float32 [B, 3, H, W] image batch")
+            raise ValueError(f"{name} takes a float32 [B, 3, H, W] image batch")
         input_shape = x.shape[-2:]
-        with engine.defer_bn_counters():
-            logist, feats = self.classifier.forward_fp32_autograd(self.backbone.forward_fp32_autograd(x))
+        if train:
+            with engine.defer_bn_counters():
+                logist, feats = self.classifier.forward_fp32_autograd(self.backbone.forward_fp32_autograd(x))
+        else:
+            logist, feats = self.classifier.forward_fp32(self.backbone.forward_fp32(x))
         logist = hip.bilinear_resize(logist, size=input_shape, align_corners=False)
         if isinstance(want_feats, str):
             if want_feats != 'lazy':
@@ -314,21 +306,6 @@ class deeplabv3_resnet50(nn.Module):
             feats = hip.UpsampledFeature(feats, input_shape, align_corners=False)
         else:
             feats = hip.bilinear_resize(feats, size=input_shape, align_corners=False) if want_feats else None
-        if self.if_linear_probing:
-            logist = hip.linear_probe(logist, self.linear_probe)
-        return logist, feats
-
-    @torch.no_grad()
-    def forward_fp32(self, x):
-        """forward() of the eval-mode network in fp32 on the f32-input MFMA kernels (DESIGN.md K16): (logits, feats), both fp32 at
-        the input size.  No buffer, operand or state is shared with forward()."""
-        self.check_fp32()
-        if x.dtype != torch.float32 or x.ndim != 4:
-            raise ValueError("forward_fp32 takes a float32 [B, 3, H, W] image batch")
-        input_shape = x.shape[-2:]
-        logist, feats = self.classifier.forward_fp32(self.backbone.forward_fp32(x))
-        logist = hip.bilinear_resize(logist, size=input_shape, align_corners=False)
-        feats = hip.bilinear_resize(feats, size=input_shape, align_corners=False)
         if self.if_linear_probing:
             logist = hip.linear_probe(logist, self.linear_probe)
         return logist, feats

@@ -8,6 +8,8 @@ so the logits are computed as ONE 1x1 conv with the composed operator T*W512*W25
 bias); the 512-channel full-resolution tensor (4.6 GB fp32 at DSEC B=8) is never materialised.
 Autograd differentiates the composition, so every parameter receives the same gradient.
 """
+from typing import Callable, NamedTuple
+
 import torch
 import torch.nn as nn
 import torch.nn.functional as f
@@ -52,6 +54,27 @@ def _conv(n_in, n_out, kernel_size, stride=1, padding=0, bias=True):
     return m
 
 
+def _conv_norm_f32(conv, norm, x, relu=False, residual=None):
+    """conv -> InstanceNorm2d [+ residual] [+ ReLU] in fp32, inference (K15): the norm in place on the conv's output."""
+    y = conv.forward_f32(x)
+    return hip.instance_norm_f32(y, relu=relu, residual=residual, eps=norm.eps, out=y)
+
+
+def _conv_norm_f32_train(conv, norm, x, relu=False, residual=None):
+    """The same step under autograd (K18), not in place."""
+    return hip.instance_norm_f32_train(conv.forward_f32_train(x), relu=relu, residual=residual, eps=norm.eps)
+
+
+class F32Layers(NamedTuple):
+    """The per-layer functions of one mode of the fp32 decoder: what SemSegE2VID._decoder_f32 and its blocks call."""
+    conv_norm: Callable            # (conv, norm, x, relu=False, residual=None) -> y
+    upsample_concat: Callable      # (x, skip=None) -> y
+
+
+F32_EVAL = F32Layers(_conv_norm_f32, hip.upsample2x_concat_f32)
+F32_TRAIN = F32Layers(_conv_norm_f32_train, hip.upsample2x_concat_f32_train)
+
+
 def _instance_norm(x, relu, residual=None):
     # nn.InstanceNorm2d defaults: affine=False, no running stats, eps=1e-5; fused [+ residual] [+ ReLU]
     return hip.instance_norm(x, relu=relu, residual=residual)
@@ -66,12 +89,14 @@ class ReLUINSConv2d(nn.Module):
     def forward(self, x):
         return _instance_norm(self.model[0](x), relu=True)
 
+    def _forward_f32(self, x, layers):
+        return layers.conv_norm(self.model[0], self.model[1], x, relu=True)
+
     def forward_f32(self, x):
-        y = self.model[0].forward_f32(x)
-        return hip.instance_norm_f32(y, relu=True, eps=self.model[1].eps, out=y)
+        return self._forward_f32(x, F32_EVAL)
 
     def forward_f32_train(self, x):
-        return hip.instance_norm_f32_train(self.model[0].forward_f32_train(x), relu=True, eps=self.model[1].eps)
+        return self._forward_f32(x, F32_TRAIN)
 
 
 class INSResBlock(nn.Module):
@@ -89,17 +114,17 @@ class INSResBlock(nn.Module):
             return self.model[5](_instance_norm(self.model[3](out), relu=False)) + x
         return _instance_norm(self.model[3](out), relu=False, residual=x)      # out += residual (:287)
 
+    def _forward_f32(self, x, layers):
+        y = layers.conv_norm(self.model[0], self.model[1], x, relu=True)
+        return layers.conv_norm(self.model[3], self.model[4], y, residual=x)
+
     def forward_f32(self, x):
-        y = self.model[0].forward_f32(x)
-        y = hip.instance_norm_f32(y, relu=True, eps=self.model[1].eps, out=y)
-        z = self.model[3].forward_f32(y)
-        return hip.instance_norm_f32(z, residual=x, eps=self.model[4].eps, out=z)
+        return self._forward_f32(x, F32_EVAL)
 
     def forward_f32_train(self, x):
         if len(self.model) > 5:
             raise NotImplementedError("forward_f32_train has no dropout (INSResBlock(dropout > 0))")
-        y = hip.instance_norm_f32_train(self.model[0].forward_f32_train(x), relu=True, eps=self.model[1].eps)
-        return hip.instance_norm_f32_train(self.model[3].forward_f32_train(y), residual=x, eps=self.model[4].eps)
+        return self._forward_f32(x, F32_TRAIN)
 
 
 def compose_head_f64(w256, b256, w512, b512, text):
@@ -231,30 +256,35 @@ class SemSegE2VID(nn.Module):
         params = (c256.weight, c256.bias, c512.weight, c512.bias, self.text_embeddings)
         return self._pw32_head.get_composed(params, lambda: compose_head_f64(*params))
 
+    def _decoder_f32(self, name, input_dict, layers):
+        """THE fp32 decoder walk of forward_fp32 and forward_fp32_train (`name`: the one called): decoder_scale_1 to 4 over the
+        latents on one F32Layers set.  Returns (out with the keys 8, 4 and 2, the decoder_scale_4 map)."""
+        for k in (1, 2, 4, 8):
+            if input_dict[k].dtype != torch.float32:
+                raise ValueError(f"{name} takes the fp32 latents of the fp32 E2VID path")
+        sz_in = input_dict[1].shape[3]
+        x = input_dict[8]
+        out = {8: x}
+        for layer in self.decoder_scale_1:
+            x = layer._forward_f32(x, layers)
+        x = layers.upsample_concat(x, input_dict[4])
+        for layer in self.decoder_scale_2:
+            x = layer._forward_f32(x, layers)
+        self.update_skip_dict(out, x, sz_in)
+        x = layers.upsample_concat(x, input_dict[2])
+        for layer in self.decoder_scale_3:
+            x = layer._forward_f32(x, layers)
+        self.update_skip_dict(out, x, sz_in)
+        x = layers.upsample_concat(x)
+        return out, self.decoder_scale_4[0]._forward_f32(x, layers)
+
     def forward_fp32(self, input_dict):
         """fp32 inference (K15): forward() in the reference's arithmetic.  input_dict: the fp32 latents {1, 2, 4, 8} of
         UNetRecurrent.forward_fp32 (logical NCHW, any strides; read where they are).  Returns (out, x_ch256) as forward():
         out[1] the fp32 logits at input size, out[2], out[4] the decoder features, x_ch256 fp32 or None."""
         self.check_fp32()
-        for k in (1, 2, 4, 8):
-            if input_dict[k].dtype != torch.float32:
-                raise ValueError("forward_fp32 takes the fp32 latents of the fp32 E2VID path")
         with torch.no_grad():
-            sz_in = input_dict[1].shape[3]
-            x = input_dict[8]
-            out = {8: x}
-            for layer in self.decoder_scale_1:
-                x = layer.forward_f32(x)
-            x = hip.upsample2x_concat_f32(x, input_dict[4])
-            for layer in self.decoder_scale_2:
-                x = layer.forward_f32(x)
-            self.update_skip_dict(out, x, sz_in)
-            x = hip.upsample2x_concat_f32(x, input_dict[2])
-            for layer in self.decoder_scale_3:
-                x = layer.forward_f32(x)
-            self.update_skip_dict(out, x, sz_in)
-            x = hip.upsample2x_concat_f32(x)
-            x = self.decoder_scale_4[0].forward_f32(x)
+            out, x = self._decoder_f32('forward_fp32', input_dict, F32_EVAL)
             x_ch256 = self.decoder_ch256[0].forward_f32(x) if self.materialize_ch256 else None
             pw = self._head_f32()
             K = self.text_embeddings.shape[0]
@@ -262,7 +292,7 @@ class SemSegE2VID(nn.Module):
             if self.if_linear_probing:
                 pp = self._pw32_probe.get(self.linear_probe.weight, self.linear_probe.bias)
                 logits = hip.conv2d_f32(logits, pp.packed, pp.bias, K, 1, 1)
-            self.update_skip_dict(out, logits, sz_in)
+            self.update_skip_dict(out, logits, input_dict[1].shape[3])
         return out, x_ch256
 
     def forward_fp32_train(self, input_dict):
@@ -274,26 +304,9 @@ class SemSegE2VID(nn.Module):
         With if_linear_probing the frozen decoder runs under no_grad and only hip.linear_probe trains.
         materialize_ch256='pooled' returns x_ch256 as the fp32 hip.PointwiseFeature."""
         self.check_fp32(train=True)
-        for k in (1, 2, 4, 8):
-            if input_dict[k].dtype != torch.float32:
-                raise ValueError("forward_fp32_train takes the fp32 latents of the fp32 E2VID path")
         frozen = self.if_linear_probing
         with torch.no_grad() if frozen else torch.enable_grad():
-            sz_in = input_dict[1].shape[3]
-            x = input_dict[8]
-            out = {8: x}
-            for layer in self.decoder_scale_1:
-                x = layer.forward_f32_train(x)
-            x = hip.upsample2x_concat_f32_train(x, input_dict[4])
-            for layer in self.decoder_scale_2:
-                x = layer.forward_f32_train(x)
-            self.update_skip_dict(out, x, sz_in)
-            x = hip.upsample2x_concat_f32_train(x, input_dict[2])
-            for layer in self.decoder_scale_3:
-                x = layer.forward_f32_train(x)
-            self.update_skip_dict(out, x, sz_in)
-            x = hip.upsample2x_concat_f32_train(x)
-            x = self.decoder_scale_4[0].forward_f32_train(x)
+            out, x = self._decoder_f32('forward_fp32_train', input_dict, F32_TRAIN)
             if self.materialize_ch256 == 'pooled':      # pre-training (K20): the superpixel mean commutes with the 1x1 conv
                 x_ch256 = hip.PointwiseFeature(x, self.decoder_ch256[0])
             else:
@@ -304,5 +317,5 @@ class SemSegE2VID(nn.Module):
             logits = hip.conv2d_f32_train(x, wf, bf, pw=self._pw32_head_train, ver=ver)
         if frozen:
             logits = hip.linear_probe(logits, self.linear_probe)
-        self.update_skip_dict(out, logits, sz_in)
+        self.update_skip_dict(out, logits, input_dict[1].shape[3])
         return out, x_ch256
