@@ -1037,6 +1037,31 @@ int oess_maskclip_refine_phase_ms(const float* logits, long long sb, long long s
                                   float pd_thresh, float ks_thresh, float* out, long long ob, long long oc, long long oy, long long ox,
                                   void* workspace, size_t workspace_bytes, float* phase_ms, oess_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------
+ * K27 Reconstructed grey levels -> the augmented student image of frame2recon.  Replaces, for `recon_sources: online_e2vid`,
+ * the host code of DSEC/dataset/sequence_ov.py:154-156 (the reconstruction PNG -> float CHW) and :204-221 (torch.flip,
+ * adjust_brightness, adjust_contrast, + 0.05 randn on the recon tensor).  Additions only: the ABI version stays.  No atomic:
+ * every result repeats bit for bit and a sample's result depends on neither B nor its place in the batch.
+ *
+ * oess_gray_augment_rgb_f32: u8 = uint8 [B, H, W] dense (PostProcessor.process_u8's bytes), out = fp32 [B, 3, H, W] dense.
+ *   Per sample b: v = byte / 255 (IEEE fp32 division) on three channels; flip_host[b] (0 / 1) mirrors along W;
+ *   v = clamp(brightness_host[b] v, 0, 1); m = mean of 0.2989 v + 0.587 v + 0.114 v over the sample (fp32 terms in that order;
+ *   two-level sum in a fixed order: fp32 partials of 4096 pixels, then their float64 sum);
+ *   v = clamp(contrast_host[b] v + (1 - contrast_host[b]) m, 0, 1), skipped for a factor of exactly 1 (the same bits);
+ *   noise_seed_host[b] != 0: v += 0.05 n, n ~ N(0, 1) from Philox-4x32-10 keyed by the seed, counter = index of the group of
+ *   four consecutive elements of the sample's [3, H, W] block, Box-Muller on u = ((word >> 8) + 1) 2^-24; no clamp afterwards.
+ *   The four host arrays are read during the call (they travel as kernel arguments): no device copy, no synchronisation.
+ *   scratch: oess_gray_augment_scratch_bytes(B, H, W) bytes, 4-byte aligned, written by the call; read only when some contrast
+ *   factor differs from 1 (may be null otherwise).
+ *   OESS_EINVAL before any launch: a null u8, out or host array, B, H or W < 1, 3 H W >= 2^31, out off 4 bytes, a flip outside
+ *   {0, 1}, a factor that is negative, infinite or NaN, a null or misaligned scratch when one is needed; OESS_ENOMEM: a short one.
+ * oess_gray_augment_scratch_bytes: 64-bit sizes in, 0 for a geometry that is refused.
+ * ------------------------------------------------------------------------------------------ */
+size_t oess_gray_augment_scratch_bytes(int64_t B, int64_t H, int64_t W);
+int oess_gray_augment_rgb_f32(const uint8_t* u8, int B, int H, int W, const int32_t* flip_host, const float* brightness_host,
+                              const float* contrast_host, const uint64_t* noise_seed_host, float* out, void* scratch,
+                              size_t scratch_bytes, oess_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -17,9 +17,11 @@ class DSECConcat(torch.utils.data.ConcatDataset):
 
     def __getitem__(self, idx):
         item = super().__getitem__(idx)
-        if isinstance(item, tuple) and isinstance(item[0], dict):
-            import bisect
-            item[0]['sequence'] = bisect.bisect_right(self.cumulative_sizes, idx if idx >= 0 else len(self) + idx)
+        if isinstance(item, tuple):
+            for ev in (item[0], item[2]):         # slot 2: the raw events of `recon_sources: online_e2vid`
+                if isinstance(ev, dict) and 'seg_offsets' in ev:
+                    import bisect
+                    ev['sequence'] = bisect.bisect_right(self.cumulative_sizes, idx if idx >= 0 else len(self) + idx)
         return item
 
     def rectify_maps(self, device):
@@ -43,7 +45,7 @@ class DatasetProvider:
     def __init__(self, dataset_path, mode='train', event_representation='voxel_grid', nr_events_data=5, delta_t_per_data=20,
                  nr_events_window=-1, nr_bins_per_data=5, require_paired_data=False, normalize_event=False, separate_pol=False,
                  semseg_num_classes=11, augmentation=False, fixed_duration=False, resize=False, config_option='', pl_sources='',
-                 superpixel_sources='', skip_ratio=1, if_sam_distillation=False, device_png=False):
+                 superpixel_sources='', skip_ratio=1, if_sam_distillation=False, device_png=False, recon_sources=None):
         dataset_path = Path(dataset_path)
         train_path, val_path = dataset_path / 'train', dataset_path / 'test'
         assert dataset_path.is_dir(), str(dataset_path)
@@ -53,7 +55,8 @@ class DatasetProvider:
         def sequences(path, names, mode_, **kw):
             return [Sequence(child, mode_, event_representation, nr_events_data, delta_t_per_data, nr_events_window, nr_bins_per_data,
                              require_paired_data, normalize_event, separate_pol, semseg_num_classes, augmentation, fixed_duration,
-                             resize=resize, config_option=config_option, pl_sources=pl_sources, device_png=device_png, **kw)
+                             resize=resize, config_option=config_option, pl_sources=pl_sources, device_png=device_png,
+                             recon_sources=recon_sources, **kw)
                     for child in path.iterdir() if any(k in str(child) for k in names)]
         if mode == 'train':
             self.train_dataset = DSECConcat(sequences(train_path, TRAIN_SEQUENCES, 'train', superpixel_sources=superpixel_sources,

@@ -10,7 +10,12 @@ with ONE difference that is the point of the MI355X path: in the voxel options t
 (13 bytes per event; `DataLoader(pin_memory=True)` pins them).  `voxelize_batch` turns a collated batch of these into the
 reference's tensor on the GPU: rectification gather, per-sub-window time normalisation, tri-linear splat, the
 `[:, :-40, :]` crop and the horizontal flip, all in `oess_voxelize_dsec_raw` (+ one flip kernel).  `materialize(index)`
-returns the reference's tuple exactly (voxel tensor first) for drop-in use and for the golden tests."""
+returns the reference's tuple exactly (voxel tensor first) for drop-in use and for the golden tests.
+
+`recon_sources='online_e2vid'` (extension) with config_option frame2recon: slot 2 is not the tensor read from
+`reconstructions/left/*.png` but the same raw-event dict plus 'aug': {'flip', 'brightness', 'contrast', 'noise_seed'} -- the
+recon's augmentation as the reference draws it (:204-221), applied on the GPU after the reconstruction (hip.recon_augment).  The
+`random` draws and their order are unchanged; torch.randn(recon.size()) becomes one torch.randint for the noise seed."""
 import os
 import random
 from pathlib import Path
@@ -23,12 +28,29 @@ from ...datasets import _io
 from ..utils.eventslicer import EventSlicer, open_h5
 
 
+ONLINE_E2VID = 'online_e2vid'
+
+
+def recon_aug_off():
+    """The recon's augmentation under `recon_sources: online_e2vid` with everything off (validation, or every coin said no)."""
+    return {'flip': False, 'brightness': 1.0, 'contrast': 1.0, 'noise_seed': 0}
+
+
+def draw_noise_seed():
+    """One torch draw for the Philox key of hip.recon_augment's noise: 1 .. 2^62 - 1 (0 means no noise)."""
+    return int(torch.randint(1, 2 ** 62, (1,)))
+
+
 class Sequence(Dataset):
     def __init__(self, seq_path, mode='train', event_representation='voxel_grid', nr_events_data=5, delta_t_per_data=20,
                  nr_events_per_data=100000, nr_bins_per_data=5, require_paired_data=False, normalize_event=False,
                  separate_pol=False, semseg_num_classes=11, augmentation=False, fixed_duration=False, remove_time_window=250,
                  resize=False, config_option='', pl_sources='', superpixel_sources='', skip_ratio=1, if_sam_distillation=False,
-                 device_png=False):
+                 device_png=False, recon_sources=None):
+        # recon_sources 'online_e2vid' (extension, DESIGN.md K27): with config_option frame2recon no file under reconstructions/ is
+        # opened; slot 2 of the tuple carries the sample's raw events and the recon's augmentation draws, and the trainer
+        # reconstructs and augments the image on the GPU (BaseTrainer.prepare_batch).  None = the PNG tree, as the reference.
+        self.recon_sources = recon_sources
         # device_png (extension, SURVEY 8f-3): label / pseudo-label / superpixel maps leave __getitem__ as the PNG FILE BYTES and are
         # decoded for the whole batch on the GPU (hip.png_decode_gray8_batch in BaseTrainer.prepare_batch), flips included
         self.device_png = bool(device_png)
@@ -151,10 +173,14 @@ class Sequence(Dataset):
         if self.config_option in ('frame2voxel', 'frame2recon'):
             p = file_path.replace('/semantic/left/', '/images_aligned/left/')
             frame = _io.image_to_chw_float(p.split('left/')[0] + 'left/' + name)
-        if self.config_option in ('recon2voxel', 'frame2recon'):
+        if self.config_option in ('recon2voxel', 'frame2recon') and not self.online_recon:
             p = file_path.replace('/semantic/left/', '/reconstructions/left/')
             recon = _io.image_to_chw_float(p.split('left/')[0] + 'left/' + name)
         return file_path, frame, recon
+
+    @property
+    def online_recon(self):
+        return self.recon_sources == ONLINE_E2VID and self.config_option == 'frame2recon'
 
     # ---- 8-bit maps: host tensors (the reference's path) or, with device_png, the undecoded file bytes
     def _map(self, path):
@@ -179,6 +205,10 @@ class Sequence(Dataset):
         label_tensor = self._map(label_path) if self.device_png else torch.from_numpy(self.get_label(label_path)).long()
         events = self.raw_events(index) if self.config_option in ('recon2voxel', 'frame2voxel') else None
         file_path, frame, recon = self._side_inputs(label_path)
+        if self.online_recon:
+            # the recon is computed on the GPU from these events; they stay unflipped (the IMAGE is mirrored, as the reference
+            # mirrors the PNG), so their own 'flip' stays False and the recon's flip travels in 'aug'
+            recon = dict(self.raw_events(index), aug=recon_aug_off())
         if self.mode == 'train':
             pl_path = file_path.replace('semantic/', self.pl_sources + '/').replace('11classes/', '')
             pl = self._map(pl_path)
@@ -201,7 +231,9 @@ class Sequence(Dataset):
                 if events is not None:
                     events['flip'] = True                                          # torch.flip(event_tensor, [2]) after voxelization
                 label_tensor = self._flip_map(label_tensor)
-                if recon is not None and opt != 'frame2voxel':
+                if isinstance(recon, dict):
+                    recon['aug']['flip'] = True
+                elif recon is not None and opt != 'frame2voxel':
                     recon = torch.flip(recon, [2])
                 if frame is not None and opt in ('frame2voxel', 'frame2recon'):
                     frame = torch.flip(frame, [2])
@@ -209,7 +241,21 @@ class Sequence(Dataset):
                     pl = self._flip_map(pl)
                 superpixel = self._flip_map(superpixel)
                 sam_feat = torch.flip(sam_feat, [2])
-            if opt == 'frame2recon':
+            if opt == 'frame2recon' and isinstance(recon, dict):
+                # the same `random` draws in the same order as below; the recon's factors go to the kernel (hip.recon_augment).
+                # The one torch draw that changes: randn(recon.size()) becomes one randint for the Philox seed, so the torch
+                # stream -- and with it the frame's noise values -- differs from a PNG-source run of the same seed
+                aug = recon['aug']
+                if random.random() >= 0.5:
+                    aug['brightness'] = random.uniform(0.8, 1.2)
+                    frame = _io.adjust_brightness(frame, random.uniform(0.8, 1.2))
+                if random.random() >= 0.5:
+                    aug['contrast'] = random.uniform(0.8, 1.2)
+                    frame = _io.adjust_contrast(frame, random.uniform(0.8, 1.2))
+                if random.random() >= 0.5:
+                    aug['noise_seed'] = draw_noise_seed()
+                    frame = frame + torch.randn(frame.size()) * 0.05
+            elif opt == 'frame2recon':
                 if random.random() >= 0.5:
                     recon = _io.adjust_brightness(recon, random.uniform(0.8, 1.2))
                     frame = _io.adjust_brightness(frame, random.uniform(0.8, 1.2))

@@ -213,6 +213,8 @@ SIGNATURES = {
                                          c_f, c_vp, c_ll, c_ll, c_ll, c_ll, c_vp, c_sz, c_vp]),
     "oess_maskclip_refine_phase_ms": (c_int, [c_vp, c_ll, c_ll, c_ll, c_ll, c_int, c_int, c_int, c_int, c_vp, c_int, c_ll, c_ll, c_int,
                                               c_f, c_f, c_vp, c_ll, c_ll, c_ll, c_ll, c_vp, c_sz, c_vp, c_vp]),
+    "oess_gray_augment_scratch_bytes": (c_sz, [c_i64, c_i64, c_i64]),
+    "oess_gray_augment_rgb_f32": (c_int, [c_vp, c_int, c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_sz, c_vp]),
 }
 
 _lib = None

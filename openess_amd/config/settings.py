@@ -13,6 +13,8 @@ appends SLIC's connectivity pass, and `online_slic_segments` must then be about 
 its fp32 forward; the student's step is not affected.
 `online_maskclip_refine: True` there (with the optional `online_maskclip_pd_thresh` 0.5 / `online_maskclip_ks_thresh` 1.0) takes
 that teacher's labels from MaskCLIP's refined output: prompt denoising and key smoothing.
+`recon_sources: 'online_e2vid'` there (with the optional `online_recon_precision` bf16 / fp32 and `online_recon_model`)
+reconstructs frame2recon's image from the sample's events on the GPU instead of reading `reconstructions/`.
 Quirk reproduced on purpose: `if_linear_probing` is read from the `clip:` block only (settings.py:258), so the
 reference's config/linear_probe/** files, which put it at top level, dispatch to OpenESSModel.
 """
@@ -212,3 +214,11 @@ class Settings:
             v = getattr(self, key)
             if isinstance(v, bool) or not isinstance(v, (int, float)) or not 0 <= v < float('inf'):
                 raise ValueError(f"clip.{key} must be a finite number >= 0, got {v!r}")
+        # `recon_sources: 'online_e2vid'`: frame2recon's reconstructed image is computed from the sample's raw
+        # events in the trainer's prepare_batch (voxelizer -> frozen E2VID -> PostProcessor -> hip.recon_augment) instead of read
+        # from `reconstructions/left/*.png`; None = the PNG tree.  `online_recon_precision` is the E2VID arithmetic there,
+        # `online_recon_model` its checkpoint ('random': seeded random weights, as run_reconstruction.load_model accepts).  What
+        # the key cannot serve is refused by the trainers (training/base_trainer_ov.py:online_recon_options).
+        self.recon_sources = c.get('recon_sources')
+        self.online_recon_precision = c.get('online_recon_precision', 'bf16')
+        self.online_recon_model = c.get('online_recon_model', self.path_to_model)

@@ -12,7 +12,7 @@ def DSECEvents(dsec_dir, nr_events_data=1, delta_t_per_data=50, nr_events_window
                task='segmentation', event_representation='voxel_grid', nr_bins_per_data=5, require_paired_data=False,
                separate_pol=False, normalize_event=False, semseg_num_classes=11, fixed_duration=False, resize=False,
                config_option='', pl_sources='', superpixel_sources='', skip_ratio=1, if_sam_distillation=False,
-               device_png=False):
+               device_png=False, recon_sources=None):
     dsec_dir = Path(dsec_dir)
     assert dsec_dir.is_dir()
     provider = DatasetProvider(dsec_dir, mode, event_representation=event_representation, nr_events_data=nr_events_data,
@@ -21,7 +21,8 @@ def DSECEvents(dsec_dir, nr_events_data=1, delta_t_per_data=50, nr_events_window
                                normalize_event=normalize_event, separate_pol=separate_pol, semseg_num_classes=semseg_num_classes,
                                augmentation=augmentation, fixed_duration=fixed_duration, resize=resize, config_option=config_option,
                                pl_sources=pl_sources, superpixel_sources=superpixel_sources, skip_ratio=skip_ratio,
-                               if_sam_distillation=if_sam_distillation, device_png=device_png)
+                               if_sam_distillation=if_sam_distillation, device_png=device_png,
+                               recon_sources=recon_sources)
     return provider.get_train_dataset() if mode == 'train' else provider.get_val_dataset()
 
 
@@ -30,7 +31,8 @@ def build_from_settings(s):
               nr_events_window=s.nr_events_window_b, event_representation=s.event_representation_b,
               nr_bins_per_data=s.nr_temporal_bins_b, separate_pol=s.separate_pol_b, normalize_event=s.normalize_event_b,
               semseg_num_classes=s.semseg_num_classes, fixed_duration=s.fixed_duration_b, config_option=s.config_option,
-              pl_sources=getattr(s, 'pl_sources', ''), device_png=getattr(s, 'device_png_decode', False))
+              pl_sources=getattr(s, 'pl_sources', ''), device_png=getattr(s, 'device_png_decode', False),
+              recon_sources=getattr(s, 'recon_sources', None))
     train = DSECEvents(augmentation=s.data_augmentation_train, mode='train', require_paired_data=s.require_paired_data_train_b,
                        superpixel_sources=dataset_superpixel_sources(s), skip_ratio=s.skip_ratio,
                        if_sam_distillation=getattr(s, 'if_sam_distillation', False), **kw)

@@ -11,12 +11,17 @@ import torch
 from torch.utils.data import Dataset
 
 from . import _synth
+from ..DSEC.dataset.sequence_ov import ONLINE_E2VID, recon_aug_off
 
 
 class SyntheticEvents(Dataset):
     def __init__(self, length=16, sensor_hw=(480, 640), crop_rows=40, nr_events_data=20, nr_events_window=100000,
                  nr_bins=5, num_classes=11, config_option='frame2voxel', superpixel_size=100, mode='train', seed=1205, pool=0,
-                 superpixel_sources=None):
+                 superpixel_sources=None, recon_sources=None, recon_augmentation=False):
+        # recon_sources 'online_e2vid' with frame2recon: slot 2 carries the sample's raw events (with explicit
+        # sub-window offsets) and the recon's augmentation draws instead of an image, as DSEC/dataset/sequence_ov.py does;
+        # recon_augmentation draws them for training samples from the sample's own generator (after every other draw)
+        self.recon_sources, self.recon_augmentation = recon_sources, bool(recon_augmentation)
         self.length, self.sensor_hw, self.crop_rows = length, tuple(sensor_hw), crop_rows
         self.nr_events_data, self.nr_events_window, self.nr_bins = nr_events_data, nr_events_window, nr_bins
         self.num_classes, self.config_option, self.superpixel_size = num_classes, config_option, superpixel_size
@@ -63,7 +68,18 @@ class SyntheticEvents(Dataset):
             superpixel = torch.ones_like(label)
         sam_feat = torch.ones(256, 64, 64)
         first = events if self.config_option in ('frame2voxel', 'recon2voxel') else frame
-        return first, label, frame, pl, superpixel, sam_feat, f"synthetic/{self.mode}/{index:06d}"
+        second = frame
+        if self.recon_sources == ONLINE_E2VID and self.config_option == 'frame2recon':
+            per = n // self.nr_events_data
+            aug = recon_aug_off()
+            if self.recon_augmentation and self.mode == 'train':
+                coins = rng.uniform(0, 1, 4) >= 0.5
+                factors = rng.uniform(0.8, 1.2, 2)
+                aug = {'flip': bool(coins[0]), 'brightness': float(factors[0]) if coins[1] else 1.0,
+                       'contrast': float(factors[1]) if coins[2] else 1.0,
+                       'noise_seed': int(rng.integers(1, 2 ** 62)) if coins[3] else 0}
+            second = dict(events, seg_offsets=torch.arange(self.nr_events_data + 1, dtype=torch.int64) * per, flip=False, aug=aug)
+        return first, label, second, pl, superpixel, sam_feat, f"synthetic/{self.mode}/{index:06d}"
 
 
 def collate(samples, arena=None):
@@ -74,10 +90,7 @@ def collate(samples, arena=None):
     (`cat` / `stack` with `out=` views of the slot) instead of into fresh allocations."""
     cat = torch.cat if arena is None else arena.cat
     stk = torch.stack if arena is None else arena.stack
-    first = [s[0] for s in samples]
-    if isinstance(first[0], dict) and 'events' in first[0]:                       # DDD17: int64 [N,4] rows per sample
-        batch0 = {'events_list': [f['events'] if arena is None else arena.put(f['events']) for f in first], 'flip': [bool(f.get('flip', False)) for f in first]}
-    elif isinstance(first[0], dict):                                              # DSEC / synthetic: x, y, t, p columns
+    def soa(first):                                                               # DSEC / synthetic: x, y, t, p columns
         ev = {k: cat([f[k] for f in first]) for k in ('x', 'y', 't', 'p')}
         ev['events_per_sample'] = torch.tensor([f['x'].numel() for f in first])
         if 'seg_offsets' in first[0]:
@@ -89,7 +102,13 @@ def collate(samples, arena=None):
             ev['flip'] = [bool(f.get('flip', False)) for f in first]
             if 'sequence' in first[0]:
                 ev['sequence'] = [int(f['sequence']) for f in first]
-        batch0 = ev
+        return ev
+
+    first = [s[0] for s in samples]
+    if isinstance(first[0], dict) and 'events' in first[0]:                       # DDD17: int64 [N,4] rows per sample
+        batch0 = {'events_list': [f['events'] if arena is None else arena.put(f['events']) for f in first], 'flip': [bool(f.get('flip', False)) for f in first]}
+    elif isinstance(first[0], dict):
+        batch0 = soa(first)
     else:
         batch0 = stk(first)
     n = len(samples[0])
@@ -100,6 +119,10 @@ def collate(samples, arena=None):
         if isinstance(col[0], dict) and 'png' in col[0]:      # undecoded 8-bit maps (device_png): the files back to back
             return {'png_bytes': cat([c['png'] for c in col]), 'png_lengths': [int(c['png'].numel()) for c in col],
                     'flip': [bool(c['flip']) for c in col], 'hw': tuple(col[0]['hw'])}
+        if isinstance(col[0], dict) and 'aug' in col[0]:      # raw events of `recon_sources: online_e2vid`: slot 0's SoA layout
+            ev = soa(col)                                     # plus the recon's four augmentation columns as lists
+            ev['aug'] = {k: [c['aug'][k] for c in col] for k in ('flip', 'brightness', 'contrast', 'noise_seed')}
+            return ev
         return stk(col)
     rest = [stack(i) for i in range(1, n - 1)]
     if n == 6:                     # DDD17 has no sam_feat (ddd17_events_loader.py:290): the batch ALWAYS carries the 7-slot layout

@@ -2247,6 +2247,59 @@ def e2vid_postprocess(img, weights, amount, bounds=None, hdr_state=None, out_u8=
     return out_u8, out_f32
 
 
+# ------------------------------------------------------------------------------------------ K27: grey levels -> augmented student image
+def recon_augment(u8, flip, brightness, contrast, noise_seed, out=None):
+    """uint8 [B, H, W] grey levels (PostProcessor.process_u8) -> fp32 [B, 3, H, W]: byte / 255 on three channels, then per sample
+    the reference's augmentation of the reconstruction (DSEC/dataset/sequence_ov.py:204-221) in its order: mirror along W
+    (`flip[b]`), adjust_brightness (`brightness[b]`, 1.0 = off), adjust_contrast (`contrast[b]`, 1.0 = off), + 0.05 N(0, 1) from
+    Philox keyed by `noise_seed[b]` (0 = off).  The four per-sample sequences live on the host and have length B; they travel as
+    kernel arguments, so nothing is copied or waited for.  ValueError before any launch for what the call cannot serve."""
+    import numpy as np
+    if not torch.is_tensor(u8) or u8.dtype != torch.uint8 or u8.dim() != 3:
+        raise ValueError("recon_augment needs a uint8 [B, H, W] tensor")
+    if not u8.is_cuda:
+        raise ValueError("recon_augment needs a GPU tensor (no CPU fallback)")
+    if not u8.is_contiguous() or u8.numel() == 0:
+        raise ValueError("recon_augment needs a contiguous, non-empty uint8 [B, H, W] tensor")
+    B, H, W = u8.shape
+    if 3 * H * W >= 2 ** 31:
+        raise ValueError(f"recon_augment: a {H} x {W} sample has 2^31 or more output elements")
+
+    def column(name, v, dtype):
+        if torch.is_tensor(v):
+            if v.is_cuda:
+                raise ValueError(f"recon_augment: {name} is a per-sample HOST sequence")
+            v = v.numpy()
+        a = np.ascontiguousarray(np.asarray(v)).astype(dtype, copy=False).reshape(-1)
+        if a.size != B:
+            raise ValueError(f"recon_augment: {name} has {a.size} entries for a batch of {B}")
+        return np.ascontiguousarray(a)
+
+    raw_flip = column('flip', flip, np.int64)
+    if ((raw_flip != 0) & (raw_flip != 1)).any():
+        raise ValueError("recon_augment: flip entries are 0 or 1")
+    f = raw_flip.astype(np.int32)
+    bri, con = column('brightness', brightness, np.float32), column('contrast', contrast, np.float32)
+    for name, a in (('brightness', bri), ('contrast', con)):
+        if not (np.isfinite(a).all() and (a >= 0).all()):
+            raise ValueError(f"recon_augment: {name} factors are finite and >= 0")
+    seed = column('noise_seed', noise_seed, np.uint64)
+    if out is None:
+        out = torch.empty((B, 3, H, W), dtype=torch.float32, device=u8.device)
+    elif (not torch.is_tensor(out) or not out.is_cuda or out.device != u8.device or out.dtype != torch.float32
+          or tuple(out.shape) != (B, 3, H, W) or not out.is_contiguous()):
+        raise ValueError("recon_augment: out must be a contiguous fp32 [B, 3, H, W] tensor on u8's device")
+    lib = _lib.load()
+    ws, need = None, 0
+    if (con != 1.0).any():
+        need = lib.oess_gray_augment_scratch_bytes(B, H, W)
+        ws = _workspace(need, u8.device, tag="recon_augment")
+    _lib.check(lib.oess_gray_augment_rgb_f32(_ptr(u8), B, H, W, f.ctypes.data, bri.ctypes.data, con.ctypes.data, seed.ctypes.data,
+                                             _ptr(out), _ptr(ws), need, _stream()), "oess_gray_augment_rgb_f32")
+    _bump(out)
+    return out
+
+
 # ------------------------------------------------------------------------------------------ K14: fp32 E2VID inference
 _F32_ACT = {None: 0, 'relu': 1, 'sigmoid': 2}
 

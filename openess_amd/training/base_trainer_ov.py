@@ -14,6 +14,7 @@ from torch.utils.data import DataLoader, Subset
 
 from .. import hip
 from ..config.settings import ONLINE_SLIC, dataset_superpixel_sources
+from ..DSEC.dataset.sequence_ov import ONLINE_E2VID, voxelize_raw_batch
 from ..evaluation.metrics import MetricsSemseg
 from ..utils.saver import CheckpointSaver
 from .ddp import GradAllReduce, broadcast_module_states, shard_indices
@@ -69,9 +70,56 @@ def online_maskclip_refine(settings):
     return {'pd_thresh': getattr(settings, 'online_maskclip_pd_thresh', 0.5), 'ks_thresh': getattr(settings, 'online_maskclip_ks_thresh', 1.0)}
 
 
+def online_recon_options(settings):
+    """`recon_sources: 'online_e2vid'` (clip block): frame2recon's reconstructed image comes from the sample's
+    events, inside prepare_batch.  None when the key is absent (the PNG tree), else {'precision', 'model'}.  The refusals of the
+    key, each before anything is built: another config_option (only frame2recon reads a reconstruction next to a frame;
+    recon2voxel stays on the PNG tree), DDD17 (its loader carries no raw events beside the frame), an unknown precision, a model
+    file that does not exist ('random' is accepted, as e2vid.run_reconstruction.load_model accepts it), and auto-HDR (its
+    window belongs to a sequence, not to a shuffled batch)."""
+    import os
+    src = getattr(settings, 'recon_sources', None)
+    if src is None:
+        return None
+    if src != ONLINE_E2VID:
+        raise ValueError(f"recon_sources must be {ONLINE_E2VID!r} or absent (the reconstructions/ tree), got {src!r}")
+    if settings.config_option != 'frame2recon':
+        raise ValueError(f"recon_sources: {ONLINE_E2VID} serves config_option frame2recon, got {settings.config_option!r}")
+    if settings.dataset_name_b != 'DSEC_events':
+        raise ValueError(f"recon_sources: {ONLINE_E2VID} serves DSEC_events, got {settings.dataset_name_b!r}")
+    precision = getattr(settings, 'online_recon_precision', 'bf16')
+    if precision not in ('bf16', 'fp32'):
+        raise ValueError(f"online_recon_precision must be 'bf16' or 'fp32', got {precision!r}")
+    model = getattr(settings, 'online_recon_model', None) or settings.path_to_model
+    if model != 'random' and not os.path.isfile(model):
+        raise ValueError(f"online_recon_model: E2VID checkpoint {model!r} not found ('random' builds seeded random weights)")
+    if getattr(settings.e2vid_config, 'auto_hdr', False):
+        raise ValueError(f"recon_sources: {ONLINE_E2VID} has no auto_hdr: its window is a property of a sequence, not of a batch")
+    return {'precision': precision, 'model': model}
+
+
+def online_recon_image(rec, post, vox, n, C, aug):
+    """The voxels [B, n C, H, W] of n sub-windows -> the augmented student image fp32 [B, 3, H, W]: the frozen
+    E2VID behind the ImageReconstructor `rec` over the sub-windows from empty states, leaving empty states -- sub-windows
+    0 .. n - 2 with their latents dropped (bf16: fused head + skewed schedule; fp32: encoders only), the decoder once, on the last
+    one -- then `post`.process_u8 on the cropped image and hip.recon_augment with the per-sample columns of `aug`."""
+    fp32 = rec.precision == 'fp32'
+    rec.last_states_for_each_channel = {'grayscale': None}
+    for i in range(n - 1):
+        kw = {'latents_only': True} if fp32 else {'need_latents': False}
+        rec.update_reconstruction(vox, channel_slice=(i * C, C), **kw)
+    img, _, _ = rec.update_reconstruction(vox, channel_slice=((n - 1) * C, C), reconstruct=True)
+    rec.last_states_for_each_channel = {'grayscale': None}        # the sequence ends with the batch
+    if rec.crop.needs_pad:
+        img = img[:, :, rec.crop.iy0:rec.crop.iy1, rec.crop.ix0:rec.crop.ix1]
+    u8 = post.process_u8(img[:, :1])
+    return hip.recon_augment(u8, [int(bool(f)) for f in aug['flip']], aug['brightness'], aug['contrast'], aug['noise_seed'])
+
+
 class BaseTrainer(object):
     is_training = True
     online_slic_segments = None      # SLIC's n_segments under `superpixel_sources: online_slic`, set by __init__
+    online_recon = None              # {'precision', 'model'} under `recon_sources: online_e2vid`, set by __init__
 
     def __init__(self, settings, train=True):
         self.settings = settings
@@ -79,6 +127,7 @@ class BaseTrainer(object):
         # before anything is built: what `superpixel_sources: online_slic` cannot serve is refused here
         self.online_slic_segments = online_slic_segments(settings, self.pooling_size())
         online_maskclip_refine(settings)         # `online_maskclip_refine: True` without its teacher is refused here too
+        self.online_recon = online_recon_options(settings)      # and what `recon_sources: online_e2vid` cannot serve
         if not torch.cuda.is_available():
             raise RuntimeError("openess_amd trainers need the GPU (no CPU fallback in the product path)")
         self.device = torch.device('cuda', torch.cuda.current_device())
@@ -109,6 +158,8 @@ class BaseTrainer(object):
         self.init_fn()
         self.createDataLoaders()
         self.models_dict = {k: v.to(self.device) for k, v in self.models_dict.items()}
+        if self.online_recon:
+            self.build_online_recon()
         self.saver = CheckpointSaver(save_dir=settings.ckpt_dir)
         self.epoch_count = self.step_count = 0
         self.checkpoint = None
@@ -132,6 +183,46 @@ class BaseTrainer(object):
     def pooling_size(self):
         """Rows per sample of the superpixel pooling: OpenESSModel pools with its own hard-coded size."""
         return getattr(self, 'pool_superpixel_size', None) or getattr(self.settings, 'superpixel_size', 100)
+
+    def build_online_recon(self):
+        """`recon_sources: online_e2vid`: a frozen E2VIDRecurrent of the trainer's own behind an ImageReconstructor
+        of the requested precision, and the PostProcessor of settings.e2vid_config (reference defaults: unsharp 0.3, sigma 1,
+        Imin 0, Imax 1).  The model is not entered in models_dict: never trained, never saved, checkpoint layouts untouched.
+        Building it leaves the torch generators where they were ('random' seeds one)."""
+        from types import SimpleNamespace
+        from ..e2vid.image_reconstructor import ImageReconstructor, PostProcessor
+        from ..e2vid.run_reconstruction import load_model
+        s = self.settings
+        with torch.random.fork_rng(devices=[self.device]):
+            model = load_model(self.online_recon['model'])
+        for p in model.parameters():
+            p.requires_grad = False
+        self.recon_model = model.to(self.device).eval()
+        opts = SimpleNamespace(**dict(vars(s.e2vid_config), precision=self.online_recon['precision']))
+        self.recon_reconstructor = ImageReconstructor(self.recon_model, s.img_size_b[0], s.img_size_b[1], s.nr_temporal_bins_b,
+                                                      self.device, opts)
+        self.recon_postprocessor = PostProcessor(self.device, s.e2vid_config)
+
+    def voxelize_events(self, ev, split):
+        """Collated raw events with explicit sub-window offsets -> [B, nr_events_data * C, H, W] on this stream."""
+        ds = self._voxel_ds[split]
+        if hasattr(ds, 'voxelize_batch'):
+            return ds.voxelize_batch(ev, self.device)
+        s = self.settings
+        (H, W), crop = self.sensor_geometry                         # the synthetic provider: one rectify map, held by the trainer
+        return voxelize_raw_batch(ev, self.device, self.rectify_maps, s.nr_temporal_bins_b, H, W, crop, s.nr_events_data_b)
+
+    def reconstruct_online(self, ev, split):
+        """Slot 2 under `recon_sources: online_e2vid`: collated raw events + the recon's augmentation columns -> the fp32
+        [B, 3, H, W] image the student reads.  Voxelizer, the frozen E2VID over the sub-windows from empty states (the decoder
+        runs once, on the last one), PostProcessor.process_u8, hip.recon_augment: all enqueued on the current stream (the ingest
+        stream, under the previous step), nothing is waited for.  Validation batches take the same route with everything off."""
+        s = self.settings
+        vox = self.voxelize_events(ev, split)
+        aug, B = ev['aug'], vox.shape[0]
+        if split != 'train':
+            aug = {'flip': [False] * B, 'brightness': [1.0] * B, 'contrast': [1.0] * B, 'noise_seed': [0] * B}
+        return online_recon_image(self.recon_reconstructor, self.recon_postprocessor, vox, s.nr_events_data_b, s.input_channels_b, aug)
 
     @staticmethod
     def rank_hint():
@@ -289,8 +380,11 @@ class BaseTrainer(object):
                           num_classes=s.semseg_num_classes, config_option=s.config_option,
                           superpixel_size=getattr(s, 'superpixel_size', 100))
             n_train = getattr(s, 'synthetic_length', 2 * s.batch_size_b * self.world)
+            if self.online_recon:
+                common.update(recon_sources=ONLINE_E2VID)
             train_ds = builder(length=n_train, mode='train', pool=getattr(s, 'synthetic_pool', 0),
-                               superpixel_sources='' if self.online_slic_segments else None, **common)
+                               superpixel_sources='' if self.online_slic_segments else None,
+                               **({'recon_augmentation': bool(s.data_augmentation_train)} if self.online_recon else {}), **common)
             val_ds = builder(length=max(s.batch_size_b, 2), mode='val', **common)
         elif s.dataset_name_b == 'DSEC_events':
             train_ds, val_ds = self.createDSECDataset(
@@ -335,6 +429,8 @@ class BaseTrainer(object):
                   event_representation=event_representation, nr_bins_per_data=nr_bins_per_data, separate_pol=separate_pol,
                   normalize_event=normalize_event, semseg_num_classes=semseg_num_classes, fixed_duration=fixed_duration,
                   config_option=config_option, pl_sources=pl_sources, device_png=getattr(self.settings, 'device_png_decode', False))
+        if self.online_recon:
+            kw['recon_sources'] = ONLINE_E2VID          # slot 2 then carries raw events, no reconstructions/ file is opened
         train = builder(augmentation=augmentation, mode='train', require_paired_data=require_paired_data_train,
                         superpixel_sources=superpixel_sources, skip_ratio=skip_ratio, if_sam_distillation=if_sam_distillation, **kw)
         val = builder(augmentation=False, mode='val', require_paired_data=require_paired_data_val, superpixel_sources='', skip_ratio=2,
@@ -373,6 +469,9 @@ class BaseTrainer(object):
                 # per slot: device tensor, non-zero = that map was filled with the ignore index.  Kept (with the file names) for
                 # check_png_status(), which runs off the hot path -- one .any() sync per `png_check_every` batches and at epoch end
                 self._png_pending.append((i + 1, status, list(sample_batched[-1]) if isinstance(sample_batched[-1], (list, tuple)) else None))
+        if isinstance(rest[1], dict) and 'aug' in rest[1]:
+            # recon_sources: online_e2vid (K27): the reconstruction from the sample's events, on this stream -- the ingest stream
+            rest[1] = self.reconstruct_online(rest[1], split)
         ds = self._voxel_ds[split]
         if isinstance(first, dict) and 'events_list' in first:            # DDD17: int64 [N,4] rows per sample
             first = ds.voxelize_batch(first['events_list'], self.device, flips=first.get('flip'))
