@@ -379,6 +379,52 @@ int oess_convlstm_w128_group_bf16(const oess_convlstm_desc_t* problems, int n, o
  * CPU tests check that every tile of every problem appears exactly once. */
 int oess_convlstm_w128_tile_lists(const int* tiles_m, const int* tiles_n, const int* cin, int n, int grid, int* lists, int capacity, int* stride);
 
+/* ------------------------------------------------------------------------------------------
+ * K28 ConvGRU (e2vid/model/submodules.py:217-253 of the reference; recurrent_block_type 'convgru').  Additions only: the ABI
+ * version and OESS_ROUTE_COUNT stay (these are entry points of their own, not routes of oess_conv2d_fwd_bf16).
+ *   u = sigmoid(conv(cat(x, h), Wu) + bu),  r = sigmoid(conv(cat(x, h), Wr) + br)          (gates)
+ *   o = tanh(conv(cat(x, r * h), Wo) + bo), h' = h * (1 - u) + o * u                        (output)
+ *
+ * bf16: TWO launches per step, each an LDS-DMA MFMA convolution with the gate algebra in its epilogue; u, r and o never exist as
+ * pre-activation tensors, nothing is concatenated or copied.  h is kept in fp32 ([B H W][C], dense: the "master") next to the
+ * bf16 copy the next step convolves, as the ConvLSTM cell is: the blend does not round h to bf16 once per step.
+ * Geometry: 3 x 3 / pad 1, C_hidden % 32 == 0, Cin == 2 C_hidden (the two-part window) or Cin == C_hidden (x alone with the
+ * x-half weights: the step from a zero state, h_prev must then be NULL), in_pix_stride and the output pixel strides % 8 == 0,
+ * every pointer 16-byte aligned, B H W < 2^31 and the input window below 2 GiB.  Anything else -- a 5 x 5 gate, another
+ * Cin (input_size != hidden_size), C_hidden % 32 != 0, a null pointer -- returns OESS_EINVAL before any launch; there is no
+ * other bf16 form.  Pixel strides are in ELEMENTS.
+ *   oess_convgru_gates_bf16: in = the (h | x) window (or x alone), NHWC bf16.  w_packed_gates = oess_conv2d_pack_weight(.., 0) of
+ *     the [2 C, Cin, 3, 3] weight whose row 2 hc + g is row hc of Wu (g = 0) / Wr (g = 1), input channels in the window's order;
+ *     bias = [bu | br] (2 C floats) or NULL.  h_prev: the fp32 master or NULL (= zero state).  Writes u (fp32 [B H W][C]) and
+ *     bf16(r * h_prev) into the window rh (pixel stride rh_pix_stride); rh_f32 (nullable, fp32 [B H W][C]) receives r * h_prev
+ *     before that rounding (tests).  No output may overlap `in`, h_prev or another output (checked, OESS_EINVAL): channel windows
+ *     of ONE buffer (same pixel stride) that do not share a channel count as disjoint.
+ *   oess_convgru_out_bf16: in = the (x | r * h) window (or x alone); w_packed = oess_conv2d_pack_weight(.., 0) of Wo restricted
+ *     to the window's channels; bias = bo or NULL; u from the gates launch.  Writes the new master h (fp32; h == h_prev, in
+ *     place, is allowed: a value is read and written by the one lane that owns it) and its bf16 rounding into the window h_bf16.
+ *     h_bf16 and h must not overlap `in`, u or each other, h_bf16 not h_prev, and h overlaps h_prev only by being it (checked).
+ *   One NHWC bf16 buffer [B][H][W][3 C] ordered h | x | r * h serves both: the encoder conv writes x into [C, 2C), the gates
+ *   launch convolves [0, 2C) (Wu / Wr with their input-channel halves swapped at pack time) and writes [2C, 3C), the output launch
+ *   convolves [C, 3C) in the reference's own channel order and writes [0, C).  No launch writes a window it convolves.
+ *   sigmoid / tanh are the fused ConvLSTM's fast forms (exp + rcp).
+ *
+ * fp32: oess_conv2d_fwd_f32 produces the pre-activations ([B H W][2 C] = u | r, then [B H W][C] = o, dense), two pointwise
+ * kernels do the rest: four launches per step.  oess_convgru_f32_workspace_bytes(pixels, C) = room for both pre-activation
+ * tensors and u (4 C floats per pixel).  No geometry rule beyond the convolution's own.
+ *   oess_convgru_gates_f32: u = sigmoid(pre[:, :C]) -> u (dense), sigmoid(pre[:, C:]) * h_prev -> the view rh.  h_prev NULL = zero.
+ *   oess_convgru_blend_f32: h = h_prev * (1 - u) + tanh(pre) * u -> the view h (h may be the view h_prev itself).
+ *   Views are B x H x W x C_hidden.  An output may not overlap an input or another output, except rh / h being the very view
+ *   h_prev (element-wise in place); NHWC channel windows of one buffer count as disjoint as above, other views by their byte
+ *   range; negative strides, null data, pointers off 4 bytes and more than (2^31 - 1) * 256 elements (one thread each on a
+ *   one-dimensional grid; the workspace query answers 0 there) are OESS_EINVAL.
+ * ------------------------------------------------------------------------------------------ */
+int oess_convgru_gates_bf16(const void* in, long long in_pix_stride, int B, int H, int W, int Cin, const void* w_packed_gates,
+                            const float* bias, int C_hidden, int R, int S, int pad, const float* h_prev, float* u, void* rh,
+                            long long rh_pix_stride, float* rh_f32, oess_stream_t stream);
+int oess_convgru_out_bf16(const void* in, long long in_pix_stride, int B, int H, int W, int Cin, const void* w_packed,
+                          const float* bias, int C_hidden, int R, int S, int pad, const float* u, const float* h_prev, float* h,
+                          void* h_bf16, long long h_bf16_pix_stride, oess_stream_t stream);
+
 /* n <= 2 INDEPENDENT 5x5 / stride-2 / pad-2 convolutions (out = act(conv(in, w) + bias), arguments as oess_conv2d_fwd_bf16 with
  * R = S = 5, stride 2, pad 2, relu in {0, 1}) in ONE launch: the encoder ConvLayers of levels 1 and 2 of E2VID's recurrent encoder
  * (e2vid/model/unet.py:141-150, submodules.py:96-115) on the skewed schedule.  Results are those of separate calls.  Neither output
@@ -713,6 +759,12 @@ int oess_conv_transpose2d_fwd_f32(const oess_f32_view_t* in, const oess_f32_view
 int oess_convlstm_step_f32(const oess_f32_view_t* xh, int B, int H, int W, int Cin, const float* w_packed, const float* bias,
                            int C_hidden, int R, int S, int pad, int prev_cell_is_zero, float* cell, const oess_f32_view_t* hidden,
                            void* ws, size_t ws_bytes, oess_stream_t stream);
+/* K28: the fp32 ConvGRU step's pointwise halves (contract in the ConvGRU block above) */
+size_t oess_convgru_f32_workspace_bytes(long long pixels, int C_hidden);     /* 0 for an impossible geometry */
+int oess_convgru_gates_f32(const float* pre, const oess_f32_view_t* h_prev, int B, int H, int W, int C_hidden, float* u,
+                           const oess_f32_view_t* rh, oess_stream_t stream);
+int oess_convgru_blend_f32(const float* pre, const float* u, const oess_f32_view_t* h_prev, int B, int H, int W, int C_hidden,
+                           const oess_f32_view_t* h, oess_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
  * K15 fp32 SemSegE2VID inference (models/style_networks.py:9-198 of the reference, validation with eval_precision: fp32): the

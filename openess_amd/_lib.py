@@ -77,6 +77,13 @@ SIGNATURES = {
     "oess_convlstm_w128_cell_relayout": (c_int, [c_vp, c_vp, c_ll, c_int, c_int, c_vp]),
     "oess_convlstm_w128_group_bf16": (c_int, [c_vp, c_int, c_vp]),
     "oess_convlstm_w128_tile_lists": (c_int, [c_vp, c_vp, c_vp, c_int, c_int, c_vp, c_int, c_vp]),
+    "oess_convgru_gates_bf16": (c_int, [c_vp, c_ll, c_int, c_int, c_int, c_int, c_vp, c_vp, c_int, c_int, c_int, c_int, c_vp, c_vp,
+                                        c_vp, c_ll, c_vp, c_vp]),
+    "oess_convgru_out_bf16": (c_int, [c_vp, c_ll, c_int, c_int, c_int, c_int, c_vp, c_vp, c_int, c_int, c_int, c_int, c_vp, c_vp,
+                                      c_vp, c_vp, c_ll, c_vp]),
+    "oess_convgru_f32_workspace_bytes": (c_sz, [c_ll, c_int]),
+    "oess_convgru_gates_f32": (c_int, [c_vp, c_view, c_int, c_int, c_int, c_int, c_vp, c_view, c_vp]),
+    "oess_convgru_blend_f32": (c_int, [c_vp, c_vp, c_view, c_int, c_int, c_int, c_int, c_view, c_vp]),
     "oess_conv5x5s2_group_bf16": (c_int, [c_vp, c_int, c_vp]),
     "oess_loss_partials_bytes": (c_sz, []),
     "oess_l1_mean_fwd": (c_int, [c_vp, c_vp, c_i64, c_int, c_vp, c_vp, c_vp]),

@@ -50,6 +50,11 @@ struct ConvArgs {
     // row-halo kernel: exact reciprocals of W and W + dil for the small per-lane quotients of its prologue (x < 256:
     // x / d == umulhi(x, floor(2^32 / d) + 1) whenever x * d < 2^32); 0 = divide
     unsigned mg_w, mg_wd;
+    // fused ConvGRU epilogues (EPI == 2 gates, EPI == 3 output: convgru_epilogue.h).  They reuse lstm_prev (fp32 master of
+    // h_prev or null = zero state), lstm_cell (EPI 2: u out; EPI 3: the new fp32 master), lstm_h / lstm_h_stride (EPI 2: the
+    // r*h window; EPI 3: the bf16 copy of the master) and lstm_C.
+    const float* gru_u;        // EPI 3: [M][C] fp32 update gate written by the gates launch
+    float* gru_rh32;           // EPI 2: optional [M][C] fp32 r*h before its bf16 rounding (tests), or null
 };
 
 __device__ __forceinline__ int swz(int row, int chunk) { return chunk ^ ((row >> 1) & 7); }

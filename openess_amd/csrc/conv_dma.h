@@ -119,6 +119,8 @@ __global__ __launch_bounds__(NTHREADS) void conv_fwd_dma_kernel(ConvArgs a) {
     f32x16_t acc[MT][NT];
     if constexpr (EPI == 1) {
         lstm_bias_init<MT, NT>(a, acc, n0, wn, lane);
+    } else if constexpr (EPI == 2 || EPI == 3) {
+        gru_bias_init<EPI, MT, NT>(a, acc, n0, wn, lane);
     } else {
 #pragma unroll
         for (int i = 0; i < MT; ++i)
@@ -194,6 +196,8 @@ __global__ __launch_bounds__(NTHREADS) void conv_fwd_dma_kernel(ConvArgs a) {
 
     if constexpr (LSTM_PREF) lstm_epilogue<MT, NT, true, false>(a, acc, smem, m0, n0, wm, wn, lane, tid, &pref);
     else if constexpr (EPI == 1) lstm_epilogue<MT, NT, false, false>(a, acc, smem, m0, n0, wm, wn, lane, tid);
+    else if constexpr (EPI == 2) gru_gates_epilogue<MT, NT>(a, acc, smem, m0, n0, wm, wn, lane, tid);       // convgru_epilogue.h
+    else if constexpr (EPI == 3) gru_out_epilogue<MT, NT>(a, acc, smem, m0, n0, wm, wn, lane, tid);
     else {
         if (a.partial) {        // split-K slice: raw fp32 accumulators, 128-byte row segments per half wave
             float* dst = a.partial + (size_t)blockIdx.y * (size_t)a.M * a.Cout;

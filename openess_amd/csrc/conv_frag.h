@@ -5,12 +5,12 @@
 // The using scope provides constexpr MT, NT (32 x 32 fragments of the wave tile along pixels / channels), EPI and
 // f32x16_t acc[MT][NT].
 
-// acc += A * B for every fragment pair; EPI == 1 (fused ConvLSTM) runs the product transposed: weights are the MFMA A operand
+// acc += A * B for every fragment pair; EPI != 0 (fused ConvLSTM, fused ConvGRU) runs the product transposed: weights are the MFMA A operand
 #define OESS_FRAG_MMA(SRC_A, SRC_B)                                                                              \
     {                                                                                                            \
         _Pragma("unroll") for (int i = 0; i < MT; ++i)                                                           \
             _Pragma("unroll") for (int j = 0; j < NT; ++j)                                                       \
-                acc[i][j] = (EPI == 1) ? __builtin_amdgcn_mfma_f32_32x32x16_bf16(SRC_B[j], SRC_A[i], acc[i][j], 0, 0, 0)     \
+                acc[i][j] = (EPI != 0) ? __builtin_amdgcn_mfma_f32_32x32x16_bf16(SRC_B[j], SRC_A[i], acc[i][j], 0, 0, 0)     \
                                        : __builtin_amdgcn_mfma_f32_32x32x16_bf16(SRC_A[i], SRC_B[j], acc[i][j], 0, 0, 0);   \
     }
 

@@ -2,6 +2,7 @@
 // the w128 tile schedule, the fused head launch, every extern "C" entry).  The kernels live in headers included below, inside
 // this file's anonymous namespace, one family each:
 //   conv_args.h        operand layout, ConvArgs, LDS swizzle, output store, activation, conv_epilogue, ConvLSTM epilogue
+//   convgru_epilogue.h the fused ConvGRU epilogues conv_fwd_dma_kernel names (instantiated by convgru.hip)
 //   conv_frag.h        the fragment macros the K loops share (MFMA block, counted LDS wait, w128 fragment reads)
 //   conv_general.h     conv_fwd_kernel: register-staged general route
 //   conv_dma.h         conv_fwd_dma_kernel (LDS-DMA routes, split-K slices, 256 x 256 tile), splitk_reduce_kernel
@@ -30,6 +31,7 @@ namespace {
 using namespace oess;
 
 #include "conv_args.h"
+#include "convgru_epilogue.h"
 #include "conv_frag.h"
 #include "conv_general.h"
 #include "conv_dma.h"

@@ -61,10 +61,12 @@ class ImageReconstructor:
             else:
                 events, (c0, cs) = event_tensor, channel_slice
             import contextlib
+            unet = getattr(self.model, 'unetrecurrent', None)
+            if unet is not None and unet.recurrent_block_type != 'convlstm':
+                wavefront = None        # a ConvLSTM schedule (K28): everything, the slice kernel included, stays on the current stream
             kw = {} if wavefront is None else {'wavefront': wavefront}
             if not need_latents and not reconstruct:
                 kw['need_head'] = False
-            unet = getattr(self.model, 'unetrecurrent', None)
             if self.skew and wavefront is None and not reconstruct and not self.no_recurrent and events.is_cuda and unet is not None:
                 kw['skew'] = True
             if (not need_latents and not reconstruct and not self.crop.needs_pad and unet is not None

@@ -258,16 +258,123 @@ class ConvLSTM(nn.Module):
         return h_view
 
 
+class ConvGRU(nn.Module):
+    """e2vid/model/submodules.py:217-253.  State = the hidden state.  Here it lives in ONE NHWC bf16 buffer `hxr` = [B, H, W, 3C]
+    ordered h | x | r*h (x written by the encoder conv, r*h by the gates launch, h by the output launch: no torch.cat, no copy,
+    no ping-pong: no launch writes a window it convolves) plus `h32`, the fp32 master of h (the blend h (1 - u) + o u does not
+    round h to bf16 once per sub-window), and `u`, the update gate between the two launches.  K28 of DESIGN.md."""
+
+    def __init__(self, input_size, hidden_size, kernel_size):
+        super().__init__()
+        pad = kernel_size // 2
+        self.input_size = input_size
+        self.hidden_size = hidden_size
+        self.reset_gate = nn.Conv2d(input_size + hidden_size, hidden_size, kernel_size, padding=pad)
+        self.update_gate = nn.Conv2d(input_size + hidden_size, hidden_size, kernel_size, padding=pad)
+        self.out_gate = nn.Conv2d(input_size + hidden_size, hidden_size, kernel_size, padding=pad)
+        for g in (self.reset_gate, self.update_gate, self.out_gate):
+            nn.init.orthogonal_(g.weight)
+            nn.init.constant_(g.bias, 0.)
+        # operands by (phase, fresh): the gates pair (update, reset) and the out gate, for the two-part window and for x alone
+        self._pw = {(ph, fr): engine.PackedWeight() for ph in ('gates', 'out') for fr in (False, True)}
+        self._pw32 = {(ph, fr): engine.PackedWeightF32() for ph in ('gates', 'out') for fr in (False, True)}
+
+    def _weights(self, phase, fresh, dtype, interleave):
+        """(weight, bias) of one launch in `dtype`.  gates: update and reset stacked (rows 2 hc + gate when `interleave`, else
+        update | reset), input channels reordered from the reference's (x | h) to the state buffer's (h | x); out: the out gate in
+        its own (x | r*h) order.  fresh: the x half alone (h = 0)."""
+        X = self.input_size
+        if phase == 'out':
+            w, b = self.out_gate.weight.detach().to(dtype), self.out_gate.bias.detach().to(dtype)
+            return (w[:, :X] if fresh else w), b
+        ws = [g.weight.detach().to(dtype) for g in (self.update_gate, self.reset_gate)]
+        ws = [w[:, :X] if fresh else torch.cat([w[:, X:], w[:, :X]], 1) for w in ws]
+        w = torch.stack(ws, 1).flatten(0, 1) if interleave else torch.cat(ws, 0)
+        return w, torch.cat([self.update_gate.bias.detach().to(dtype), self.reset_gate.bias.detach().to(dtype)])
+
+    def _convs(self, phase):
+        return (self.out_gate,) if phase == 'out' else (self.update_gate, self.reset_gate)
+
+    def _packed(self, phase, fresh):
+        """The bf16 operand (engine.PackedWeight) of one launch, repacked when a gate parameter's version moves."""
+        pw = self._pw[(phase, fresh)]
+        ver = tuple(engine.param_versions(c.weight, c.bias) for c in self._convs(phase))
+        if pw.key is None or pw.key[0] != ver:
+            with torch.no_grad():
+                w, b = self._weights(phase, fresh, torch.float32, True)
+            pw.get(w.contiguous(), b.contiguous(), ver=ver)
+        return pw
+
+    def _packed_f32(self, phase, fresh):
+        params = [p for c in self._convs(phase) for p in (c.weight, c.bias)]
+        return self._pw32[(phase, fresh)].get_composed(params, lambda: self._weights(phase, fresh, torch.float64, False))
+
+    def new_state(self, B, H, W, device):
+        """A fresh bf16 state: nothing is zero-filled, the first step convolves the x window alone and reads no h."""
+        C = self.hidden_size
+        f32 = lambda: torch.empty((B, H, W, C), dtype=torch.float32, device=device)
+        return {'block': 'convgru', 'hxr': engine.empty_cl(B, 3 * C, H, W, device), 'h32': f32(), 'u': f32(), 'fresh': True}
+
+    def new_state_f32(self, B, H, W, device):
+        C = self.hidden_size
+        return {'block': 'convgru', 'precision': 'fp32', 'hxr': torch.empty((B, H, W, 3 * C), dtype=torch.float32, device=device),
+                'fresh': True}
+
+    def x_window(self, state):
+        """The [B, C, H, W] view the encoder conv writes (either precision)."""
+        C = self.hidden_size
+        return engine.from_nhwc(state['hxr'][..., C:2 * C]) if state.get('precision') == 'fp32' else state['hxr'][:, C:2 * C]
+
+    def step(self, state, rh_f32=None):
+        """One bf16 step on a new_state state whose x window was just written: two launches (hip.convgru_gates,
+        hip.convgru_out).  3 x 3 gates, input_size == hidden_size, hidden_size % 32 == 0; anything else is refused by the entry
+        points (there is no unfused bf16 form).  rh_f32: optional fp32 [B, H, W, C] receiving r*h before its rounding (tests).
+        Returns the bf16 hidden state view [B, C, H, W]."""
+        g = self.out_gate
+        C, fresh = self.hidden_size, state['fresh']
+        if self.input_size != C:
+            raise ValueError("the bf16 ConvGRU kernels need input_size == hidden_size")
+        k, pad = g.kernel_size[0], g.padding[0]
+        buf = engine.nhwc(state['hxr'])
+        pa, pb = self._packed('gates', fresh), self._packed('out', fresh)
+        win_a = buf[..., C:2 * C] if fresh else buf[..., :2 * C]
+        win_b = buf[..., C:2 * C] if fresh else buf[..., C:]
+        hip.convgru_gates(win_a, pa.packed, pa.bias, state['h32'], state['u'], buf[..., 2 * C:], k, pad, h_is_zero=fresh, rh_f32=rh_f32)
+        hip.convgru_out(win_b, pb.packed, pb.bias, state['u'], state['h32'], buf[..., :C], k, pad, h_is_zero=fresh)
+        state['fresh'] = False
+        return state['hxr'][:, :C]
+
+    def step_f32(self, state):
+        """One fp32 step (K28) on a new_state_f32 state whose x window was just written: hip.convgru_step_f32, four launches.
+        Returns the hidden state view [B, C, H, W]."""
+        g = self.out_gate
+        fresh = state['fresh']
+        pa, pb = self._packed_f32('gates', fresh), self._packed_f32('out', fresh)
+        h = hip.convgru_step_f32(state['hxr'], pa.packed, pa.bias, pb.packed, pb.bias, self.hidden_size, g.kernel_size[0], g.padding[0],
+                                 h_is_zero=fresh)
+        state['fresh'] = False
+        return h
+
+
+def state_block_type(state):
+    """'convgru' for a ConvGRU state (either precision), 'convlstm' for any other state, None for None."""
+    if state is None:
+        return None
+    return 'convgru' if isinstance(state, dict) and state.get('block') == 'convgru' else 'convlstm'
+
+
 class RecurrentConvLayer(nn.Module):
-    """e2vid/model/submodules.py:96-115."""
+    """e2vid/model/submodules.py:96-115.  recurrent_block_type 'convlstm' or 'convgru'; a state belongs to one block type and one
+    precision (unet.check_states)."""
 
     def __init__(self, in_channels, out_channels, kernel_size=3, stride=1, padding=0,
                  recurrent_block_type='convlstm', activation='relu', norm=None):
         super().__init__()
-        assert recurrent_block_type == 'convlstm', "only ConvLSTM is used by E2VID_lightweight"
+        assert recurrent_block_type in ('convlstm', 'convgru')
         self.recurrent_block_type = recurrent_block_type
         self.conv = ConvLayer(in_channels, out_channels, kernel_size, stride, padding, activation, norm)
-        self.recurrent_block = ConvLSTM(input_size=out_channels, hidden_size=out_channels, kernel_size=3)
+        RecurrentBlock = ConvLSTM if recurrent_block_type == 'convlstm' else ConvGRU
+        self.recurrent_block = RecurrentBlock(input_size=out_channels, hidden_size=out_channels, kernel_size=3)
 
     def _state_shape(self, x):
         """(B, Ho, Wo, Co) of the encoder conv's output for the input x."""
@@ -279,6 +386,8 @@ class RecurrentConvLayer(nn.Module):
 
     def new_state(self, x):
         B, Ho, Wo, Co = self._state_shape(x)
+        if self.recurrent_block_type == 'convgru':
+            return self.recurrent_block.new_state(B, Ho, Wo, x.device)
         # fused ConvLSTM path: the first step convolves the x half only (zero state) and every later read of a cat(x, h) buffer
         # follows the encoder conv's write of its x half and the previous step's write of its h half -> no zero fill needed
         # (6 fills of up to 157 MB per pre-training step); the conv + gate-kernel path reads h_prev = 0 from the buffer itself
@@ -307,6 +416,9 @@ class RecurrentConvLayer(nn.Module):
 
     def run_conv(self, x, prev_state):
         state = prev_state if prev_state is not None else self.new_state(x)
+        if self.recurrent_block_type == 'convgru':
+            self.conv(x, out=self.recurrent_block.x_window(state))  # x -> the x window of the h | x | r*h buffer
+            return state
         Co = self.conv.conv2d.out_channels
         self.conv(x, out=state['xh'][state['cur']][:, :Co])         # x -> first half of the current cat(x, h) buffer
         return state
@@ -315,6 +427,8 @@ class RecurrentConvLayer(nn.Module):
         """State of the fp32 path: one cat(x, h) buffer fp32 [B, Ho, Wo, 2 C] (x half written by the encoder conv, h half by the
         ConvLSTM step), the cell fp32 [B, Ho, Wo, C], 'fresh' = no previous state; 'precision' tells it from a bf16 state."""
         B, Ho, Wo, Co = self._state_shape(x)
+        if self.recurrent_block_type == 'convgru':
+            return self.recurrent_block.new_state_f32(B, Ho, Wo, x.device)
         return {'precision': 'fp32', 'xh': torch.empty((B, Ho, Wo, 2 * Co), dtype=torch.float32, device=x.device),
                 'cell': torch.empty((B, Ho, Wo, Co), dtype=torch.float32, device=x.device), 'fresh': True}
 
@@ -322,6 +436,9 @@ class RecurrentConvLayer(nn.Module):
         """fp32 inference (K14): encoder conv into the x half of the state's cat(x, h) buffer, then the ConvLSTM step.
         Returns (h view [B, C, Ho, Wo], state)."""
         state = prev_state if prev_state is not None else self.new_state_f32(x)
+        if self.recurrent_block_type == 'convgru':
+            self.conv.forward_f32(x, out=self.recurrent_block.x_window(state))
+            return self.recurrent_block.step_f32(state), state
         Co = self.conv.conv2d.out_channels
         self.conv.forward_f32(x, out=engine.from_nhwc(state['xh'][..., :Co]))
         return self.recurrent_block.step_f32(state), state

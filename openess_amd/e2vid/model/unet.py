@@ -8,7 +8,8 @@ import torch
 import torch.nn as nn
 
 from ... import engine, hip
-from .submodules import ConvLayer, RecurrentConvLayer, ResidualBlock, TransposedConvLayer, UpsampleConvLayer, check_runs
+from .submodules import (ConvLayer, RecurrentConvLayer, ResidualBlock, TransposedConvLayer, UpsampleConvLayer, check_runs,
+                         state_block_type)
 
 
 class _SkewStates(list):
@@ -31,13 +32,18 @@ def state_precision(state):
     return 'fp32' if isinstance(state, dict) and state.get('precision') == 'fp32' else 'bf16'
 
 
-def check_states(prev_states, precision):
-    """ValueError when a state of the other precision is passed to a step of `precision`."""
+def check_states(prev_states, precision, block_type=None):
+    """ValueError when a state of the other precision is passed to a step of `precision`, or (block_type given) a state of the
+    other recurrent block type to a model of `block_type`."""
     for i, st in enumerate(prev_states if prev_states is not None else []):
         got = state_precision(st)
         if got is not None and got != precision:
             raise ValueError(f"E2VID state of level {i} is {got}, this step runs in {precision}: states do not carry over between "
                              "precisions (start a new sequence)")
+        blk = state_block_type(st)
+        if block_type is not None and blk is not None and blk != block_type:
+            raise ValueError(f"E2VID state of level {i} is a {blk} state, this model's recurrent blocks are {block_type}: states do "
+                             "not carry over between block types (start a new sequence)")
 
 
 def _latents(head, blocks):
@@ -54,6 +60,7 @@ class UNetRecurrent(nn.Module):
         super().__init__()
         self.num_input_channels = num_input_channels
         self.num_output_channels = num_output_channels
+        self.recurrent_block_type = recurrent_block_type
         self.skip_type = skip_type
         self.norm = norm
         self.num_encoders = num_encoders
@@ -113,6 +120,8 @@ class UNetRecurrent(nn.Module):
         """True when `forward(None, ..., need_head=False, raw=(events, c0, cs, normalize))` may replace EventPreprocessor + NHWC8
         re-layout + head + encoder-0 conv by one kernel."""
         if not (events.is_cuda and events.dtype == torch.float32 and events.is_contiguous() and events.ndim == 4 and 0 < cs <= 5):
+            return False
+        if self.recurrent_block_type != 'convlstm':      # the fused head writes the x half of a ConvLSTM cat(x, h) buffer
             return False
         probe = torch.empty((1, 8, 1, 1), dtype=torch.bfloat16, device=events.device)
         return self._head_enc0_fusable(probe)
@@ -198,8 +207,27 @@ class UNetRecurrent(nn.Module):
         `need_head=False` (the caller discards this call's latents: every sub-window but the last of a pre-training step,
         pretrain_trainer.py:437-441): latent[1] is None and head + encoder-0 conv run as ONE kernel.
         `skew=True`: the skewed single-stream schedule of _forward_skew (calls with need_head=False return no usable latents and
-        leave the deeper levels one / two sub-windows behind; the need_head=True call that ends the sequence drains them)."""
-        check_states(prev_states, 'bf16')
+        leave the deeper levels one / two sub-windows behind; the need_head=True call that ends the sequence drains them).
+        ConvGRU models (K28) run the plain order whatever is asked: skew, wavefront and the fused head + encoder-0 kernel are
+        ConvLSTM schedules; with raw= the slice is normalised and packed by its own kernel.  Same values, no level left behind.
+        With wavefront= every launch goes to the CURRENT stream, ordered after the wavefront's level-0 stream, where such a caller
+        prepared x (ImageReconstructor does not use the level streams for such a model at all).
+        Lifetime of the bf16 latents: latent[2], [4], ... are views of the states' buffers.  A ConvLSTM state ping-pongs two
+        cat(x, h) buffers, so its latents survive the next call and are overwritten by the one after; a ConvGRU state has ONE
+        h window, so its latents are overwritten by the very next call with these states: clone what has to outlive it."""
+        check_states(prev_states, 'bf16', self.recurrent_block_type)
+        if self.recurrent_block_type != 'convlstm':
+            if wavefront is not None and x is not None:
+                # a caller that prepared x on the wavefront's level-0 stream (its place in the ConvLSTM schedule): everything
+                # below runs on the current stream, which therefore waits for that stream and keeps x's block from being reused
+                main = torch.cuda.current_stream(x.device)
+                main.wait_stream(wavefront.streams[0])
+                x.record_stream(main)
+            skew, wavefront = False, None
+            if raw is not None:
+                x = hip.event_slice_to_nhwc8(raw[0], raw[1], raw[2], normalize=raw[3])
+                raw = None
+            need_head = True                # (nothing fuses the head away: its output exists either way)
         if skew and not reconstruct and wavefront is None:
             return self._forward_skew(x, prev_states, need_head, raw)
         if isinstance(prev_states, _SkewStates):
@@ -256,7 +284,7 @@ class UNetRecurrent(nn.Module):
         reconstruct=False (a training step, which reads the latents alone): returns after the encoders, img is None; the head and
         the encoders run the same launches on the same operands, so states and latents are the same bits."""
         self.check_fp32()
-        check_states(prev_states, 'fp32')
+        check_states(prev_states, 'fp32', self.recurrent_block_type)
         if x.dtype != torch.float32 or x.ndim != 4 or x.shape[1] != self.num_input_channels:
             raise ValueError(f"forward_fp32 needs an fp32 [B, {self.num_input_channels}, H, W] tensor")
         if prev_states is None:

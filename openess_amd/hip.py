@@ -756,6 +756,51 @@ def convlstm_fused(xh, packed_gates, bias, cell, hidden_out, k, pad, prev_cell_i
     return hidden_out
 
 
+def _convgru_f32_state(t, shape, what):
+    if t is not None and (t.dtype != torch.float32 or not t.is_contiguous() or tuple(t.shape) != shape):
+        raise ValueError(f"{what} must be a contiguous fp32 [B, H, W, C] = {shape} tensor")
+
+
+def convgru_gates(win, packed_gates, bias, h_master, u, rh_out, k=3, pad=1, h_is_zero=False, rh_f32=None):
+    """ConvGRU gates launch (oess_convgru_gates_bf16, K28): u = sigmoid(conv(win, Wu) + bu) -> `u` (fp32 [B, H, W, C]) and
+    bf16(sigmoid(conv(win, Wr) + br) * h) -> `rh_out` (NHWC bf16 [B, H, W, C] view, e.g. a channel window of the buffer `win`
+    belongs to, but none it convolves).  win: NHWC bf16 view, the (h | x) window or x alone (then h_is_zero).  h_master: the fp32
+    [B, H, W, C] hidden state (not read when h_is_zero).  packed_gates: pack_conv_weight of the [2C, Cin, k, k] weight with rows
+    2 hc + (0: update, 1: reset), bias [bu | br].  rh_f32: optional fp32 [B, H, W, C] receiving r * h before its rounding."""
+    lib = _lib.load()
+    _need_gpu(win, packed_gates, bias, h_master, u, rh_out, rh_f32)
+    B, H, W, Cin, ps = _nhwc_geom(win)
+    _, _, _, C, rs = _nhwc_geom(rh_out)
+    for t, what in ((u, "u"), (rh_f32, "rh_f32"), (None if h_is_zero else h_master, "h_master")):
+        _convgru_f32_state(t, (B, H, W, C), "convgru_gates: " + what)
+    if bias is not None and (bias.dtype != torch.float32 or not bias.is_contiguous() or bias.numel() != 2 * C):
+        raise ValueError("convgru_gates: bias must be contiguous fp32 [2C]")
+    _lib.check(lib.oess_convgru_gates_bf16(_ptr(win), ps, B, H, W, Cin, _ptr(packed_gates), _ptr(bias), C, k, k, pad,
+                                           None if h_is_zero else _ptr(h_master), _ptr(u), _ptr(rh_out), rs, _ptr(rh_f32), _stream()),
+               "oess_convgru_gates_bf16")
+    return u
+
+
+def convgru_out(win, packed, bias, u, h_master, h_bf16_out, k=3, pad=1, h_is_zero=False):
+    """ConvGRU output launch (oess_convgru_out_bf16, K28): h' = h (1 - u) + tanh(conv(win, Wo) + bo) u, in place in `h_master`
+    (fp32 [B, H, W, C]; only written when h_is_zero) and rounded to bf16 into `h_bf16_out` (NHWC bf16 view no part of `win`).
+    win: NHWC bf16 view, the (x | r h) window or x alone (then h_is_zero); u from convgru_gates."""
+    lib = _lib.load()
+    _need_gpu(win, packed, bias, u, h_master, h_bf16_out)
+    B, H, W, Cin, ps = _nhwc_geom(win)
+    _, _, _, C, hs = _nhwc_geom(h_bf16_out)
+    for t, what in ((u, "u"), (h_master, "h_master")):
+        if t is None:
+            raise ValueError(f"convgru_out: {what} is required")
+        _convgru_f32_state(t, (B, H, W, C), "convgru_out: " + what)
+    if bias is not None and (bias.dtype != torch.float32 or not bias.is_contiguous() or bias.numel() != C):
+        raise ValueError("convgru_out: bias must be contiguous fp32 [C]")
+    _lib.check(lib.oess_convgru_out_bf16(_ptr(win), ps, B, H, W, Cin, _ptr(packed), _ptr(bias), C, k, k, pad, _ptr(u),
+                                         None if h_is_zero else _ptr(h_master), _ptr(h_master), _ptr(h_bf16_out), hs, _stream()),
+               "oess_convgru_out_bf16")
+    return h_bf16_out
+
+
 def convlstm_w128_cell_elems(pixels, C):
     """Number of fp32 elements of a w128-tiled cell state for `pixels` = B*H*W pixels and C hidden channels (0: C % 64 != 0)."""
     return int(_lib.load().oess_convlstm_w128_cell_bytes(int(pixels), int(C))) // 4
@@ -2460,6 +2505,70 @@ def convlstm_step_f32(xh, packed, bias, C, k, pad, cell, hidden_out, prev_cell_i
     _bump(cell)
     _bump(hidden_out)
     return hidden_out
+
+
+def convgru_gates_f32(pre, h_prev, u, rh_out):
+    """fp32 ConvGRU gates (oess_convgru_gates_f32, K28): pre = contiguous fp32 [B, H, W, 2C] pre-activations (update | reset);
+    u = sigmoid(update) -> `u` (contiguous fp32 [B, H, W, C]); sigmoid(reset) * h_prev -> `rh_out`.  h_prev, rh_out: [B, C, H, W]
+    fp32 views (h_prev None: zero state)."""
+    lib = _lib.load()
+    _need_gpu(pre, h_prev, u, rh_out)
+    B, C, H, W = rh_out.shape
+    _convgru_f32_state(pre, (B, H, W, 2 * C), "convgru_gates_f32: pre")
+    _convgru_f32_state(u, (B, H, W, C), "convgru_gates_f32: u")
+    if h_prev is not None and tuple(h_prev.shape) != (B, C, H, W):
+        raise ValueError(f"convgru_gates_f32: h_prev shape {tuple(h_prev.shape)} != {(B, C, H, W)}")
+    vh = None if h_prev is None else _f32_view(h_prev, "h_prev")
+    vr = _f32_view(rh_out, "rh_out")
+    _lib.check(lib.oess_convgru_gates_f32(_ptr(pre), _f32_ref(vh), B, H, W, C, _ptr(u), ctypes.byref(vr), _stream()),
+               "oess_convgru_gates_f32")
+    _bump(u)
+    _bump(rh_out)
+    return u
+
+
+def convgru_blend_f32(pre, u, h_prev, h_out):
+    """fp32 ConvGRU blend (oess_convgru_blend_f32, K28): h_out = h_prev (1 - u) + tanh(pre) u.  pre, u: contiguous fp32
+    [B, H, W, C]; h_prev (None: zero state), h_out: [B, C, H, W] fp32 views; h_out may be h_prev."""
+    lib = _lib.load()
+    _need_gpu(pre, u, h_prev, h_out)
+    B, C, H, W = h_out.shape
+    _convgru_f32_state(pre, (B, H, W, C), "convgru_blend_f32: pre")
+    _convgru_f32_state(u, (B, H, W, C), "convgru_blend_f32: u")
+    if h_prev is not None and tuple(h_prev.shape) != (B, C, H, W):
+        raise ValueError(f"convgru_blend_f32: h_prev shape {tuple(h_prev.shape)} != {(B, C, H, W)}")
+    vh = None if h_prev is None else _f32_view(h_prev, "h_prev")
+    vo = _f32_view(h_out, "h_out")
+    _lib.check(lib.oess_convgru_blend_f32(_ptr(pre), _ptr(u), _f32_ref(vh), B, H, W, C, ctypes.byref(vo), _stream()),
+               "oess_convgru_blend_f32")
+    _bump(h_out)
+    return h_out
+
+
+def convgru_step_f32(hxr, gates_packed, gates_bias, out_packed, out_bias, C, k, pad, h_is_zero=False):
+    """One fp32 ConvGRU step (K28) on the state buffer hxr = fp32 [B, H, W, 3C] ordered h | x | r h, whose x window was just
+    written: conv2d_f32 of the (h | x) window -> gates -> conv2d_f32 of the (x | r h) window -> blend into the h window: four
+    launches.  gates_packed: pack_conv_weight_f32 of the [2C, 2C, k, k] weight (rows update | reset, input channels h | x),
+    out_packed of the out gate's weight in its own (x | r h) order; h_is_zero: both are the x-half operands ([.., C, k, k]) and
+    only the x window is convolved.  Returns the h window as a [B, C, H, W] view."""
+    lib = _lib.load()
+    _need_gpu(hxr)
+    if hxr.dtype != torch.float32 or hxr.ndim != 4 or not hxr.is_contiguous() or hxr.shape[3] != 3 * C:
+        raise ValueError("convgru_step_f32: the state buffer is contiguous fp32 [B, H, W, 3C]")
+    B, H, W, _ = hxr.shape
+    P = B * H * W
+    need = lib.oess_convgru_f32_workspace_bytes(P, C)
+    ws = _f32_workspace(need, "convgru_step_f32", (B, H, W, C), hxr.device, "convgru_f32").view(torch.float32)
+    pre = ws[:2 * P * C].view(B, H, W, 2 * C)
+    u = ws[2 * P * C:3 * P * C].view(B, H, W, C)
+    pre_o = ws[3 * P * C:4 * P * C].view(B, H, W, C)
+    win = lambda c0, c1: hxr[..., c0:c1].permute(0, 3, 1, 2)
+    h = win(0, C)
+    conv2d_f32(win(C, 2 * C) if h_is_zero else win(0, 2 * C), gates_packed, gates_bias, 2 * C, k, k, 1, pad, out=pre.permute(0, 3, 1, 2))
+    convgru_gates_f32(pre, None if h_is_zero else h, u, win(2 * C, 3 * C))
+    conv2d_f32(win(C, 2 * C) if h_is_zero else win(C, 3 * C), out_packed, out_bias, C, k, k, 1, pad, out=pre_o.permute(0, 3, 1, 2))
+    convgru_blend_f32(pre_o, u, None if h_is_zero else h, h)
+    return h
 
 
 # ------------------------------------------------------------------------------------------ K15: fp32 SemSegE2VID inference
