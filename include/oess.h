@@ -1114,6 +1114,45 @@ int oess_gray_augment_rgb_f32(const uint8_t* u8, int B, int H, int W, const int3
                               const float* contrast_host, const uint64_t* noise_seed_host, float* out, void* scratch,
                               size_t scratch_bytes, oess_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------
+ * K29 CLIP text tower in fp32 (OpenAI CLIP's text encoder: width 512, 8 heads of 64, 12 pre-LN blocks, context 77, causal
+ * mask, QuickGELU, ln_final, the end-of-text row times text_projection): class names -> the [K, 512] text embeddings every
+ * classifier here multiplies with.  Inference only.  Additions only: the ABI version stays.  No atomic: every result repeats
+ * bit for bit.
+ *
+ * oess_attention_d64_causal_f32: oess_attention_d64_f32 (same arguments, same checks, same kernel body) where query i of a
+ *   sequence sees keys 0 .. i of that sequence.  A workgroup (128 queries) stops after the last 64-key tile one of its queries
+ *   sees; a score with key > query is -inf like one with key >= L.  Row 0 of a sequence is its V row.
+ * oess_clip_text_embed_f32: out[n L + t, :] = table[ids[n, t], :] + pos[t, :], ids int64 [N, L] dense, table fp32 [V, C], pos fp32
+ *   [>= L, C], out [N L, C]; row strides in floats.  One fp32 add per element.  16-byte accesses when C % 4 == 0, the three
+ *   strides % 4 == 0 and table, pos, out are 16-byte aligned.  The ids live on the device: the caller checks 0 <= id < V
+ *   (an id outside gives a row of NaN and reads nothing outside the table).  OESS_EINVAL: a null pointer, N, L, V or C < 1,
+ *   C > 2^20, a stride below C or >= 2^31, N L >= 2^31, ids off 8 bytes, another pointer off 4, more than 2^31 - 1 workgroups.
+ * oess_linear_tokens_quick_gelu_f32: oess_linear_tokens_f32 with the epilogue v / (1 + expf(-1.702 v)) (QuickGELU
+ *   v sigmoid(1.702 v), accurate expf) after bias and residual; no `act` argument; otherwise its arguments and refusals.
+ * oess_clip_text_eot_layernorm_f32: per sequence n, t* = the FIRST largest of ids[n, 0 .. L) (torch.argmax), y[n, :] =
+ *   oess_layernorm_f32 of row n L + t* of x [N L, C].  One wave per sequence; the same two routes chosen by the same rule
+ *   (C, both strides, the four pointers), so the result equals oess_layernorm_f32 on the gathered rows bit for bit when the
+ *   route is the same.  OESS_EINVAL: what oess_layernorm_f32 refuses, a null ids or one off 8 bytes, N or L < 1, N L >= 2^31.
+ * oess_prompt_mean_normalize_f32: e fp32 [N, D], 1 <= D <= 2048; class k owns the prompts host_offsets[k] .. host_offsets[k + 1] - 1
+ *   (int64 [K + 1], ascending, first 0, last N, no empty class; dev_offsets is the same array in device memory, host_offsets is
+ *   read during the call).  out[k] = s / |s|, s = sum over the class's prompts IN THEIR ORDER of e[n] / |e[n]|, | | = sqrtf of
+ *   the sum of squares, true divisions.  The mean's 1 / count cancels and is not applied.  A zero row gives NaN.  One wave per
+ *   class.  OESS_EINVAL: a null pointer, N, D or K < 1, N >= 2^31, D > 2048, a stride below D or >= 2^31, e or out off 4 bytes,
+ *   an offsets array off 8, offsets that do not start at 0, end at N and ascend strictly.
+ * ------------------------------------------------------------------------------------------ */
+int oess_attention_d64_causal_f32(const float* qkv, long long qkv_row_stride, int B, int L, int heads, float scale, float* out,
+                                  long long out_row_stride, oess_stream_t stream);
+int oess_clip_text_embed_f32(const int64_t* ids, int N, int L, const float* table, long long table_row_stride, int V, int C,
+                             const float* pos, long long pos_row_stride, float* out, long long out_row_stride, oess_stream_t stream);
+int oess_linear_tokens_quick_gelu_f32(const float* x, long long x_row_stride, int64_t rows, int Cin, const float* w_packed,
+                                      const float* bias, int Cout, const float* residual, long long res_row_stride, float* out,
+                                      long long out_row_stride, oess_stream_t stream);
+int oess_clip_text_eot_layernorm_f32(const float* x, long long x_row_stride, const int64_t* ids, int N, int L, int C, const float* gamma,
+                                     const float* beta, float eps, float* y, long long y_row_stride, oess_stream_t stream);
+int oess_prompt_mean_normalize_f32(const float* e, long long e_row_stride, int64_t N, int D, const int64_t* host_offsets,
+                                   const int64_t* dev_offsets, int K, float* out, long long out_row_stride, oess_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -215,6 +215,11 @@ SIGNATURES = {
     "oess_attention_d64_f32": (c_int, [c_vp, c_ll, c_int, c_int, c_int, c_f, c_vp, c_ll, c_vp]),
     "oess_layernorm_f32": (c_int, [c_vp, c_ll, c_i64, c_int, c_vp, c_vp, c_f, c_vp, c_ll, c_vp]),
     "oess_linear_tokens_f32": (c_int, [c_vp, c_ll, c_i64, c_int, c_vp, c_vp, c_int, c_int, c_vp, c_ll, c_vp, c_ll, c_vp]),
+    "oess_attention_d64_causal_f32": (c_int, [c_vp, c_ll, c_int, c_int, c_int, c_f, c_vp, c_ll, c_vp]),
+    "oess_clip_text_embed_f32": (c_int, [c_vp, c_int, c_int, c_vp, c_ll, c_int, c_int, c_vp, c_ll, c_vp, c_ll, c_vp]),
+    "oess_linear_tokens_quick_gelu_f32": (c_int, [c_vp, c_ll, c_i64, c_int, c_vp, c_vp, c_int, c_vp, c_ll, c_vp, c_ll, c_vp]),
+    "oess_clip_text_eot_layernorm_f32": (c_int, [c_vp, c_ll, c_vp, c_int, c_int, c_int, c_vp, c_vp, c_f, c_vp, c_ll, c_vp]),
+    "oess_prompt_mean_normalize_f32": (c_int, [c_vp, c_ll, c_i64, c_int, c_vp, c_vp, c_int, c_vp, c_ll, c_vp]),
     "oess_maskclip_refine_workspace_bytes": (c_sz, [c_int, c_int, c_int, c_int, c_int]),
     "oess_maskclip_refine_f32": (c_int, [c_vp, c_ll, c_ll, c_ll, c_ll, c_int, c_int, c_int, c_int, c_vp, c_int, c_ll, c_ll, c_int, c_f,
                                          c_f, c_vp, c_ll, c_ll, c_ll, c_ll, c_vp, c_sz, c_vp]),

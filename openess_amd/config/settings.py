@@ -214,6 +214,27 @@ class Settings:
             v = getattr(self, key)
             if isinstance(v, bool) or not isinstance(v, (int, float)) or not 0 <= v < float('inf'):
                 raise ValueError(f"clip.{key} must be a finite number >= 0, got {v!r}")
+        # `text_classes`: the class names the run classifies into, a list whose entries are a name or a list of
+        # synonyms pooled into one class.  The trainers compute the [K, 512] text embeddings from them on the GPU (CLIP's text
+        # tower from `clip_text_checkpoint`, tokenised with the merges file `clip_bpe_path`, prompts from `text_templates`:
+        # 'single' = 'a photo of a {}.', 'none' = the bare name, or a file with one template per line) and point
+        # text_embeddings_path at the result.  Types are checked here; what the trainers refuse is in
+        # training/base_trainer_ov.py:text_classes_options.
+        self.text_classes = c.get('text_classes')
+        if self.text_classes is not None:
+            ok = isinstance(self.text_classes, list) and len(self.text_classes) > 0 and all(
+                (isinstance(e, str) and e.strip()) or
+                (isinstance(e, list) and len(e) > 0 and all(isinstance(n, str) and n.strip() for n in e)) for e in self.text_classes)
+            if not ok:
+                raise ValueError(f"clip.text_classes must be a non-empty list of names or lists of synonyms, got {self.text_classes!r}")
+        for key in ('clip_text_checkpoint', 'clip_bpe_path'):
+            v = c.get(key)
+            if v is not None and not isinstance(v, str):
+                raise ValueError(f"clip.{key} must be a path, got {v!r}")
+            setattr(self, key, v)
+        self.text_templates = c.get('text_templates', 'single')
+        if not isinstance(self.text_templates, str) or not self.text_templates:
+            raise ValueError(f"clip.text_templates must be 'single', 'none' or a path, got {self.text_templates!r}")
         # `recon_sources: 'online_e2vid'`: frame2recon's reconstructed image is computed from the sample's raw
         # events in the trainer's prepare_batch (voxelizer -> frozen E2VID -> PostProcessor -> hip.recon_augment) instead of read
         # from `reconstructions/left/*.png`; None = the PNG tree.  `online_recon_precision` is the E2VID arithmetic there,

@@ -30,6 +30,7 @@ constexpr int BK = 16;
 constexpr int MAXTAP = 49;             // tap table: up to the 7 x 7 stem of ResNet (oess_conv2d_dilated_fwd_f32)
 constexpr int MAXTAP_V1 = 25;          // what oess_conv2d_fwd_f32 / oess_convlstm_step_f32 take
 constexpr int ACT_GELU = 3;            // internal epilogue code, reached through oess_linear_tokens_f32 only
+constexpr int ACT_QUICK_GELU = 4;      // internal epilogue code, reached through oess_linear_tokens_quick_gelu_f32 only (K29)
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
@@ -51,7 +52,7 @@ struct Params {
     const float* w;
     int CoutP;
     const float* bias;
-    int Cout, act;                   // act: 0 none, 1 ReLU, 2 sigmoid; ACT_GELU: the GELU instances (launch)
+    int Cout, act;                   // act: 0 none, 1 ReLU, 2 sigmoid; ACT_GELU, ACT_QUICK_GELU: instances of their own (launch)
     View res;
     int has_res;
     float* out;
@@ -113,8 +114,9 @@ __device__ __forceinline__ float4 fetch4(const Params& P, int b, int y, int x, i
 
 // VEC: Cin % 16 == 0 and dense, 16-byte aligned channels in both inputs -> a K step lies inside one tap, float4 loads
 // GELU (K25): the token GEMM's exact-GELU epilogue (oess_linear_tokens_f32, act 1) is an instance of its own, so the instances
-// the convolutions run are unchanged by it
-template <int BN, bool VEC, bool GELU = false>
+// the convolutions run are unchanged by it.  EPI: 0 the runtime act, 1 that GELU, 2 QuickGELU v sigmoid(1.702 v) with the accurate
+// expf (K29: the FFN of CLIP's text tower, oess_linear_tokens_quick_gelu_f32)
+template <int BN, bool VEC, int EPI = 0>
 __global__ __launch_bounds__(NT) void conv_f32_kernel(const Params P) {
     constexpr int WN = BN / 32, WM = 4 / WN, BM = WM * 64;
     constexpr int LDA = BM + 32, LDB = BN + 32;          // +32 floats: the two k rows of one MFMA operand read hit disjoint banks
@@ -277,7 +279,8 @@ __global__ __launch_bounds__(NT) void conv_f32_kernel(const Params P) {
             if (oy >= P.oh || ox >= P.ow) continue;
             float v = (s ? acc1[r] : acc0[r]) + bias;
             if (P.has_res) v = v + P.res.p[b * P.res.sb + oy * P.res.sy + ox * P.res.sx + n * P.res.sc];
-            if (GELU) v = 0.5f * v * (1.0f + erff(v * 0.70710678f));
+            if (EPI == 1) v = 0.5f * v * (1.0f + erff(v * 0.70710678f));
+            else if (EPI == 2) v = v / (1.0f + expf(-1.702f * v));
             else if (P.act == 1) v = v > 0.f ? v : 0.f;
             else if (P.act == 2) v = 1.0f / (1.0f + expf(-v));
             P.out[b * P.ob + oy * P.oy + ox * P.ox + n * P.oc] = v;
@@ -325,11 +328,19 @@ int launch(Params& P, int nphase, hipStream_t stream) {
     dim3 grid((unsigned)((M + BM - 1) / BM), (unsigned)(P.CoutP / (bn64 ? 64 : 32)), (unsigned)nphase);
     if (P.act == ACT_GELU) {
         if (bn64) {
-            if (vec) hipLaunchKernelGGL((conv_f32_kernel<64, true, true>), grid, dim3(NT), 0, stream, P);
-            else hipLaunchKernelGGL((conv_f32_kernel<64, false, true>), grid, dim3(NT), 0, stream, P);
+            if (vec) hipLaunchKernelGGL((conv_f32_kernel<64, true, 1>), grid, dim3(NT), 0, stream, P);
+            else hipLaunchKernelGGL((conv_f32_kernel<64, false, 1>), grid, dim3(NT), 0, stream, P);
         } else {
-            if (vec) hipLaunchKernelGGL((conv_f32_kernel<32, true, true>), grid, dim3(NT), 0, stream, P);
-            else hipLaunchKernelGGL((conv_f32_kernel<32, false, true>), grid, dim3(NT), 0, stream, P);
+            if (vec) hipLaunchKernelGGL((conv_f32_kernel<32, true, 1>), grid, dim3(NT), 0, stream, P);
+            else hipLaunchKernelGGL((conv_f32_kernel<32, false, 1>), grid, dim3(NT), 0, stream, P);
+        }
+    } else if (P.act == ACT_QUICK_GELU) {
+        if (bn64) {
+            if (vec) hipLaunchKernelGGL((conv_f32_kernel<64, true, 2>), grid, dim3(NT), 0, stream, P);
+            else hipLaunchKernelGGL((conv_f32_kernel<64, false, 2>), grid, dim3(NT), 0, stream, P);
+        } else {
+            if (vec) hipLaunchKernelGGL((conv_f32_kernel<32, true, 2>), grid, dim3(NT), 0, stream, P);
+            else hipLaunchKernelGGL((conv_f32_kernel<32, false, 2>), grid, dim3(NT), 0, stream, P);
         }
     } else if (bn64) {
         if (vec) hipLaunchKernelGGL((conv_f32_kernel<64, true>), grid, dim3(NT), 0, stream, P);
@@ -441,12 +452,11 @@ int oess_conv_transpose2d_fwd_f32(const oess_f32_view_t* in, const oess_f32_view
 }
 
 // K25: a token GEMM as the 1 x 1 convolution of a [1, C, 1, rows] map (the Params oess_conv2d_fwd_f32 builds at R = S = 1)
-int oess_linear_tokens_f32(const float* x, long long x_row_stride, int64_t rows, int Cin, const float* w_packed, const float* bias,
-                           int Cout, int act, const float* residual, long long res_row_stride, float* out, long long out_row_stride,
-                           oess_stream_t stream) {
+static int linear_tokens(const float* x, long long x_row_stride, int64_t rows, int Cin, const float* w_packed, const float* bias,
+                         int Cout, int act, const float* residual, long long res_row_stride, float* out, long long out_row_stride,
+                         oess_stream_t stream) {
     if (!x || !out || !weights_ok(w_packed, bias) || (residual && ((uintptr_t)residual & 3) != 0)) return OESS_EINVAL;
-    if (rows < 1 || rows >= (1LL << 31) || Cin < 1 || Cin > (1 << 20) || Cout < 1 || Cout > (1 << 20) || (act != 0 && act != 1))
-        return OESS_EINVAL;
+    if (rows < 1 || rows >= (1LL << 31) || Cin < 1 || Cin > (1 << 20) || Cout < 1 || Cout > (1 << 20)) return OESS_EINVAL;
     if (x_row_stride < Cin || out_row_stride < Cout || (residual && res_row_stride < Cout)) return OESS_EINVAL;
     if (x_row_stride >= (1LL << 31) || out_row_stride >= (1LL << 31) || (residual && res_row_stride >= (1LL << 31)))
         return OESS_EINVAL;                                       // rows x stride stays inside the 64-bit index arithmetic
@@ -460,7 +470,7 @@ int oess_linear_tokens_f32(const float* x, long long x_row_stride, int64_t rows,
     P.stride = 1; P.off_y = 0; P.off_x = 0; P.ostride = 1;
     P.oh = 1; P.ow = (int)rows;
     P.skip = 0;
-    P.w = w_packed; P.CoutP = ceil_to(Cout, 32); P.bias = bias; P.Cout = Cout; P.act = act ? ACT_GELU : 0;
+    P.w = w_packed; P.CoutP = ceil_to(Cout, 32); P.bias = bias; P.Cout = Cout; P.act = act;
     P.has_res = residual != nullptr;
     P.res = View{residual, 0, 0, res_row_stride, 1};
     P.out = out;
@@ -469,6 +479,22 @@ int oess_linear_tokens_f32(const float* x, long long x_row_stride, int64_t rows,
     ph.ntap = 1; ph.py = 0; ph.px = 0; ph.w_off = 0; ph.kp = ceil_to(Cin, BK);
     ph.dy[0] = 0; ph.dx[0] = 0;
     return launch(P, 1, (hipStream_t)stream);
+}
+
+int oess_linear_tokens_f32(const float* x, long long x_row_stride, int64_t rows, int Cin, const float* w_packed, const float* bias,
+                           int Cout, int act, const float* residual, long long res_row_stride, float* out, long long out_row_stride,
+                           oess_stream_t stream) {
+    if (act != 0 && act != 1) return OESS_EINVAL;
+    return linear_tokens(x, x_row_stride, rows, Cin, w_packed, bias, Cout, act ? ACT_GELU : 0, residual, res_row_stride, out,
+                         out_row_stride, stream);
+}
+
+// K29: the same GEMM with QuickGELU as its epilogue (an entry of its own: act 2 of oess_linear_tokens_f32 stays refused)
+int oess_linear_tokens_quick_gelu_f32(const float* x, long long x_row_stride, int64_t rows, int Cin, const float* w_packed,
+                                      const float* bias, int Cout, const float* residual, long long res_row_stride, float* out,
+                                      long long out_row_stride, oess_stream_t stream) {
+    return linear_tokens(x, x_row_stride, rows, Cin, w_packed, bias, Cout, ACT_QUICK_GELU, residual, res_row_stride, out, out_row_stride,
+                         stream);
 }
 
 size_t oess_conv2d_dgrad_s2_f32_packed_floats(int Cout, int Cin, int R) {

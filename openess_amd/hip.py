@@ -1104,12 +1104,15 @@ def layer_norm_tokens_f32(x, gamma, beta, eps=1e-6, out=None):
     return out
 
 
-def attention_d64_f32(qkv, B, L, heads, out=None):
+def attention_d64_f32(qkv, B, L, heads, out=None, causal=False):
     """softmax(Q K^T / 8) V per head (head dim 64) from the packed in_proj output [B*L, 3*heads*64] in fp32 -> [B*L, heads*64]
-    fp32 on the f32-input MFMA (oess_attention_d64_f32): fp32 products, fp32 softmax, no rounding in between."""
+    fp32 on the f32-input MFMA (oess_attention_d64_f32): fp32 products, fp32 softmax, no rounding in between.  causal (K29):
+    query i of a sequence sees keys 0 .. i of it (oess_attention_d64_causal_f32, the text tower's mask)."""
     lib = _lib.load()
     if not all(isinstance(v, int) and v >= 1 for v in (B, L, heads)):
         raise ValueError("attention_d64_f32: B, L and heads must be positive integers")
+    if not isinstance(causal, bool):
+        raise ValueError("attention_d64_f32: causal must be a bool")
     C = heads * 64
     _check_tokens_f32("attention_d64_f32", "qkv", qkv, (B * L, 3 * C))
     if _token_stride(qkv) % 4 or qkv.data_ptr() % 16:
@@ -1121,18 +1124,19 @@ def attention_d64_f32(qkv, B, L, heads, out=None):
     _need_gpu(qkv)
     if out is None:
         out = torch.empty((B * L, C), dtype=torch.float32, device=qkv.device)
-    _lib.check(lib.oess_attention_d64_f32(_ptr(qkv), _token_stride(qkv), B, L, heads, 0.125, _ptr(out), _token_stride(out), _stream()),
-               "oess_attention_d64_f32")
+    name = "oess_attention_d64_causal_f32" if causal else "oess_attention_d64_f32"
+    _lib.check(getattr(lib, name)(_ptr(qkv), _token_stride(qkv), B, L, heads, 0.125, _ptr(out), _token_stride(out), _stream()), name)
     return out
 
 
-_F32_TOKEN_ACT = {None: 0, 'gelu': 1}
+_F32_TOKEN_ACT = {None: 0, 'gelu': 1, 'quick_gelu': None}       # quick_gelu (K29) is an entry of its own, not an `act` code
 
 
 def linear_tokens_f32(x, packed, bias, Cout, act=None, residual=None, out=None):
     """y = act(x W^T + b [+ residual]) for fp32 tokens x [rows, Cin] on the fp32 conv kernel (oess_linear_tokens_f32).  packed:
     pack_conv_weight_f32(W[:, :, None, None]); act: None or 'gelu' (exact, nn.GELU's default); bias [Cout] and residual
-    [rows, Cout] optional; x, residual and out may be row-strided.  act None gives conv2d_f32(..., R=S=1)'s bits."""
+    [rows, Cout] optional; x, residual and out may be row-strided.  act None gives conv2d_f32(..., R=S=1)'s bits.
+    act 'quick_gelu': v sigmoid(1.702 v), CLIP's activation (oess_linear_tokens_quick_gelu_f32)."""
     lib = _lib.load()
     _check_tokens_f32("linear_tokens_f32", "x", x)
     rows, Cin = x.shape
@@ -1153,9 +1157,108 @@ def linear_tokens_f32(x, packed, bias, Cout, act=None, residual=None, out=None):
     _need_gpu(x)
     if out is None:
         out = torch.empty((rows, Cout), dtype=torch.float32, device=x.device)
+    if act == 'quick_gelu':
+        _lib.check(lib.oess_linear_tokens_quick_gelu_f32(_ptr(x), _token_stride(x), rows, Cin, _ptr(packed), _ptr(bias), Cout,
+                                                         _ptr(residual), 0 if residual is None else _token_stride(residual),
+                                                         _ptr(out), _token_stride(out), _stream()), "oess_linear_tokens_quick_gelu_f32")
+        return out
     _lib.check(lib.oess_linear_tokens_f32(_ptr(x), _token_stride(x), rows, Cin, _ptr(packed), _ptr(bias), Cout, _F32_TOKEN_ACT[act],
                                           _ptr(residual), 0 if residual is None else _token_stride(residual), _ptr(out),
                                           _token_stride(out), _stream()), "oess_linear_tokens_f32")
+    return out
+
+
+# ---- K29: what CLIP's text tower needs next to the token kernels above
+def _check_ids(what, ids, like=None):
+    if not isinstance(ids, torch.Tensor) or ids.dtype != torch.int64 or ids.ndim != 2 or ids.shape[0] < 1 or ids.shape[1] < 1 \
+            or not ids.is_contiguous():
+        raise ValueError(f"{what}: ids must be contiguous int64 [N, L]")
+    if like is not None and ids.device != like.device:
+        raise ValueError(f"{what}: ids must be on {like.device}")
+
+
+def clip_text_embed(ids, token_embedding, positional_embedding, out=None):
+    """x[n L + t, :] = token_embedding[ids[n, t], :] + positional_embedding[t, :]: int64 ids [N, L], fp32 table [V, C] and positions
+    [>= L, C] -> fp32 [N L, C] (oess_clip_text_embed_f32; one add per element, exact).  An id outside [0, V) or more tokens than
+    positions is a ValueError before the launch (reading the ids back synchronises once)."""
+    lib = _lib.load()
+    what = "clip_text_embed"
+    _check_tokens_f32(what, "token_embedding", token_embedding)
+    V, C = token_embedding.shape
+    _check_ids(what, ids, token_embedding)
+    N, L = ids.shape
+    if not isinstance(positional_embedding, torch.Tensor) or positional_embedding.ndim != 2 or positional_embedding.shape[1] != C:
+        raise ValueError(f"{what}: positional_embedding must be fp32 [>= L, {C}]")
+    _check_tokens_f32(what, "positional_embedding", positional_embedding, like=token_embedding)
+    if L > positional_embedding.shape[0]:
+        raise ValueError(f"{what}: {L} tokens per text, positional_embedding has {positional_embedding.shape[0]} rows")
+    lo, hi = int(ids.min()), int(ids.max())
+    if lo < 0 or hi >= V:
+        raise ValueError(f"{what}: ids must lie in [0, {V}), got {lo} .. {hi}")
+    if out is not None:
+        _check_tokens_f32(what, "out", out, (N * L, C), token_embedding)
+    _need_gpu(token_embedding)
+    if out is None:
+        out = torch.empty((N * L, C), dtype=torch.float32, device=ids.device)
+    _lib.check(lib.oess_clip_text_embed_f32(_ptr(ids), N, L, _ptr(token_embedding), _token_stride(token_embedding), V, C,
+                                            _ptr(positional_embedding), _token_stride(positional_embedding), _ptr(out),
+                                            _token_stride(out), _stream()), "oess_clip_text_embed_f32")
+    return out
+
+
+def clip_text_eot_norm(x, ids, gamma, beta, eps=1e-5, out=None):
+    """LayerNorm of the end-of-text row of each text: x fp32 [N L, C] (C <= 2048), ids int64 [N, L]; row argmax_t ids[n, t] (the
+    first maximum, as torch.argmax) of text n, normalised like layer_norm_tokens_f32 -> fp32 [N, C]
+    (oess_clip_text_eot_layernorm_f32; the other N (L - 1) rows are not touched)."""
+    lib = _lib.load()
+    what = "clip_text_eot_norm"
+    _check_tokens_f32(what, "x", x)
+    _check_ids(what, ids, x)
+    N, L = ids.shape
+    C = x.shape[1]
+    if x.shape[0] != N * L:
+        raise ValueError(f"{what}: x must be fp32 [{N * L}, C] for ids {list(ids.shape)}")
+    if C > 2048:
+        raise ValueError(f"{what}: x has more than 2048 channels")
+    _check_affine(what, "gamma", gamma, C, x)
+    _check_affine(what, "beta", beta, C, x)
+    if not eps > 0:
+        raise ValueError(f"{what}: eps must be positive")
+    if out is not None:
+        _check_tokens_f32(what, "out", out, (N, C), x)
+    _need_gpu(x)
+    if out is None:
+        out = torch.empty((N, C), dtype=torch.float32, device=x.device)
+    _lib.check(lib.oess_clip_text_eot_layernorm_f32(_ptr(x), _token_stride(x), _ptr(ids), N, L, C, _ptr(gamma), _ptr(beta), float(eps),
+                                                    _ptr(out), _token_stride(out), _stream()), "oess_clip_text_eot_layernorm_f32")
+    return out
+
+
+def prompt_mean_normalize(e, group_offsets, out=None):
+    """out[k] = normalize(sum over the prompts n of class k of normalize(e[n])): e fp32 [N, D] (D <= 2048), group_offsets int64
+    [K + 1] (ascending from 0 to N, no empty class; CPU or GPU) -> fp32 [K, D] unit rows (oess_prompt_mean_normalize_f32; a class's
+    prompts are added in their order, so the result repeats bit for bit)."""
+    lib = _lib.load()
+    what = "prompt_mean_normalize"
+    _check_tokens_f32(what, "e", e)
+    N, D = e.shape
+    if D > 2048:
+        raise ValueError(f"{what}: e has more than 2048 channels")
+    if not isinstance(group_offsets, torch.Tensor) or group_offsets.dtype != torch.int64 or group_offsets.ndim != 1 \
+            or group_offsets.numel() < 2:
+        raise ValueError(f"{what}: group_offsets must be int64 [K + 1]")
+    host = group_offsets.cpu().contiguous()
+    K = host.numel() - 1
+    if int(host[0]) != 0 or int(host[-1]) != N or bool((host[1:] <= host[:-1]).any()):
+        raise ValueError(f"{what}: group_offsets must ascend strictly from 0 to {N}")
+    if out is not None:
+        _check_tokens_f32(what, "out", out, (K, D), e)
+    _need_gpu(e)
+    dev = group_offsets.contiguous() if group_offsets.device == e.device else host.to(e.device)
+    if out is None:
+        out = torch.empty((K, D), dtype=torch.float32, device=e.device)
+    _lib.check(lib.oess_prompt_mean_normalize_f32(_ptr(e), _token_stride(e), N, D, _ptr(host), _ptr(dev), K, _ptr(out),
+                                                  _token_stride(out), _stream()), "oess_prompt_mean_normalize_f32")
     return out
 
 

@@ -98,6 +98,50 @@ def online_recon_options(settings):
     return {'precision': precision, 'model': model}
 
 
+def text_classes_options(settings):
+    """`text_classes` (clip block): the text embeddings come from the class names, computed by CLIP's text tower
+    on the GPU.  None when the key is absent, else {'classes', 'checkpoint', 'bpe', 'templates'}.  Refused, each before anything
+    is built: the key without its two paths, together with a non-empty text_embeddings_path (two sources for one tensor), a
+    path that is no file (the templates' included), a class count other than semseg_num_classes."""
+    import os
+    classes = getattr(settings, 'text_classes', None)
+    if classes is None:
+        return None
+    ckpt, bpe = getattr(settings, 'clip_text_checkpoint', None), getattr(settings, 'clip_bpe_path', None)
+    if not ckpt or not bpe:
+        raise ValueError("text_classes needs clip_text_checkpoint (CLIP weights) and clip_bpe_path (the BPE merges file)")
+    if getattr(settings, 'text_embeddings_path', None):
+        raise ValueError(f"text_classes and text_embeddings_path ({settings.text_embeddings_path!r}) both name the text embeddings: "
+                         "give one of them")
+    templates = getattr(settings, 'text_templates', 'single')
+    for key, path in (('clip_text_checkpoint', ckpt), ('clip_bpe_path', bpe)) + \
+            ((('text_templates', templates),) if templates not in ('single', 'none') else ()):
+        if not os.path.isfile(path):
+            raise ValueError(f"{key}: {path!r} not found")
+    if len(classes) != settings.semseg_num_classes:
+        raise ValueError(f"text_classes names {len(classes)} classes, semseg_num_classes is {settings.semseg_num_classes}")
+    return {'classes': classes, 'checkpoint': ckpt, 'bpe': bpe, 'templates': templates}
+
+
+def write_text_embeddings(settings, options, device, rank=0):
+    """The embeddings of `options` (text_classes_options) -> a file every text_embeddings_path consumer loads; the setting then
+    names it, so every model receives them through the mechanism that exists.  The file lies in the run's log directory when
+    there is one, else it is a temporary file."""
+    import os
+    import tempfile
+    from ..models.clip_text import compute_text_embeddings
+    emb = compute_text_embeddings(options['checkpoint'], options['bpe'], options['classes'], options['templates'], device)
+    if getattr(settings, 'timestr', None) and os.path.isdir(os.path.dirname(settings.ckpt_dir)):
+        path = os.path.join(os.path.dirname(settings.ckpt_dir), 'text_embeddings.pt' if rank == 0 else f'text_embeddings.rank{rank}.pt')
+    else:
+        fd, path = tempfile.mkstemp(prefix='openess_text_embeddings_', suffix='.pt')
+        os.close(fd)
+    torch.save(emb, path)
+    settings.logger.info("text embeddings of %d classes from %s written to %s", emb.shape[0], options['checkpoint'], path)
+    settings.text_embeddings_path = path
+    return path
+
+
 def online_recon_image(rec, post, vox, n, C, aug):
     """The voxels [B, n C, H, W] of n sub-windows -> the augmented student image fp32 [B, 3, H, W]: the frozen
     E2VID behind the ImageReconstructor `rec` over the sub-windows from empty states, leaving empty states -- sub-windows
@@ -128,6 +172,7 @@ class BaseTrainer(object):
         self.online_slic_segments = online_slic_segments(settings, self.pooling_size())
         online_maskclip_refine(settings)         # `online_maskclip_refine: True` without its teacher is refused here too
         self.online_recon = online_recon_options(settings)      # and what `recon_sources: online_e2vid` cannot serve
+        text_classes = text_classes_options(settings)           # and `text_classes` without what it needs
         if not torch.cuda.is_available():
             raise RuntimeError("openess_amd trainers need the GPU (no CPU fallback in the product path)")
         self.device = torch.device('cuda', torch.cuda.current_device())
@@ -155,6 +200,10 @@ class BaseTrainer(object):
             print(msg)
         self.metrics_semseg_b = MetricsSemseg(settings.semseg_num_classes, settings.semseg_ignore_label,
                                               settings.semseg_class_names)
+        # `text_classes`: before any trainer's buildModels (every init_fn starts with it), the embeddings are
+        # computed and settings.text_embeddings_path names them; without the key nothing happens
+        if text_classes is not None:
+            write_text_embeddings(settings, text_classes, self.device, self.rank)
         self.init_fn()
         self.createDataLoaders()
         self.models_dict = {k: v.to(self.device) for k, v in self.models_dict.items()}
