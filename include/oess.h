@@ -499,6 +499,15 @@ int oess_zero_insert_nhwc_bf16(const void* in, long long in_pix_stride, int B, i
                                void* out, long long out_pix_stride, oess_stream_t stream);
 int oess_downsample_sum2x_nhwc_bf16(const void* gout, long long gout_pix_stride, int B, int H, int W, int C, void* gin,
                                     long long gin_pix_stride, oess_stream_t stream);
+/* The front half of the E2VID UpsampleConvLayer (e2vid/model/submodules.py:65-93) behind a skip sum, in one pass:
+ * out[b, oy, ox, c] = bf16( bilinear2x( f32(x) + f32(skip) ) ), bilinear2x = F.interpolate(scale_factor=2, mode='bilinear',
+ * align_corners=False): source coordinate max(0, (o + 0.5) / 2 - 0.5), taps floor and min(floor + 1, n - 1).  Sum and
+ * interpolation in fp32, ONE rounding (to nearest even) at the store.  x, skip: [B, H, W, C]; out: [B, 2H, 2W, C]; NHWC bf16,
+ * pixel strides in elements (channel slices of wider buffers are fine).  skip nullable (no sum).
+ * OESS_EINVAL, nothing launched: C % 8 != 0, a non-positive size, a pixel stride smaller than C or no multiple of 8, a null x or
+ * out, an out whose byte range overlaps an input's. */
+int oess_upsample_bilinear2x_sum_nhwc_bf16(const void* x, long long x_pix_stride, const void* skip, long long skip_pix_stride, int B,
+                                           int H, int W, int C, void* out, long long out_pix_stride, oess_stream_t stream);
 /* nn.Upsample(scale, bilinear, align_corners=True) + F.normalize(dim=1) in one pass (models/image_model.py:121-143).  inv_norm
  * (nullable, needs normalize != 0): [B * H*scale * W*scale] fp32, 1 / max(|x|, 1e-12) of every output pixel -- what
  * oess_l2norm_nhwc_bwd needs, so the differentiable head never materialises the un-normalised full-resolution tensor. */

@@ -116,6 +116,7 @@ SIGNATURES = {
                                             c_ll, c_vp, c_sz, c_vp]),
     "oess_upsample_nearest2x_nhwc_bf16": (c_int, [c_vp, c_ll, c_int, c_int, c_int, c_int, c_vp, c_ll, c_vp]),
     "oess_downsample_sum2x_nhwc_bf16": (c_int, [c_vp, c_ll, c_int, c_int, c_int, c_int, c_vp, c_ll, c_vp]),
+    "oess_upsample_bilinear2x_sum_nhwc_bf16": (c_int, [c_vp, c_ll, c_vp, c_ll, c_int, c_int, c_int, c_int, c_vp, c_ll, c_vp]),
     "oess_bilinear_l2norm_nhwc_bf16": (c_int, [c_vp, c_ll, c_int, c_int, c_int, c_int, c_int, c_int, c_vp, c_ll, c_vp, c_vp]),
     "oess_conv2d_wgrad_bf16": (c_int, [c_vp, c_ll, c_int, c_int, c_int, c_int, c_vp, c_ll, c_int, c_int, c_int, c_int,
                                        c_int, c_int, c_int, c_vp, c_vp, c_sz, c_vp]),

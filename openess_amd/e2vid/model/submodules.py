@@ -105,8 +105,22 @@ class TransposedConvLayer(_ConvNormAct):
 
 
 class UpsampleConvLayer(_ConvNormAct):
-    """e2vid/model/submodules.py:65-93: bilinear x2 (align_corners=False) -> conv -> BN -> relu.  The bf16 path only holds the
-    parameters; the fp32 path (forward_f32) runs it, the interpolation gathered inside the conv's operand load."""
+    """e2vid/model/submodules.py:65-93: bilinear x2 (align_corners=False) -> conv -> BN -> relu.  Only the offline
+    reconstruction path runs it (unet.py:165-166), in either precision.  bf16 (forward, K30): the skip sum and the interpolation
+    are one streaming kernel (oess_upsample_bilinear2x_sum_nhwc_bf16: fp32 inside, one rounding to bf16), the convolution is the
+    MFMA conv on the layer's regular packing with the eval-mode BatchNorm folded in and ReLU fused in the epilogue, as in
+    ConvLayer.  fp32 (forward_f32, K14): one launch, the interpolation gathered inside the conv's operand load."""
+
+    def forward(self, x, skip=None):
+        """relu(BN(conv(upsample2x(x [+ skip])))) on logical-NCHW channels_last bf16 tensors (channel slices of wider buffers are
+        fine); the sum is taken in fp32 inside the upsampling kernel, so the decoder input is rounded once."""
+        check_runs(self.norm, self.bn, self.activation_name)
+        c = self.conv2d
+        up = hip.upsample2x_sum_nhwc(engine.nhwc(x), None if skip is None else engine.nhwc(skip))
+        pw = self._pw.get(c.weight, c.bias, self.bn)
+        y = hip.conv2d_nhwc(up, pw.packed, pw.bias, c.out_channels, c.kernel_size[0], c.kernel_size[1], c.stride[0], c.padding[0], 1,
+                            relu=self.activation_name == 'relu')
+        return engine.from_nhwc(y)
 
     def forward_f32(self, x, skip=None):
         """fp32 inference (K14): act(BN(conv(upsample2x(x + skip)))) in one launch."""

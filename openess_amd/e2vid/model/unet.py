@@ -265,7 +265,11 @@ class UNetRecurrent(nn.Module):
             for resblock in self.resblocks:
                 x = resblock(x)
             for i, decoder in enumerate(self.decoders):
-                x = decoder(x + blocks[self.num_encoders - i - 1])           # apply_skip_connection = skip_sum
+                skip = blocks[self.num_encoders - i - 1]                     # apply_skip_connection = skip_sum
+                if isinstance(decoder, UpsampleConvLayer):
+                    x = decoder(x, skip=skip)                                # summed in fp32 inside the upsampling kernel (K30)
+                else:
+                    x = decoder(x + skip)
             logits = engine.conv2d_infer(x + head, self.pred._packed(x.shape[1]), 1, 1, 1, 0, 1, out_f32=True)     # 32 -> 1, fp32 output
             img = torch.sigmoid(logits.float())
         return img, states, _latents(head, blocks)

@@ -10,7 +10,9 @@ executes; `-o/--output_folder` + `--dataset_name` follow e2vid/options/inference
 :126-140) on each cropped frame and writes its bytes; its tuning flags (`--unsharp_mask_amount`, `--Imin`, `--auto_hdr`, ...) keep
 the reference's defaults and are refused without it.  Without `--postprocess` a frame is round(clamp(img, 0, 1) * 255).
 `--precision fp32` runs the network in fp32 as the reference does (f32-input MFMA kernels); the default `bf16`
-runs it on the training path's bf16-storage kernels.
+runs it on the training path's bf16-storage kernels.  Both precisions run every recurrent checkpoint with `norm` None or `BN` and
+`skip_type: sum`: ConvLSTM or ConvGRU blocks (K28), transposed-convolution decoders (`use_upsample_conv: False`) or the
+reference's default bilinear upsample + convolution decoders (K30: the skip sum and the x2 interpolation are one HIP kernel).
 
 Checkpoint format: the reference's (`{'arch': 'E2VIDRecurrent', 'model' | 'config.model': {...}, 'state_dict': ...}`,
 e2vid/utils/loading_utils.py:5-16); `-c random` builds E2VID_lightweight with seeded random weights (no checkpoint

@@ -1577,6 +1577,31 @@ def zero_insert(x_nhwc, stride, Hz, Wz):
     return out
 
 
+def upsample2x_sum_nhwc(x_nhwc, skip_nhwc=None, out=None):
+    """bf16(bilinear2x(f32(x) + f32(skip))) on NHWC bf16 views, bilinear2x = F.interpolate(scale_factor=2, mode='bilinear',
+    align_corners=False): the skip sum and the upsampling of an E2VID UpsampleConvLayer in one pass, fp32 inside, rounded once
+    (K30).  skip_nhwc None: no sum.  out: optional [B, 2H, 2W, C] bf16 NHWC view (a channel slice of a wider buffer is fine) that
+    shares no memory with an input.  Returns [B, 2H, 2W, C] bf16."""
+    lib = _lib.load()
+    _need_gpu(x_nhwc, skip_nhwc, out)
+    B, H, W, C, ps = _nhwc_geom(x_nhwc)
+    if C % 8:
+        raise ValueError(f"upsample2x_sum_nhwc needs a channel count that is a multiple of 8, got {C}")
+    sps = 0
+    if skip_nhwc is not None:
+        if tuple(skip_nhwc.shape) != (B, H, W, C):
+            raise ValueError(f"skip has shape {tuple(skip_nhwc.shape)}, x has {(B, H, W, C)}")
+        sps = _nhwc_geom(skip_nhwc)[4]
+    if out is None:
+        out = torch.empty((B, 2 * H, 2 * W, C), dtype=torch.bfloat16, device=x_nhwc.device)
+    elif out.dtype != torch.bfloat16 or tuple(out.shape) != (B, 2 * H, 2 * W, C):
+        raise ValueError(f"out must be bf16 {(B, 2 * H, 2 * W, C)}, got {out.dtype} {tuple(out.shape)}")
+    ops = _nhwc_geom(out)[4]
+    _lib.check(lib.oess_upsample_bilinear2x_sum_nhwc_bf16(_ptr(x_nhwc), ps, _ptr(skip_nhwc), sps, B, H, W, C, _ptr(out), ops, _stream()),
+               "oess_upsample_bilinear2x_sum_nhwc_bf16")
+    return out
+
+
 def bilinear_l2norm(x, scale=4, normalize=True):
     """nn.Upsample(scale, bilinear, align_corners=True) + F.normalize(dim=1), inference form (no autograd)."""
     lib = _lib.load()
