@@ -535,6 +535,22 @@ int oess_l2norm_nhwc_bwd(const void* y, long long y_pix_stride, const void* grad
                          int64_t P, int C, int is_bf16, float eps, void* grad_x, long long gx_pix_stride, oess_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Class labels from logits without the full-resolution tensor (K31): out[b, y, x] = argmax_k up(logits)[b, k, y, x], the
+ * labels of F.interpolate(logits, size=(H, W), mode='bilinear', align_corners).argmax(1) (the online MaskCLIP teacher) and of
+ * logits.argmax(dim=1) (if_switchable_train, training/pretrain_trainer.py:513-514, :556-557).
+ *   logits: NHWC [B x h x w x K] fp32 or bf16 (is_bf16 != 0), pixel stride in elements (a channel slice of a wider buffer is fine);
+ *   out: int64 [B x H x W], dense.  1 <= K <= 256.
+ *   (H, W) == (h, w): no interpolation, the K raw values are compared.  Otherwise every class value is the fp32 blend of
+ *   oess_resize_bilinear_nhwc_fwd's general kernel -- same index rule, bf16 taps widened first, same association, no FMA --, so the
+ *   labels equal those of the composed path bit for bit.
+ *   Argmax rule = torch.argmax: the first index among equal maxima; a NaN is larger than everything; the first NaN wins.
+ * OESS_EINVAL, nothing launched, out untouched: a null pointer, K outside 1 ... 256, a non-positive size, pix_stride < K, B * H or
+ * B * h above 2^31 - 1, or an element count of logits / out that overflows 64-bit byte offsets.  No geometry is refused for size:
+ * source rows that do not fit the kernel's LDS budget are read from global memory. */
+int oess_argmax_labels(const void* logits, int is_bf16, long long pix_stride, int B, int K, int h, int w, int H, int W,
+                       int align_corners, int64_t* out, oess_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * MaskCLIP ViT-B/16 image tower (models/maskclip_model.py:448-541 TransformerEncoderLayer, :545-851 VisionTransformer):
  * the non-GEMM pieces.  The linear layers (patch embedding, in_proj, out_proj, FFN, proj) run on oess_conv2d_fwd_bf16 as
  * 1x1 / 16x16 convolutions over the token axis (bias, residual and GELU fused in the epilogue).

@@ -1969,6 +1969,30 @@ def bilinear_resize(x, size=None, scale_factor=None, align_corners=False):
     return _BilinearResize.apply(x, int(size[0]), int(size[1]), bool(align_corners))
 
 
+def argmax_labels(logits, size=None, align_corners=False, out=None):
+    """Class labels of logical B x K x h x w fp32 / bf16 logits: int64 [B, H, W], the integers of
+    bilinear_resize(logits.float(), size, align_corners).argmax(1) without the full-resolution tensor.  size=None
+    (or the input size) interpolates nothing: logits.argmax(1) on the raw values.  torch.argmax's tie / NaN rule.  No autograd."""
+    if not torch.is_tensor(logits) or not logits.is_cuda:
+        raise ValueError("argmax_labels needs a CUDA/HIP tensor (no CPU fallback)")
+    if logits.dtype not in (torch.float32, torch.bfloat16) or logits.ndim != 4:
+        raise ValueError("argmax_labels expects 4-D float32 / bfloat16 logits [B, K, h, w]")
+    B, K, h, w = logits.shape
+    if not 1 <= K <= 256:
+        raise ValueError(f"argmax_labels handles 1 <= K <= 256 classes, got {K}")
+    H, W = (h, w) if size is None else (int(size[0]), int(size[1]))
+    if out is None:
+        out = torch.empty((B, H, W), dtype=torch.int64, device=logits.device)
+    elif (not torch.is_tensor(out) or tuple(out.shape) != (B, H, W) or out.dtype != torch.int64 or out.device != logits.device
+          or not out.is_contiguous()):
+        raise ValueError(f"out must be a contiguous int64 tensor of shape {(B, H, W)} on {logits.device}")
+    xn = _nhwc_any(logits.detach())
+    _lib.check(_lib.load().oess_argmax_labels(_ptr(xn), int(logits.dtype == torch.bfloat16), _pix_stride(xn), B, K, h, w, H, W,
+                                              int(bool(align_corners)), _ptr(out), _stream()), "oess_argmax_labels")
+    _bump(out)
+    return out
+
+
 class _L2Normalize(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, eps):

@@ -336,3 +336,22 @@ class maskClipFeatureExtractor(nn.Module):
         _, logits = self.decoder.forward_fp32(v_map)
         refined = self.decoder.refine_output(logits, k)
         return hip.bilinear_resize(refined, size=(img.shape[2], img.shape[3]), align_corners=self.align_corners)
+
+    @torch.no_grad()
+    def labels(self, img, refine=False, precision='bf16'):
+        """int64 [B, H, W] pseudo-labels: the integers of forward(img, refine).argmax(1) (precision='fp32': of forward_fp32),
+        from the stride-level fp32 logits (or the refined output) on hip.argmax_labels -- the [B, K, H, W] tensor that only the
+        argmax read is never written."""
+        if precision not in ('bf16', 'fp32'):
+            raise ValueError(f"precision must be 'bf16' or 'fp32', got {precision!r}")
+        fp32 = precision == 'fp32'
+        enc = self.encoder.forward_fp32 if fp32 else self.encoder
+        dec = self.decoder.forward_fp32 if fp32 else self.decoder
+        x = img.float() if fp32 else img
+        if not refine:
+            _, low = dec(enc(x))
+        else:
+            v_map, k = enc(x, return_k=True)
+            _, logits = dec(v_map)
+            low = self.decoder.refine_output(logits.float(), k)
+        return hip.argmax_labels(low.float(), size=(img.shape[2], img.shape[3]), align_corners=self.align_corners)

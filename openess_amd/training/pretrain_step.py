@@ -4,6 +4,7 @@ training/pretrain_trainer.py: buildModels (:107-208), createOptimizerDict (:211-
 smoke() and the trainer classes; it owns the models_dict / optimizers_dict with the reference's key names.
 """
 import contextlib
+import functools
 import math
 from types import SimpleNamespace
 
@@ -27,6 +28,24 @@ class _Front:
         self.content = self.teacher_enc = self.teacher_out = self.online_pl = self.streams = self.done = None
 
 
+def _label_options(init):
+    """PretrainStep's keyword-only options of K31, taken off the call before the positional constructor runs -- its
+    parameter list is pinned (tests/test_pretrain_precision.py), and these have no place in it:
+      online_labels=None      callable frame -> int64 [B, H, W] (maskClipFeatureExtractor.labels: hip.argmax_labels on the
+                              stride-level logits); when given, front() calls it in place of online_teacher(frame).argmax(dim=1)
+      switchable_train=False  if_switchable_train (pretrain_trainer.py:513-514, :556-557): while epoch_count >= switch_epoch the
+      switch_epoch=5          dense-CLIP pseudo-labels are the argmax of the student's own logits; batch[3] and the online teacher
+                              (either form) are then unused.  epoch_count starts at 0; the trainer sets it every step."""
+    @functools.wraps(init)
+    def with_options(self, *args, online_labels=None, switchable_train=False, switch_epoch=5, **kwargs):
+        self.online_labels = online_labels
+        self.switchable_train = bool(switchable_train)
+        self.switch_epoch = int(switch_epoch)
+        self.epoch_count = 0
+        init(self, *args, **kwargs)
+    return with_options
+
+
 class PretrainStep:
     # frame2voxel + contrastive: the student's 256-channel map is only pooled over superpixels, and the mean commutes with its 1x1
     # convolution (hip.PointwiseFeature); False = materialise the map as the reference does (A/B, tests)
@@ -48,10 +67,12 @@ class PretrainStep:
     # reference does (pretrain_trainer.py:434); False stops after the encoder, whose BatchNorm updates are the call's only effect.
     run_unused_teacher_head = True
 
+    @_label_options
     def __init__(self, config_option='frame2voxel', num_classes=11, img_size=(440, 640), nr_events_data=20,
                  nr_temporal_bins=5, if_spatial_contrastive=False, if_dense_clip_supervision=True, superpixel_size=100,
                  lr=5e-4, weight_task_loss=1.0, task_loss=('dice', 'cross_entropy'), output_stride=32, device='cuda',
                  e2vid_config=None, text_embeddings=None, seed=1205, online_teacher=None, wavefront=False, precision='bf16'):
+        # keyword-only on top of these (see _label_options): online_labels=None, switchable_train=False, switch_epoch=5
         # precision: arithmetic of the whole step.  'bf16' (default) builds and runs exactly the bf16 step.  'fp32'
         # is the reference's arithmetic (use_amp: False in every YAML); what it cannot run is refused here, before any model is built
         if precision not in ('bf16', 'fp32'):
@@ -60,7 +81,7 @@ class PretrainStep:
             if config_option != 'frame2voxel':
                 raise NotImplementedError(f"precision='fp32' pre-trains frame2voxel, not {config_option!r}: DeepLabv3 has no fp32 "
                                           "backward (train-mode BatchNorm, strided and dilated convolutions)")
-            if online_teacher is not None:
+            if online_teacher is not None or self.online_labels is not None:
                 raise NotImplementedError("precision='fp32' has no online teacher: the MaskCLIP ViT has no fp32 form")
             if wavefront:
                 raise NotImplementedError("precision='fp32' has no wavefront schedule: fp32 E2VID runs on one stream "
@@ -143,6 +164,11 @@ class PretrainStep:
             if name == 'front_sensor_b':
                 m.eval()                       # unfrozen_e2vid: False in every pre-training YAML
 
+    @property
+    def switched(self):
+        """True once the pseudo-labels come from the student's own logits (switchable_train and epoch_count >= switch_epoch)."""
+        return self.switchable_train and self.epoch_count >= self.switch_epoch
+
     def front(self, batch):
         """Frozen half of the step for `batch` (see the class comment): teacher encoder (+ its head when nothing trains it) and,
         for frame2voxel, the 20 recurrent E2VID encoder steps.  Everything is enqueued, nothing is waited for; the handle goes to
@@ -161,9 +187,13 @@ class PretrainStep:
             F.wait_stream(main)                  # the batch's tensors and everything queued so far (NOT what the caller enqueues later)
             T.wait_stream(main)
         ctx = (lambda st: torch.cuda.stream(st)) if cuda else (lambda st: contextlib.nullcontext())
-        if self.online_teacher is not None:
-            with ctx(T if cuda else None), torch.no_grad():
-                h.online_pl = self.online_teacher(frame).argmax(dim=1)
+        if not self.switched:
+            if self.online_labels is not None:
+                with ctx(T if cuda else None), torch.no_grad():
+                    h.online_pl = self.online_labels(frame)
+            elif self.online_teacher is not None:
+                with ctx(T if cuda else None), torch.no_grad():
+                    h.online_pl = self.online_teacher(frame).argmax(dim=1)
         with ctx(T if cuda else None):
             # the teacher head is trained by the contrastive loss: then it belongs to the back half; otherwise nothing can reach it
             # and the whole forward runs here without autograd bookkeeping (the reference runs it too, pretrain_trainer.py:434,484)
@@ -267,6 +297,8 @@ class PretrainStep:
         if self.config_option == 'frame2voxel':
             pl = batch[3]
             pred, feat_voxel = self.task_backend.forward_fp32_train(h.content) if self.precision == 'fp32' else self.task_backend(h.content)
+            if self.switched:
+                pl = hip.argmax_labels(pred[1].detach())
             loss_dense = self.task_loss(pred[1], pl) * self.weight_task_loss
             losses['dense_clip_loss'] = loss_dense.detach()
             if self.if_spatial_contrastive:
@@ -287,6 +319,8 @@ class PretrainStep:
                 losses['contrastive_nce_loss'] = loss_nce.detach()
                 t_loss = t_loss + loss_nce
             if self.if_dense_clip_supervision:
+                if self.switched:
+                    pl = hip.argmax_labels(logits_recon.detach())
                 loss_dense = self.task_loss(logits_recon, pl) * self.weight_task_loss
                 losses['dense_clip_loss'] = loss_dense.detach()
                 t_loss = t_loss + loss_dense

@@ -44,7 +44,7 @@ class OpenESSPretrainModel(BaseTrainer):
                 text = torch.load(s.text_embeddings_path, map_location='cpu')
             except (FileNotFoundError, OSError):
                 s.logger.info("text embeddings '%s' not found: random unit-norm embeddings", s.text_embeddings_path)
-        online = None
+        online = online_labels = None
         if getattr(s, 'pl_sources', '') == 'online_maskclip':          # extension: labels from the frozen tower, in the step
             from ..models.maskclip_model import maskClipFeatureExtractor
             kw = {k: getattr(s, k) for k in ('text_embeddings_path', 'visual_projs_path', 'maskclip_checkpoint') if getattr(s, k, None)}
@@ -57,11 +57,21 @@ class OpenESSPretrainModel(BaseTrainer):
             precision = getattr(s, 'online_teacher_precision', 'bf16')
             if precision not in ('bf16', 'fp32'):
                 raise ValueError(f"online_teacher_precision must be 'bf16' or 'fp32', got {precision!r}")
+            # the step asks the tower for labels, not logits: the same integers from the stride-level logits on
+            # hip.argmax_labels, without the [B, K, H, W] tensor; online_teacher stays the logits form of the same choices (a tower
+            # class with no `labels` gets its logits argmax-ed by the step, as before)
+            if hasattr(online, 'labels'):
+                online_labels = functools.partial(online.labels, refine=refine is not None, precision=precision)
             if precision == 'fp32':
                 online = online.forward_fp32
             if refine is not None:
                 online = functools.partial(online, refine=True)
-        self.step = PretrainStep(config_option=s.config_option, online_teacher=online, num_classes=s.semseg_num_classes, img_size=tuple(s.img_size_b),
+        # `if_switchable_train: True` (read next to if_finetuning, config/settings.py): from epoch 5 on the dense-CLIP pseudo-labels
+        # are the argmax of the student's own logits (pretrain_trainer.py:513-514, :556-557)
+        self._switch_logged = False
+        self.step = PretrainStep(config_option=s.config_option, online_teacher=online, online_labels=online_labels,
+                                 switchable_train=bool(getattr(s, 'if_switchable_train', False)),
+                                 num_classes=s.semseg_num_classes, img_size=tuple(s.img_size_b),
                                  nr_events_data=s.nr_events_data_b, nr_temporal_bins=s.nr_temporal_bins_b,
                                  if_spatial_contrastive=s.if_spatial_contrastive,
                                  if_dense_clip_supervision=s.if_dense_clip_supervision, superpixel_size=s.superpixel_size,
@@ -90,9 +100,19 @@ class OpenESSPretrainModel(BaseTrainer):
     def front_step(self, batch):
         """Frozen half of the step (teacher encoder, recurrent E2VID encoder) for `batch`, enqueued on its own HIP streams: trainEpoch
         calls it for batch i+1 before train_step(batch i, front=...) (PretrainStep.front / pipeline_steps)."""
+        self._sync_epoch()
         return self.step.front(batch)
 
+    def _sync_epoch(self):
+        """The step switches its pseudo-label source on the trainer's epoch counter (if_switchable_train)."""
+        self.step.epoch_count = self.epoch_count
+        if self.step.switched and not self._switch_logged:
+            self._switch_logged = True
+            self.settings.logger.info("if_switchable_train: epoch %d >= %d, pseudo-labels are now the argmax of the student's own "
+                                      "logits (batch labels and the online teacher are unused)", self.epoch_count, self.step.switch_epoch)
+
     def train_step(self, batch, front=None):
+        self._sync_epoch()
         for opt in self.optimizers_dict.values():
             opt.zero_grad()
         self.grad_reducer.prepare()          # N > 1: gradients accumulate straight into the all-reduce buckets
