@@ -450,6 +450,38 @@ int oess_event_slice_to_nhwc8_bf16(const float* in, int B, int Ctot, int c0, int
                                    int normalize, void* out_nhwc8, oess_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * K32 EventPreprocessor's hot-pixel removal and flip (e2vid/utils/inference_utils.py:71-75) inside the event kernels.
+ * Order as in the reference: events[:, :, y, x] = 0 for every listed pixel, then torch.flip(events, dims=[2, 3]), then the
+ * non-zero mean / std normalisation.  hot_mask: H x W bytes on the device, non-zero = hot, in SOURCE coordinates (null = no
+ * list); flip != 0 mirrors H and W.  The input tensor is only read (the reference zeroes the caller's tensor in place).
+ * Every *_pre entry point computes what its option-less namesake computes on torch.flip(zeroed copy, [2, 3]); `pre` must not
+ * be null.  Statistics: hot pixels add nothing to {sum, sumsq, nnz}; the flip does not change them (read in source order).
+ * ------------------------------------------------------------------------------------------ */
+typedef struct {
+    const unsigned char* hot_mask; /* [H][W], 1 = hot, may be null */
+    int flip;
+} oess_event_pre_t;
+int oess_masked_stats_slice_pre_f32(const float* in, int B, int Ctot, int c0, int Cs, int H, int W, const oess_event_pre_t* pre,
+                                    double* stats, oess_stream_t stream);
+int oess_masked_stats_slices_pre_f32(const float* in, int B, int Ctot, int Cs, int n_slices, int H, int W,
+                                     const oess_event_pre_t* pre, double* stats, oess_stream_t stream);
+/* Statistics + apply to dense fp32 NCHW: out[b, c, y, x] = norm(in'[b, c0 + c, H-1-y, W-1-x]) (flip) with in' = in with the hot
+ * pixels zeroed; normalize == 0 only zeroes and mirrors.  The whole tensor is the slice c0 = 0, Cs = Ctot.  out must not
+ * alias in.  stats as for oess_masked_normalize_slice_f32. */
+int oess_masked_normalize_slice_pre_f32(const float* in, float* out, int B, int Ctot, int c0, int Cs, int H, int W,
+                                        const oess_event_pre_t* pre, int normalize, double* stats, oess_stream_t stream);
+/* oess_event_slice_to_nhwc8_bf16 with the options (normalize == 0 still zeroes and mirrors). */
+int oess_event_slice_to_nhwc8_pre_bf16(const float* in, int B, int Ctot, int c0, int Cs, int H, int W, const oess_event_pre_t* pre,
+                                       const double* stats, int normalize, void* out_nhwc8, oess_stream_t stream);
+/* oess_e2vid_events_head_enc0_bf16 with the options: the per-patch loader reads the mirrored source pixel and the mask; the
+ * zero padding at the image border is unchanged. */
+int oess_e2vid_events_head_enc0_pre_bf16(const float* events, int B, int Ctot, int c0, int Cs, int H, int W,
+                                         const oess_event_pre_t* pre, const double* stats, int normalize,
+                                         const void* head_w_packed, const float* head_bias, int head_relu,
+                                         const void* enc_w_packed, const float* enc_bias, int enc_relu, void* out,
+                                         long long out_pix_stride, oess_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * Normalisation and resampling on NHWC bf16 (pixel strides in elements, C % 8 == 0).
  * Replace nn.BatchNorm2d (train-mode batch statistics; models/_resnet.py:74-114, image_model.py:130-143),
  * nn.InstanceNorm2d + ReLU (models/style_networks.py:252-289), F.interpolate(nearest, x2)

@@ -42,6 +42,14 @@ class F32View(ctypes.Structure):
 c_view = ctypes.POINTER(F32View)
 
 
+class EventPre(ctypes.Structure):
+    """oess_event_pre_t (include/oess.h): EventPreprocessor's hot-pixel mask ([H][W] bytes on the device, or null) and flip."""
+    _fields_ = [("hot_mask", c_vp), ("flip", c_int)]
+
+
+c_pre = ctypes.POINTER(EventPre)
+
+
 # name -> (restype, argtypes).  Must list EVERY symbol of include/oess.h (tests/test_abi.py checks).
 SIGNATURES = {
     "oess_abi_version": (c_int, []),
@@ -108,6 +116,12 @@ SIGNATURES = {
     "oess_masked_stats_slice_f32": (c_int, [c_vp, c_int, c_int, c_int, c_int, c_i64, c_vp, c_vp]),
     "oess_masked_stats_slices_f32": (c_int, [c_vp, c_int, c_int, c_int, c_int, c_i64, c_vp, c_vp]),
     "oess_event_slice_to_nhwc8_bf16": (c_int, [c_vp, c_int, c_int, c_int, c_int, c_ll, c_vp, c_int, c_vp, c_vp]),
+    "oess_masked_stats_slice_pre_f32": (c_int, [c_vp, c_int, c_int, c_int, c_int, c_int, c_int, c_pre, c_vp, c_vp]),
+    "oess_masked_stats_slices_pre_f32": (c_int, [c_vp, c_int, c_int, c_int, c_int, c_int, c_int, c_pre, c_vp, c_vp]),
+    "oess_masked_normalize_slice_pre_f32": (c_int, [c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, c_int, c_pre, c_int, c_vp, c_vp]),
+    "oess_event_slice_to_nhwc8_pre_bf16": (c_int, [c_vp, c_int, c_int, c_int, c_int, c_int, c_int, c_pre, c_vp, c_int, c_vp, c_vp]),
+    "oess_e2vid_events_head_enc0_pre_bf16": (c_int, [c_vp, c_int, c_int, c_int, c_int, c_int, c_int, c_pre, c_vp, c_int, c_vp, c_vp,
+                                                     c_int, c_vp, c_vp, c_int, c_vp, c_ll, c_vp]),
     "oess_norm_partials_bytes": (c_sz, [c_int, c_ll, c_int, c_int]),
     "oess_norm_stats_nhwc_bf16": (c_int, [c_vp, c_ll, c_int, c_ll, c_int, c_vp, c_vp, c_vp, c_sz, c_vp]),
     "oess_norm_stats_finalize_nhwc_bf16": (c_int, [c_vp, c_ll, c_int, c_ll, c_int, c_f, c_vp, c_vp, c_vp, c_vp, c_f, c_vp, c_vp,

@@ -46,14 +46,22 @@ struct S2Head {              // FUSED: the encoder's input is relu(conv5x5(x8, h
     int Ctot, c0, Cs, normalize;
     const double* stats;     // {sum, sumsq, nnz} of the slice
 };
+// K32: EventPreprocessor's hot-pixel mask and flip (inference_utils.py:71-75) in the ev loader of the fused kernel (PRE
+// instantiation only: the option-less kernels do not see this struct)
+struct S2Pre {
+    const unsigned char* mask;   // [H][W] bytes in source coordinates, non-zero = hot; may be null
+    int flip;                    // voxel pixel (iy, ix) reads source pixel (H - 1 - iy, W - 1 - ix)
+};
 constexpr int S2_IMG_PITCH = 72;                                     // bf16 output image [128 pixels][64 + 8]
 
 template <typename F, int... Is>
 __device__ __forceinline__ void s2_for_taps(F&& f, std::integer_sequence<int, Is...>) { (f(std::integral_constant<int, Is>{}), ...); }
 
 // one 8 x 16-pixel x 64-channel tile (`bid` = tile index after the XCD remap)
-template <bool FUSED>
-__device__ __forceinline__ void conv5x5s2_halo_tile(const ConvArgs& a, const S2Head& hd, const int bid, unsigned char* smem) {
+template <bool FUSED, bool PRE = false>
+__device__ __forceinline__ void conv5x5s2_halo_tile(const ConvArgs& a, const S2Head& hd, const int bid, unsigned char* smem,
+                                                    const S2Pre& pre = S2Pre{}) {
+    static_assert(FUSED || !PRE, "the event options live in the fused kernel's ev loader");
     constexpr int S2_RING = FUSED ? S2_RING_FUSED : S2_RING_PLAIN;
     const int tile_n = bid % a.tiles_n;
     int patch = bid / a.tiles_n;
@@ -189,8 +197,21 @@ __device__ __forceinline__ void conv5x5s2_halo_tile(const ConvArgs& a, const S2H
                 const int iy = 2 * oy0 - 4 + vy, ix = 2 * ox0 - 4 + vx;
                 okv[i] = v < S2_VH * S2_VW && (unsigned)iy < (unsigned)a.H && (unsigned)ix < (unsigned)a.W;
                 const float* src = hd.ev + ((long long)b * hd.Ctot + hd.c0) * hw_ + (long long)iy * a.W + ix;
+                bool hot = false;
+                if constexpr (PRE) {
+                    // the border test above is on the mirrored (output) coordinates: the zero padding stays where it was.  The
+                    // mask byte is loaded beside the events (no load waits for it); a hot pixel enters the normalisation below
+                    // as a zero, as in the reference's zeroed tensor
+                    const long long spix = pre.flip ? (long long)(a.H - 1 - iy) * a.W + (a.W - 1 - ix) : (long long)iy * a.W + ix;
+                    src = hd.ev + ((long long)b * hd.Ctot + hd.c0) * hw_ + spix;
+                    if (pre.mask) hot = pre.mask[okv[i] ? spix : 0] != 0;
+                }
 #pragma unroll
                 for (int c = 0; c < 5; ++c) raw[i][c] = (okv[i] && c < hd.Cs) ? src[c * hw_] : 0.0f;
+                if constexpr (PRE) {
+#pragma unroll
+                    for (int c = 0; c < 5; ++c) raw[i][c] = hot ? 0.0f : raw[i][c];
+                }
             }
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
@@ -390,6 +411,18 @@ __global__ __launch_bounds__(256, 2) void conv5x5s2_halo_kernel(ConvArgs a, S2He
         bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
     }
     conv5x5s2_halo_tile<FUSED>(a, hd, bid, smem);
+}
+
+// K32: the fused kernel with the event options (hd.ev != null)
+__global__ __launch_bounds__(256, 2) void conv5x5s2_halo_pre_kernel(ConvArgs a, S2Head hd, S2Pre pre) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    const int nwg = a.tiles_m * a.tiles_n;
+    int bid = blockIdx.x;
+    {
+        const int q = nwg >> 3, r = nwg & 7, xcd = bid & 7, idx = bid >> 3;
+        bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
+    }
+    conv5x5s2_halo_tile<true, true>(a, hd, bid, smem, pre);
 }
 
 // Two independent problems of the plain kernel in one launch (encoder convs of levels 1 and 2 on the skewed schedule of the

@@ -10,7 +10,8 @@
 //   conv_lstm_w128.h   conv3x3_lstm_w128_kernel: persistent w128 ConvLSTM gates
 //   conv_w128_gemm.h   conv1x1_w128_kernel: persistent w128 1x1 / GEMM
 //   conv3x3_w128.h     conv3x3_w128_kernel: persistent w128 3x3
-//   conv5x5s2_halo.h   conv5x5s2_halo_kernel, S2Head (fused E2VID head), S2Group and the grouped kernel
+//   conv5x5s2_halo.h   conv5x5s2_halo_kernel, S2Head (fused E2VID head), S2Group and the grouped kernel, S2Pre and
+//                      conv5x5s2_halo_pre_kernel (fused head with EventPreprocessor's hot-pixel mask and flip)
 //   conv_dma32.h       conv_fwd_dma32_kernel: 32-wide K slabs in a deeper ring
 //   conv_smallcin.h    conv_smallcin_kernel: Cin == 8
 //   conv_pack.h        pack_weight_kernel, pack_fwd_multi_kernel, pack_flip_multi_kernel
@@ -117,7 +118,8 @@ void conv_set_attrs() {
                              (const void*)&conv_fwd_dma_kernel<256, 256, 2, true>,
                              (const void*)&conv_fwd_dma_kernel<128, 128, 4, true, 0, 512>,
                              (const void*)&conv_fwd_dma32_kernel<128, true, 0, 3>, (const void*)&conv5x5s2_halo_kernel<false>,
-                             (const void*)&conv5x5s2_halo_kernel<true>, (const void*)&conv5x5s2_halo_group_kernel};
+                             (const void*)&conv5x5s2_halo_kernel<true>, (const void*)&conv5x5s2_halo_group_kernel,
+                             (const void*)&conv5x5s2_halo_pre_kernel};
         for (const void* f : fns) (void)hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
         if (dev >= 0 && dev < 64) set_on[dev] = true;
     }
@@ -832,7 +834,7 @@ int oess_conv5x5s2_group_bf16(const oess_conv_s2_desc_t* d, int n, oess_stream_t
 }
 
 static int e2vid_head_enc0_launch(const S2Head& hd, int B, int H, int W, const void* enc_w_packed, const float* enc_bias, int enc_relu,
-                                  void* out, long long out_pix_stride, oess_stream_t stream) {
+                                  void* out, long long out_pix_stride, oess_stream_t stream, const S2Pre* pre = nullptr) {
     conv_set_attrs();
     ConvArgs a;
     memset(&a, 0, sizeof(a));
@@ -843,7 +845,8 @@ static int e2vid_head_enc0_launch(const S2Head& hd, int B, int H, int W, const v
     a.M = B * a.Ho * a.Wo; a.relu = enc_relu;
     a.tiles_n = 1;
     a.tiles_m = s2_tiles_m(B, a.Ho, a.Wo);
-    hipLaunchKernelGGL((conv5x5s2_halo_kernel<true>), dim3(a.tiles_m), dim3(256), S2_LDS_FUSED, (hipStream_t)stream, a, hd);
+    if (pre) hipLaunchKernelGGL(conv5x5s2_halo_pre_kernel, dim3(a.tiles_m), dim3(256), S2_LDS_FUSED, (hipStream_t)stream, a, hd, *pre);
+    else hipLaunchKernelGGL((conv5x5s2_halo_kernel<true>), dim3(a.tiles_m), dim3(256), S2_LDS_FUSED, (hipStream_t)stream, a, hd);
     OESS_HIP(hipGetLastError());
     return OESS_OK;
 }
@@ -858,6 +861,20 @@ int oess_e2vid_events_head_enc0_bf16(const float* events, int B, int Ctot, int c
         return OESS_EINVAL;
     S2Head hd{nullptr, 8, (const uint16_t*)head_w_packed, head_bias, head_relu, events, Ctot, c0, Cs, normalize, stats};
     return e2vid_head_enc0_launch(hd, B, H, W, enc_w_packed, enc_bias, enc_relu, out, out_pix_stride, stream);
+}
+
+int oess_e2vid_events_head_enc0_pre_bf16(const float* events, int B, int Ctot, int c0, int Cs, int H, int W,
+                                         const oess_event_pre_t* pre, const double* stats, int normalize,
+                                         const void* head_w_packed, const float* head_bias, int head_relu,
+                                         const void* enc_w_packed, const float* enc_bias, int enc_relu, void* out,
+                                         long long out_pix_stride, oess_stream_t stream) {
+    if (!events || !pre || !head_w_packed || !enc_w_packed || !out || B <= 0 || H <= 0 || W <= 0 || Ctot <= 0 || c0 < 0 || Cs <= 0 ||
+        Cs > 5 || c0 + Cs > Ctot || (normalize && !stats) || (out_pix_stride & 7) || out_pix_stride < 64 || (((uintptr_t)out) & 15) ||
+        (unsigned)head_relu > 1u || (unsigned)enc_relu > 1u)
+        return OESS_EINVAL;
+    S2Head hd{nullptr, 8, (const uint16_t*)head_w_packed, head_bias, head_relu, events, Ctot, c0, Cs, normalize, stats};
+    const S2Pre sp{pre->hot_mask, pre->flip ? 1 : 0};
+    return e2vid_head_enc0_launch(hd, B, H, W, enc_w_packed, enc_bias, enc_relu, out, out_pix_stride, stream, &sp);
 }
 
 int oess_e2vid_head_enc0_bf16(const void* x8, long long x8_pix_stride, int B, int H, int W, const void* head_w_packed,

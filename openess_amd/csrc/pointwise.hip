@@ -84,6 +84,39 @@ __global__ __launch_bounds__(THREADS) void norm_to_nhwc8_kernel(const float* __r
     }
 }
 
+// K32: the same with EventPreprocessor's hot-pixel mask ([H][W] bytes, source coordinates, may be null) and flip
+// (inference_utils.py:71-75): output pixel r of sample blockIdx.y takes source pixel HW - 1 - r under the flip (mirroring H and W
+// of a contiguous plane reverses its linear index); a hot source pixel is zero in every channel before the normalisation.
+__global__ __launch_bounds__(THREADS) void norm_to_nhwc8_pre_kernel(const float* __restrict__ in, int Ctot, int c0, int Cs, int64_t HW,
+                                                                    const unsigned char* __restrict__ mask, int flip,
+                                                                    const double* __restrict__ stats, int normalize,
+                                                                    uint16_t* __restrict__ out) {
+    const double nnz = stats ? stats[2] : 0.0;
+    const bool active = normalize && nnz > 0.0;
+    float mean = 0.f, stdv = 1.f;
+    if (active) {
+        const float nf = (float)nnz;
+        mean = (float)stats[0] / nf;
+        stdv = sqrtf(__fsub_rn((float)stats[1] / nf, __fmul_rn(mean, mean)));
+    }
+    const int64_t b = blockIdx.y;
+    for (int64_t r = (int64_t)blockIdx.x * THREADS + threadIdx.x; r < HW; r += (int64_t)gridDim.x * THREADS) {
+        const int64_t sp = flip ? HW - 1 - r : r;
+        const bool hot = mask && mask[sp] != 0;
+        union { uint4 q; uint16_t h[8]; } o;
+        o.q = make_uint4(0u, 0u, 0u, 0u);
+#pragma unroll
+        for (int c = 0; c < 8; ++c) {
+            if (c < Cs) {
+                float a = hot ? 0.0f : in[(b * Ctot + c0 + c) * HW + sp];
+                if (active) a = __fmul_rn((a != 0.0f) ? 1.0f : 0.0f, __fsub_rn(a, mean)) / stdv;
+                o.h[c] = f32_to_bf16(a);
+            }
+        }
+        *reinterpret_cast<uint4*>(out + (b * HW + r) * 8) = o.q;
+    }
+}
+
 
 // ---------------------------------------------------------------------------------------------
 // Linear probe: nn.Conv2d(K, K, 1) on the fp32 logits (models/style_networks.py:169-170, models/deeplabv3.py:186-187), K <= 32.
@@ -229,6 +262,20 @@ int oess_event_slice_to_nhwc8_bf16(const float* in, int B, int Ctot, int c0, int
     return OESS_OK;
 }
 
+
+int oess_event_slice_to_nhwc8_pre_bf16(const float* in, int B, int Ctot, int c0, int Cs, int H, int W, const oess_event_pre_t* pre,
+                                       const double* stats, int normalize, void* out_nhwc8, oess_stream_t stream) {
+    if (!in || !out_nhwc8 || !pre || B <= 0 || B > 65535 || Ctot <= 0 || c0 < 0 || Cs <= 0 || Cs > 8 || c0 + Cs > Ctot || H <= 0 ||
+        W <= 0 || (normalize && !stats))
+        return OESS_EINVAL;
+    const int64_t HW = (int64_t)H * W;
+    int64_t gx = (HW + THREADS - 1) / THREADS;
+    if (gx > 4096) gx = 4096;
+    hipLaunchKernelGGL(norm_to_nhwc8_pre_kernel, dim3((unsigned)gx, (unsigned)B), dim3(THREADS), 0, (hipStream_t)stream, in, Ctot, c0,
+                       Cs, HW, pre->hot_mask, pre->flip, stats, normalize, (uint16_t*)out_nhwc8);
+    OESS_HIP(hipGetLastError());
+    return OESS_OK;
+}
 
 size_t oess_linear_probe_partials_bytes(int K) { return (K > 0 && K <= LP_KMAX) ? (size_t)LP_MAX_ROWS * (K * K + K) * sizeof(double) : 0; }
 

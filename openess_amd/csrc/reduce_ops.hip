@@ -177,6 +177,109 @@ int run_normalize(const float* in, float* out, int64_t L, int64_t nchunk, int64_
     return OESS_OK;
 }
 
+// ------------------------------------------------------------------------------------------ K32
+// K2 with EventPreprocessor's hot-pixel list (inference_utils.py:71-72) as a byte mask [H][W] in source coordinates: a hot pixel
+// counts as zero in every channel.  The flip (:74-75) permutes the tensor and leaves the statistics alone.
+// grid = (blocks per plane, B, slices): a thread walks the PIXELS of the H x W plane (grid-stride) and, per group of four pixels,
+// the Cs channels of its slice -- the pixel index is the mask index, so no per-element division is needed (norm_stats_kernel's
+// flat walk over the Cs * HW chunk would need r % HW per load), and the mask word is read once per Cs event loads.
+// Same partial-row layout and finalize kernel as K2.
+__global__ __launch_bounds__(THREADS) void norm_stats_masked_kernel(const float* __restrict__ in, int Cs, int64_t HW, int64_t in_stride,
+                                                                    int64_t in_off, int vec, const unsigned char* __restrict__ mask,
+                                                                    double* __restrict__ stats) {
+    double acc[3] = {0.0, 0.0, 0.0};
+    const float* src = in + in_off + (int64_t)blockIdx.z * Cs * HW + (int64_t)blockIdx.y * in_stride;
+    double* row = stats + 4 * (int64_t)gridDim.z + 4 * ((int64_t)blockIdx.z * K2_MAX_ROWS + (int64_t)blockIdx.y * gridDim.x + blockIdx.x);
+    const int64_t tid = (int64_t)blockIdx.x * THREADS + threadIdx.x, nthr = (int64_t)gridDim.x * THREADS;
+    if (vec) {
+        const int64_t P4 = HW >> 2;
+        for (int64_t r = tid; r < P4; r += nthr) {
+            const uint32_t m = *reinterpret_cast<const uint32_t*>(mask + r * 4);
+#pragma unroll 5
+            for (int c = 0; c < Cs; ++c) {
+                const float4 v = *reinterpret_cast<const float4*>(src + (int64_t)c * HW + r * 4);
+                const float a[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+                for (int k = 0; k < 4; ++k) {
+                    const float z = ((m >> (8 * k)) & 0xffu) ? 0.0f : a[k];
+                    const double d = (double)z;
+                    acc[0] += d; acc[1] += d * d; acc[2] += (z != 0.0f) ? 1.0 : 0.0;
+                }
+            }
+        }
+    } else {
+        for (int64_t r = tid; r < HW; r += nthr) {
+            const bool hot = mask[r] != 0;
+            for (int c = 0; c < Cs; ++c) {
+                const float z = hot ? 0.0f : src[(int64_t)c * HW + r];
+                const double d = (double)z;
+                acc[0] += d; acc[1] += d * d; acc[2] += (z != 0.0f) ? 1.0 : 0.0;
+            }
+        }
+    }
+    block_partial_store<3>(acc, row);
+}
+
+// Apply to dense fp32 NCHW, grid = (blocks per plane, Cs, B): out[b, c, p'] = norm(hot[p] ? 0 : in[b, c0 + c, p]) with p' = HW - 1 - p
+// under the flip (mirroring H and W of a contiguous plane reverses its linear index) -- norm_apply_kernel's float32 arithmetic.
+__global__ __launch_bounds__(THREADS) void norm_apply_pre_kernel(const float* __restrict__ in, float* __restrict__ out, int Cs, int64_t HW,
+                                                                 int64_t in_stride, int64_t in_off, int vec,
+                                                                 const unsigned char* __restrict__ mask, int flip, int normalize,
+                                                                 const double* __restrict__ stats) {
+    const double nnz = normalize ? stats[2] : 0.0;
+    const bool active = nnz > 0.0;
+    float mean = 0.f, stdv = 1.f;
+    if (active) {
+        const float nf = (float)nnz;
+        mean = (float)stats[0] / nf;
+        stdv = sqrtf(__fsub_rn((float)stats[1] / nf, __fmul_rn(mean, mean)));
+    }
+    const float* src = in + in_off + (int64_t)blockIdx.z * in_stride + (int64_t)blockIdx.y * HW;
+    float* dst = out + ((int64_t)blockIdx.z * Cs + blockIdx.y) * HW;
+    const int64_t tid = (int64_t)blockIdx.x * THREADS + threadIdx.x, nthr = (int64_t)gridDim.x * THREADS;
+    if (vec) {
+        const int64_t P4 = HW >> 2;
+        for (int64_t r = tid; r < P4; r += nthr) {
+            const float4 v = *reinterpret_cast<const float4*>(src + r * 4);
+            const uint32_t m = mask ? *reinterpret_cast<const uint32_t*>(mask + r * 4) : 0u;
+            float a[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                a[k] = ((m >> (8 * k)) & 0xffu) ? 0.0f : a[k];
+                if (active) a[k] = __fmul_rn((a[k] != 0.0f) ? 1.0f : 0.0f, __fsub_rn(a[k], mean)) / stdv;
+            }
+            if (flip) *reinterpret_cast<float4*>(dst + (HW - 4 - r * 4)) = make_float4(a[3], a[2], a[1], a[0]);
+            else *reinterpret_cast<float4*>(dst + r * 4) = make_float4(a[0], a[1], a[2], a[3]);
+        }
+    } else {
+        for (int64_t r = tid; r < HW; r += nthr) {
+            float a = (mask && mask[r]) ? 0.0f : src[r];
+            if (active) a = __fmul_rn((a != 0.0f) ? 1.0f : 0.0f, __fsub_rn(a, mean)) / stdv;
+            dst[flip ? HW - 1 - r : r] = a;
+        }
+    }
+}
+
+// blocks per plane of the two kernels above: >= 2 pixel groups per thread, at most K2_MAX_ROWS partial rows per slice
+__host__ unsigned pre_plane_blocks(int64_t HW, int vec, int64_t cap) {
+    int64_t gx = (HW / (vec ? 4 : 1) + THREADS * 2 - 1) / (THREADS * 2);
+    if (gx > cap) gx = cap;
+    if (gx < 1) gx = 1;
+    return (unsigned)gx;
+}
+
+// statistics of n_slices consecutive Cs-channel slices from channel c0 on under a hot-pixel mask (mask != null)
+int run_masked_stats(const float* in, int B, int Ctot, int c0, int Cs, int n_slices, int64_t HW, const unsigned char* mask,
+                     double* stats, hipStream_t st) {
+    const int vec = ((HW & 3) == 0) && (((uintptr_t)in & 15) == 0) && (((uintptr_t)mask & 3) == 0);
+    const dim3 grid(pre_plane_blocks(HW, vec, K2_MAX_ROWS / B), (unsigned)B, (unsigned)n_slices);
+    hipLaunchKernelGGL(norm_stats_masked_kernel, grid, dim3(THREADS), 0, st, in, Cs, HW, (int64_t)Ctot * HW, (int64_t)c0 * HW, vec,
+                       mask, stats);
+    hipLaunchKernelGGL(norm_stats_finalize_kernel, dim3((unsigned)n_slices), dim3(THREADS), 0, st, stats, (int)(grid.x * grid.y));
+    OESS_HIP(hipGetLastError());
+    return OESS_OK;
+}
+
 // ------------------------------------------------------------------------------------------ K7
 // Superpixel scatter-mean, forward.  DETERMINISTIC: every partial sum that meets another one does so as a 64-bit fixed-point
 // integer (2^-32 units), so neither the order in which lane groups reach the LDS table nor the order in which workgroups
@@ -868,6 +971,45 @@ int oess_masked_stats_slices_f32(const float* in, int B, int Ctot, int Cs, int n
     grid.z = (unsigned)n_slices;
     hipLaunchKernelGGL(norm_stats_kernel, grid, dim3(THREADS), 0, st, in, L, (int64_t)B, in_stride, (int64_t)0, vec, stats);
     hipLaunchKernelGGL(norm_stats_finalize_kernel, dim3((unsigned)n_slices), dim3(THREADS), 0, st, stats, (int)(grid.x * grid.y));
+    OESS_HIP(hipGetLastError());
+    return OESS_OK;
+}
+
+// K32: without a mask the statistics are those of the option-less entry points (the flip does not change them)
+int oess_masked_stats_slice_pre_f32(const float* in, int B, int Ctot, int c0, int Cs, int H, int W, const oess_event_pre_t* pre,
+                                    double* stats, oess_stream_t stream) {
+    if (!pre || H <= 0 || W <= 0) return OESS_EINVAL;
+    const int64_t HW = (int64_t)H * W;
+    if (!pre->hot_mask) return oess_masked_stats_slice_f32(in, B, Ctot, c0, Cs, HW, stats, stream);
+    if (!in || !stats || B <= 0 || Ctot <= 0 || Cs <= 0 || c0 < 0 || c0 + Cs > Ctot || B > K2_MAX_ROWS) return OESS_EINVAL;
+    return run_masked_stats(in, B, Ctot, c0, Cs, 1, HW, pre->hot_mask, stats, (hipStream_t)stream);
+}
+
+int oess_masked_stats_slices_pre_f32(const float* in, int B, int Ctot, int Cs, int n_slices, int H, int W,
+                                     const oess_event_pre_t* pre, double* stats, oess_stream_t stream) {
+    if (!pre || H <= 0 || W <= 0) return OESS_EINVAL;
+    const int64_t HW = (int64_t)H * W;
+    if (!pre->hot_mask) return oess_masked_stats_slices_f32(in, B, Ctot, Cs, n_slices, HW, stats, stream);
+    if (!in || !stats || B <= 0 || Ctot <= 0 || Cs <= 0 || n_slices <= 0 || (int64_t)n_slices * Cs > Ctot || B > K2_MAX_ROWS ||
+        n_slices > 65535)
+        return OESS_EINVAL;
+    return run_masked_stats(in, B, Ctot, 0, Cs, n_slices, HW, pre->hot_mask, stats, (hipStream_t)stream);
+}
+
+int oess_masked_normalize_slice_pre_f32(const float* in, float* out, int B, int Ctot, int c0, int Cs, int H, int W,
+                                        const oess_event_pre_t* pre, int normalize, double* stats, oess_stream_t stream) {
+    if (!pre || !in || !out || in == out || H <= 0 || W <= 0 || B <= 0 || Ctot <= 0 || Cs <= 0 || c0 < 0 || c0 + Cs > Ctot ||
+        B > K2_MAX_ROWS || Cs > 65535 || (normalize && !stats))
+        return OESS_EINVAL;
+    const int64_t HW = (int64_t)H * W;
+    if (normalize) {
+        const int rc = oess_masked_stats_slice_pre_f32(in, B, Ctot, c0, Cs, H, W, pre, stats, stream);
+        if (rc != OESS_OK) return rc;
+    }
+    const int vec = ((HW & 3) == 0) && (((uintptr_t)in & 15) == 0) && (((uintptr_t)out & 15) == 0) && (((uintptr_t)pre->hot_mask & 3) == 0);
+    const dim3 grid(pre_plane_blocks(HW, vec, 64), (unsigned)Cs, (unsigned)B);
+    hipLaunchKernelGGL(norm_apply_pre_kernel, grid, dim3(THREADS), 0, (hipStream_t)stream, in, out, Cs, HW, (int64_t)Ctot * HW,
+                       (int64_t)c0 * HW, vec, pre->hot_mask, pre->flip, normalize, (const double*)stats);
     OESS_HIP(hipGetLastError());
     return OESS_OK;
 }

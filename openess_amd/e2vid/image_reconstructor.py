@@ -72,7 +72,8 @@ class ImageReconstructor:
             if (not need_latents and not reconstruct and not self.crop.needs_pad and unet is not None
                     and unet.events_fusable(events, cs)):
                 # EventPreprocessor apply + NHWC8 re-layout + head + encoder-0 conv in ONE kernel, straight from the event tensor
-                kw['raw'] = (events, c0, cs, not self.event_preprocessor.no_normalize)
+                # (hot-pixel mask and flip ride along: the kernel's patch loader applies them, K32)
+                kw['raw'] = (events, c0, cs, not self.event_preprocessor.no_normalize, self.event_preprocessor.pre_for(events))
                 x = None
             else:
                 first = torch.cuda.stream(wavefront.streams[0]) if wavefront is not None else contextlib.nullcontext()
@@ -98,7 +99,10 @@ class ImageReconstructor:
                 x = self.event_preprocessor(events)
             else:
                 (c0, cs) = channel_slice
-                if self.event_preprocessor.no_normalize:
+                pre = self.event_preprocessor.pre_for(event_tensor)
+                if pre is not None:          # hot pixels zeroed, H and W mirrored (K32), then the slice's normalisation
+                    x = hip.masked_normalize_slice(event_tensor, c0, cs, pre=pre, normalize=not self.event_preprocessor.no_normalize)
+                elif self.event_preprocessor.no_normalize:
                     x = event_tensor[:, c0:c0 + cs]
                 else:
                     x = hip.masked_normalize_slice(event_tensor, c0, cs)

@@ -46,6 +46,11 @@ def check_states(prev_states, precision, block_type=None):
                              "not carry over between block types (start a new sequence)")
 
 
+def _raw_pre(raw):
+    """The hip.EventPre of a raw = (events, c0, cs, normalize[, pre]) tuple (None for the four-element form)."""
+    return raw[4] if len(raw) > 4 else None
+
+
 def _latents(head, blocks):
     """The latents by downsampling factor (unet.py:163): {1: head output, 2: encoder 0's hidden state, 4: encoder 1's, ...}."""
     return {1: head, **{2 ** (i + 1): b for i, b in enumerate(blocks)}}
@@ -100,17 +105,18 @@ class UNetRecurrent(nn.Module):
 
     def _head_enc0(self, x, prev_state, raw=None):
         """Encoder 0's conv output straight from the voxel slice (the 32-channel head output is never written): fills the x half
-        of the level-0 cat(x, h) buffer and returns the state.  raw = (events fp32 [B, Ctot, H, W], c0, cs, normalize): the slice is
-        normalised and packed inside the kernel as well (x is not needed)."""
+        of the level-0 cat(x, h) buffer and returns the state.  raw = (events fp32 [B, Ctot, H, W], c0, cs, normalize[, pre]): the
+        slice is normalised and packed inside the kernel as well (x is not needed); pre = the hip.EventPre of EventPreprocessor's
+        hot-pixel list and flip, or None."""
         h, e = self.head, self.encoders[0]
         state = prev_state if prev_state is not None else e.new_state(raw[0] if raw is not None else x)
         ec = e.conv
         pwh, pwe = h._packed(8), ec._packed(32)
         out = engine.nhwc(state['xh'][state['cur']][:, :64])
         if raw is not None:
-            ev, c0, cs, normalize = raw
+            ev, c0, cs, normalize = raw[:4]
             hip.e2vid_events_head_enc0(ev, c0, cs, normalize, pwh.packed, pwh.bias, h.activation_name == 'relu', pwe.packed, pwe.bias,
-                                       ec.activation_name == 'relu', out=out)
+                                       ec.activation_name == 'relu', out=out, pre=_raw_pre(raw))
         else:
             hip.e2vid_head_enc0(engine.nhwc(x), pwh.packed, pwh.bias, h.activation_name == 'relu', pwe.packed, pwe.bias,
                                 ec.activation_name == 'relu', out=out)
@@ -225,7 +231,7 @@ class UNetRecurrent(nn.Module):
                 x.record_stream(main)
             skew, wavefront = False, None
             if raw is not None:
-                x = hip.event_slice_to_nhwc8(raw[0], raw[1], raw[2], normalize=raw[3])
+                x = hip.event_slice_to_nhwc8(raw[0], raw[1], raw[2], normalize=raw[3], pre=_raw_pre(raw))
                 raw = None
             need_head = True                # (nothing fuses the head away: its output exists either way)
         if skew and not reconstruct and wavefront is None:

@@ -46,11 +46,12 @@ def load_model(path_to_model):
 
 def reconstruct(path_to_events, model, output_folder=None, window_size=None, fixed_duration=False, window_duration=33.33,
                 num_events_per_pixel=0.35, skipevents=0, suboffset=0, device='cuda', max_windows=None, postprocessor=None,
-                options=None, precision='bf16'):
+                options=None, precision='bf16', hot_pixels_file=None, flip=False):
     """Returns the list of reconstructed images (uint8 [H, W]); writes frame_%010d.png + timestamps.txt when a folder is given.
     postprocessor: a PostProcessor applied to each cropped frame (its bytes are the image); None = round(clamp(img, 0, 1) * 255).
     options: passed to ImageReconstructor (no_normalize, no_recurrent).  precision: 'bf16' (default) or 'fp32' (the whole network
-    in fp32, UNetRecurrent.forward_fp32); it overrides options.precision."""
+    in fp32, UNetRecurrent.forward_fp32); it overrides options.precision.  hot_pixels_file (comma-separated `x,y` rows) / flip:
+    EventPreprocessor's event-side options (e2vid/options/inference_options.py); when given they override the options' own."""
     if precision not in ('bf16', 'fp32'):
         raise ValueError(f"precision must be 'bf16' or 'fp32', got {precision!r}")
     with open(path_to_events) as f:
@@ -59,6 +60,10 @@ def reconstruct(path_to_events, model, output_folder=None, window_size=None, fix
     device = torch.device(device)
     model = model.to(device).eval()
     opts = SimpleNamespace(**dict(vars(options) if options is not None else {}, precision=precision))
+    if hot_pixels_file:
+        opts.hot_pixels_file = hot_pixels_file
+    if flip:
+        opts.flip = True
     rec = ImageReconstructor(model, height, width, model.num_bins, device, opts)
     N = window_size
     if not fixed_duration and N is None:
@@ -98,7 +103,7 @@ POSTPROCESS_FLAGS = (('unsharp_mask_amount', 0.3, float), ('unsharp_mask_sigma',
                      ('bilateral_filter_sigma', 0.0, float))
 
 
-def main(argv=None):
+def build_parser():
     p = argparse.ArgumentParser(description='Evaluating a trained network')
     p.add_argument('-c', '--path_to_model', required=True, type=str)
     p.add_argument('-i', '--input_file', required=True, type=str)
@@ -114,6 +119,8 @@ def main(argv=None):
     p.add_argument('--dataset_name', default='reconstruction', type=str)
     p.add_argument('--no-normalize', dest='no_normalize', action='store_true')
     p.add_argument('--no-recurrent', dest='no_recurrent', action='store_true')
+    p.add_argument('--hot_pixels_file', default=None, type=str, help='comma-separated x,y rows: pixels zeroed in every event tensor')
+    p.add_argument('--flip', dest='flip', action='store_true', help='mirror the event tensors (H and W) before the network')
     p.add_argument('--precision', choices=('bf16', 'fp32'), default='bf16',
                    help="network arithmetic: bf16 (default, the training path's kernels) or fp32 (as the reference)")
     g = p.add_argument_group('post-processing (e2vid/options/inference_options.py:31-46; only with --postprocess)')
@@ -123,11 +130,16 @@ def main(argv=None):
             g.add_argument('--' + name, dest=name, action='store_true', default=None)
         else:
             g.add_argument('--' + name, dest=name, default=None, type=typ, help='default: {}'.format(default))
+    return p
+
+
+def main(argv=None):
+    p = build_parser()
     a = p.parse_args(argv)
     given = ['--' + name for name, _, _ in POSTPROCESS_FLAGS if getattr(a, name) is not None]
     if given and not a.postprocess:
         p.error('{} need(s) --postprocess'.format(', '.join(given)))
-    opts = SimpleNamespace(no_normalize=a.no_normalize, no_recurrent=a.no_recurrent,
+    opts = SimpleNamespace(no_normalize=a.no_normalize, no_recurrent=a.no_recurrent, hot_pixels_file=a.hot_pixels_file, flip=a.flip,
                            **{name: default if getattr(a, name) is None else getattr(a, name) for name, default, _ in POSTPROCESS_FLAGS})
     post = PostProcessor(torch.device('cuda'), opts) if a.postprocess else None
     out = os.path.join(a.output_folder, a.dataset_name) if a.output_folder else None

@@ -40,23 +40,75 @@ class CropParameters:
         self.iy0, self.iy1 = self.cy - floor(height / 2), self.cy + ceil(height / 2)
 
 
+def load_hot_pixels(path):
+    """The reference's hot-pixel file (e2vid/utils/inference_utils.py:59-64): comma-separated `x,y` rows -> int64 [n, 2].  A file
+    that cannot be opened prints the reference's warning and lists nothing.  A single row is one pixel (np.loadtxt returns a
+    1-D pair for it, on which the reference's `for x, y in ...` loop breaks)."""
+    import numpy as np
+    try:
+        rows = np.loadtxt(path, delimiter=',', ndmin=2)
+    except IOError:
+        print('WARNING: could not load hot pixels file: {}'.format(path))
+        return np.zeros((0, 2), np.int64)
+    if rows.size and rows.shape[1] != 2:
+        raise ValueError(f"hot pixels file {path}: rows must be `x,y`, got {rows.shape[1]} columns")
+    rows = rows.reshape(-1, 2).astype(np.int64)             # .astype(np.int) there: truncation towards zero
+    print('Will remove {} hot pixels'.format(rows.shape[0]))
+    return rows
+
+
 class EventPreprocessor:
-    """Whole-tensor non-zero mean/std normalisation (hot-pixel list empty and flip off in every shipped
-    config, e2vid/options/inference_options.py).  `__call__` keeps the reference contract (tensor in,
-    tensor out); `slice_to_nhwc8` is the fused form used by ImageReconstructor."""
+    """Hot-pixel removal, flip and the whole-tensor non-zero mean/std normalisation, in the reference's order
+    (e2vid/utils/inference_utils.py:70-87): events[:, :, y, x] = 0 for every `x,y` row of options.hot_pixels_file, then
+    torch.flip(events, dims=[2, 3]) with options.flip, then the normalisation unless options.no_normalize.  `__call__` keeps the
+    reference contract (tensor in, tensor out); `slice_to_nhwc8` is the fused form used by ImageReconstructor.  Both options
+    run inside the event kernels (hip.EventPre).  Difference from the reference, documented: the caller's tensor
+    is NOT mutated (the reference zeroes the hot pixels of its argument in place)."""
 
     def __init__(self, options=None):
         self.no_normalize = bool(getattr(options, 'no_normalize', False))
-        if getattr(options, 'hot_pixels_file', None) or getattr(options, 'flip', False):
-            raise NotImplementedError("hot-pixel removal / flip are not on the training path")
+        self.hot_pixels_file = getattr(options, 'hot_pixels_file', None) or None
+        self.hot_pixel_locations = load_hot_pixels(self.hot_pixels_file) if self.hot_pixels_file else []
+        self.flip = bool(getattr(options, 'flip', False))
+        if self.flip:
+            print('Will flip event tensors.')
+        self._pre = {}                                     # (H, W, device) -> hip.EventPre, built at the first tensor of that size
+
+    def pre_for(self, events):
+        """The hip.EventPre of this preprocessor for a [B, C, H, W] tensor (None without options).  The mask is built once per
+        (H, W, device); a row outside H x W is a ValueError naming it (the reference raises IndexError, or wraps a negative one)."""
+        if not self.flip and len(self.hot_pixel_locations) == 0:
+            return None
+        if events.ndim != 4:
+            raise ValueError(f"hot-pixel removal / flip need a [B, C, H, W] event tensor, got {tuple(events.shape)}")
+        H, W = int(events.shape[2]), int(events.shape[3])
+        key = (H, W, events.device)
+        pre = self._pre.get(key)
+        if pre is None:
+            mask = None
+            if len(self.hot_pixel_locations):
+                import numpy as np
+                m = np.zeros((H, W), np.uint8)
+                for i, (x, y) in enumerate(self.hot_pixel_locations):
+                    if not (0 <= x < W and 0 <= y < H):
+                        raise ValueError(f"hot pixels file {self.hot_pixels_file}: row {i + 1} (x={x}, y={y}) is outside the "
+                                         f"{W} x {H} (W x H) event tensor")
+                    m[y, x] = 1
+                mask = torch.from_numpy(m).to(events.device)
+            pre = self._pre[key] = hip.EventPre(mask, self.flip)
+        return pre
 
     def __call__(self, events):
-        if self.no_normalize:
-            return events
-        return hip.masked_normalize(events.contiguous())
+        pre = self.pre_for(events)
+        if pre is None:
+            if self.no_normalize:
+                return events
+            return hip.masked_normalize(events.contiguous())
+        events = events.contiguous()
+        return hip.masked_normalize_slice(events, 0, events.shape[1], pre=pre, normalize=not self.no_normalize)
 
     def slice_to_nhwc8(self, events, c0, cs):
-        return hip.event_slice_to_nhwc8(events, c0, cs, normalize=not self.no_normalize)
+        return hip.event_slice_to_nhwc8(events, c0, cs, normalize=not self.no_normalize, pre=self.pre_for(events))
 
 
 def _e2vid_grid_hip(events, num_bins, width, height, device):

@@ -200,8 +200,51 @@ def png_decode_gray8_batch(files, lengths, H, W, flips=None, out=None):
 
 
 # ------------------------------------------------------------------------------------------ K2
-def masked_normalize(x, out=None):
-    """EventPreprocessor / normalize_voxel_grid on a dense float32 tensor (whole-tensor statistics)."""
+class EventPre:
+    """EventPreprocessor's event-side options (e2vid/utils/inference_utils.py:71-75) for the kernels that read the raw event
+    tensor: hot_mask = uint8 [H, W] device tensor, non-zero = hot pixel, in SOURCE coordinates (None: no list); flip mirrors H and
+    W.  Order as in the reference: zero the hot pixels, then flip, then normalise.  With `pre=` a wrapper computes what it
+    computes without on torch.flip(zeroed copy, [2, 3]); the caller's tensor is only read."""
+
+    def __init__(self, hot_mask=None, flip=False):
+        if hot_mask is not None:
+            if not isinstance(hot_mask, torch.Tensor) or hot_mask.dtype != torch.uint8:
+                raise ValueError("EventPre: hot_mask must be a uint8 tensor")
+            if hot_mask.ndim != 2 or not hot_mask.is_contiguous():
+                raise ValueError("EventPre: hot_mask must be a contiguous [H, W] tensor")
+        self.hot_mask, self.flip = hot_mask, bool(flip)
+
+    def tag(self):
+        """What a statistics cache has to compare: the flip does not change statistics, the mask does."""
+        m = self.hot_mask
+        return None if m is None else (m.data_ptr(), m._version)
+
+    def bind(self, events):
+        """Host-side checks against the [B, C, H, W] event tensor -> the oess_event_pre_t to pass (keep it alive over the call)."""
+        if events.ndim != 4:
+            raise ValueError("pre= needs a [B, C, H, W] event tensor")
+        m = self.hot_mask
+        if m is not None:
+            if tuple(m.shape) != tuple(events.shape[2:]):
+                raise ValueError(f"EventPre: hot_mask is {tuple(m.shape)}, the event tensor is H x W = {tuple(events.shape[2:])}")
+            if not m.is_cuda or m.device != events.device:
+                raise ValueError(f"EventPre: hot_mask is on {m.device}, the event tensor on {events.device}")
+        return _lib.EventPre(None if m is None else m.data_ptr(), int(self.flip))
+
+
+def _bind_pre(pre, events):
+    if not isinstance(pre, EventPre):
+        raise ValueError("pre must be a hip.EventPre")
+    return pre.bind(events)
+
+
+def masked_normalize(x, out=None, pre=None):
+    """EventPreprocessor / normalize_voxel_grid on a dense float32 tensor (whole-tensor statistics).  pre (EventPre; x is then
+    [B, C, H, W]): hot pixels zeroed and H, W mirrored first."""
+    if pre is not None:
+        if x.ndim != 4:
+            raise ValueError("pre= needs a [B, C, H, W] event tensor")
+        return masked_normalize_slice(x, 0, x.shape[1], out=out, pre=pre)
     lib = _lib.load()
     _need_gpu(x)
     if x.dtype != torch.float32 or not x.is_contiguous():
@@ -214,8 +257,12 @@ def masked_normalize(x, out=None):
     return out
 
 
-def masked_normalize_slice(x, c0, cs, out=None):
-    """Normalise the channel slice x[:, c0:c0+cs] of a contiguous [B, C, H, W] float32 tensor."""
+def masked_normalize_slice(x, c0, cs, out=None, pre=None, normalize=True):
+    """Normalise the channel slice x[:, c0:c0+cs] of a contiguous [B, C, H, W] float32 tensor.  pre (EventPre): hot pixels
+    zeroed and H, W mirrored first; normalize=False (with pre only) stops after that."""
+    cpre = None if pre is None else _bind_pre(pre, x)
+    if pre is None and not normalize:
+        raise ValueError("normalize=False without pre= is a plain slice")
     lib = _lib.load()
     _need_gpu(x)
     if x.dtype != torch.float32 or not x.is_contiguous() or x.ndim != 4:
@@ -224,6 +271,13 @@ def masked_normalize_slice(x, c0, cs, out=None):
     if out is None:
         out = torch.empty((B, cs, H, W), dtype=torch.float32, device=x.device)
     stats = torch.empty(lib.oess_masked_stats_doubles(1), dtype=torch.float64, device=x.device)
+    if cpre is not None:
+        if out.data_ptr() == x.data_ptr():
+            raise ValueError("pre=: out must not alias the input")
+        _lib.check(lib.oess_masked_normalize_slice_pre_f32(_ptr(x), _ptr(out), B, Ct, c0, cs, H, W, ctypes.byref(cpre),
+                                                           int(bool(normalize)), _ptr(stats), _stream()),
+                   "oess_masked_normalize_slice_pre_f32")
+        return out
     _lib.check(lib.oess_masked_normalize_slice_f32(_ptr(x), _ptr(out), B, Ct, c0, cs, H * W, _ptr(stats), _stream()),
                "oess_masked_normalize_slice_f32")
     return out
@@ -695,9 +749,12 @@ def e2vid_head_enc0(x8, head_packed, head_bias, head_relu, enc_packed, enc_bias,
     return out
 
 
-def e2vid_events_head_enc0(events, c0, cs, normalize, head_packed, head_bias, head_relu, enc_packed, enc_bias, enc_relu, out=None):
+def e2vid_events_head_enc0(events, c0, cs, normalize, head_packed, head_bias, head_relu, enc_packed, enc_bias, enc_relu, out=None,
+                           pre=None):
     """e2vid_head_enc0 fed from the fp32 event tensor [B, Ctot, H, W]: the slice's EventPreprocessor normalisation and the
-    NHWC8 bf16 packing happen inside the kernel (no intermediate tensor at all between the voxel grid and encoder 0's output)."""
+    NHWC8 bf16 packing happen inside the kernel (no intermediate tensor at all between the voxel grid and encoder 0's output).
+    pre (EventPre): the patch loader also zeroes the hot pixels and mirrors H and W (K32)."""
+    cpre = None if pre is None else _bind_pre(pre, events)
     lib = _lib.load()
     _need_gpu(events, head_packed, enc_packed)
     if events.dtype != torch.float32 or not events.is_contiguous() or events.ndim != 4:
@@ -711,7 +768,14 @@ def e2vid_events_head_enc0(events, c0, cs, normalize, head_packed, head_bias, he
     _, _, _, _, ops = _nhwc_geom(out)
     if tuple(out.shape) != (B, Ho, Wo, 64):
         raise ValueError(f"bad output shape {tuple(out.shape)} != {(B, Ho, Wo, 64)}")
-    stats = _slice_stats(events, c0, cs) if normalize else None
+    stats = _slice_stats(events, c0, cs, pre) if normalize else None
+    if cpre is not None:
+        _lib.check(lib.oess_e2vid_events_head_enc0_pre_bf16(_ptr(events), B, Ct, c0, cs, H, W, ctypes.byref(cpre), _ptr(stats),
+                                                            int(bool(normalize)), _ptr(head_packed), _ptr(head_bias),
+                                                            int(bool(head_relu)), _ptr(enc_packed), _ptr(enc_bias),
+                                                            int(bool(enc_relu)), _ptr(out), ops, _stream()),
+                   "oess_e2vid_events_head_enc0_pre_bf16")
+        return out
     _lib.check(lib.oess_e2vid_events_head_enc0_bf16(_ptr(events), B, Ct, c0, cs, H, W, _ptr(stats), int(bool(normalize)),
                                                     _ptr(head_packed), _ptr(head_bias), int(bool(head_relu)), _ptr(enc_packed),
                                                     _ptr(enc_bias), int(bool(enc_relu)), _ptr(out), ops, _stream()),
@@ -910,49 +974,77 @@ def conv5x5s2_group(problems):
 _SLICE_STATS = {}
 
 
-def masked_stats_slices(events, cs, index=None):
+def masked_stats_slices(events, cs, index=None, pre=None):
     """{sum, sumsq, nnz, -} of every cs-channel slice of a contiguous fp32 [B, Ctot, H, W] tensor in ONE launch -> float64
-    [Ctot // cs, 4]; with `index` the row of that slice.
+    [Ctot // cs, 4]; with `index` the row of that slice.  pre (EventPre): its hot pixels add nothing (the flip does not change
+    statistics); the mask is part of the cache key below.
     The table is cached ONLY for the access pattern it exists for -- a sub-window loop walking the slices of one tensor in order
     (0, 1, 2, ...): a request is served from the cache iff the tensor's (pointer, version, shape) are unchanged AND `index` is
     exactly the successor of the previous request.  Anything else -- slice 0 (a new loop: the voxelizer rewrites the same
     allocation every batch with the same version), a loop entered in the middle, a repeated or skipped slice, `index=None` --
     recomputes, so stale statistics of a previous batch cannot be served to a caller that does not start at slice 0."""
+    cpre = None if pre is None else _bind_pre(pre, events)
     lib = _lib.load()
     B, Ct, H, W = events.shape
     key = (events.device.index, torch.cuda.current_stream(events.device).cuda_stream)
     tag = (events.data_ptr(), events._version, tuple(events.shape), cs)
+    if pre is not None and pre.tag() is not None:
+        tag = tag + (pre.tag(),)
     hit = _SLICE_STATS.get(key)
     if hit is not None and hit[0] == tag and index is not None and index > 0 and index == hit[2]:
         hit[2] = index + 1
         return hit[1][index]
     n = Ct // cs
     buf = torch.empty(lib.oess_masked_stats_doubles(n), dtype=torch.float64, device=events.device)   # totals + partial rows
-    _lib.check(lib.oess_masked_stats_slices_f32(_ptr(events), B, Ct, cs, n, H * W, _ptr(buf), _stream()),
-               "oess_masked_stats_slices_f32")
+    if cpre is not None:
+        _need_gpu(events)
+        if events.dtype != torch.float32 or not events.is_contiguous():
+            raise ValueError("needs contiguous float32 [B, C, H, W]")
+        _lib.check(lib.oess_masked_stats_slices_pre_f32(_ptr(events), B, Ct, cs, n, H, W, ctypes.byref(cpre), _ptr(buf), _stream()),
+                   "oess_masked_stats_slices_pre_f32")
+    else:
+        _lib.check(lib.oess_masked_stats_slices_f32(_ptr(events), B, Ct, cs, n, H * W, _ptr(buf), _stream()),
+                   "oess_masked_stats_slices_f32")
     stats = buf[:4 * n].view(n, 4)
     _SLICE_STATS[key] = [tag, stats, (index + 1) if index is not None else -1]
     return stats if index is None else stats[index]
 
 
-def _slice_stats(events, c0, cs):
-    """The EventPreprocessor statistics of events[:, c0:c0+cs]: a row of the table of all slices when the tensor is a whole
-    number of cs-channel slices (masked_stats_slices), otherwise one launch for this slice alone."""
-    B, Ct, H, W = events.shape
-    if Ct > cs and Ct % cs == 0 and c0 % cs == 0:
-        return masked_stats_slices(events, cs, index=c0 // cs)
+def masked_stats_slice(events, c0, cs, pre=None):
+    """{sum, sumsq, nnz, -} (float64, on the device) of the one slice events[:, c0:c0+cs] of a contiguous fp32 [B, Ctot, H, W]
+    tensor, by a launch of its own.  pre (EventPre): its hot pixels add nothing."""
+    cpre = None if pre is None else _bind_pre(pre, events)
     lib = _lib.load()
+    _need_gpu(events)
+    if events.dtype != torch.float32 or not events.is_contiguous() or events.ndim != 4:
+        raise ValueError("needs contiguous float32 [B, C, H, W]")
+    B, Ct, H, W = events.shape
     stats = torch.empty(lib.oess_masked_stats_doubles(1), dtype=torch.float64, device=events.device)
+    if cpre is not None:
+        _lib.check(lib.oess_masked_stats_slice_pre_f32(_ptr(events), B, Ct, c0, cs, H, W, ctypes.byref(cpre), _ptr(stats), _stream()),
+                   "oess_masked_stats_slice_pre_f32")
+        return stats
     _lib.check(lib.oess_masked_stats_slice_f32(_ptr(events), B, Ct, c0, cs, H * W, _ptr(stats), _stream()),
                "oess_masked_stats_slice_f32")
     return stats
 
 
-def event_slice_to_nhwc8(events, c0, cs, normalize=True, out=None):
+def _slice_stats(events, c0, cs, pre=None):
+    """The EventPreprocessor statistics of events[:, c0:c0+cs]: a row of the table of all slices when the tensor is a whole
+    number of cs-channel slices (masked_stats_slices), otherwise one launch for this slice alone."""
+    B, Ct, H, W = events.shape
+    if Ct > cs and Ct % cs == 0 and c0 % cs == 0:
+        return masked_stats_slices(events, cs, index=c0 // cs, pre=pre)
+    return masked_stats_slice(events, c0, cs, pre=pre)
+
+
+def event_slice_to_nhwc8(events, c0, cs, normalize=True, out=None, pre=None):
     """events: contiguous fp32 [B, Ctot, H, W]; returns logical [B, 8, H, W] channels_last bf16 holding the
     (optionally EventPreprocessor-normalised) slice events[:, c0:c0+cs], zero padded to 8 channels.
     When the tensor is a whole number of cs-channel slices (the sub-windows of one sample) the statistics of ALL slices are
-    formed by one launch at the first request and reused for the others."""
+    formed by one launch at the first request and reused for the others.
+    pre (EventPre): hot pixels zeroed and H, W mirrored first, also with normalize=False (K32)."""
+    cpre = None if pre is None else _bind_pre(pre, events)
     lib = _lib.load()
     _need_gpu(events)
     if events.dtype != torch.float32 or not events.is_contiguous() or events.ndim != 4:
@@ -960,7 +1052,11 @@ def event_slice_to_nhwc8(events, c0, cs, normalize=True, out=None):
     B, Ct, H, W = events.shape
     if out is None:
         out = torch.empty((B, H, W, 8), dtype=torch.bfloat16, device=events.device)
-    stats = _slice_stats(events, c0, cs) if normalize else None
+    stats = _slice_stats(events, c0, cs, pre) if normalize else None
+    if cpre is not None:
+        _lib.check(lib.oess_event_slice_to_nhwc8_pre_bf16(_ptr(events), B, Ct, c0, cs, H, W, ctypes.byref(cpre), _ptr(stats),
+                                                          int(normalize), _ptr(out), _stream()), "oess_event_slice_to_nhwc8_pre_bf16")
+        return out.permute(0, 3, 1, 2)
     _lib.check(lib.oess_event_slice_to_nhwc8_bf16(_ptr(events), B, Ct, c0, cs, H * W, _ptr(stats), int(normalize),
                                                   _ptr(out), _stream()), "oess_event_slice_to_nhwc8_bf16")
     return out.permute(0, 3, 1, 2)

@@ -75,8 +75,8 @@ def online_recon_options(settings):
     events, inside prepare_batch.  None when the key is absent (the PNG tree), else {'precision', 'model'}.  The refusals of the
     key, each before anything is built: another config_option (only frame2recon reads a reconstruction next to a frame;
     recon2voxel stays on the PNG tree), DDD17 (its loader carries no raw events beside the frame), an unknown precision, a model
-    file that does not exist ('random' is accepted, as e2vid.run_reconstruction.load_model accepts it), and auto-HDR (its
-    window belongs to a sequence, not to a shuffled batch)."""
+    file that does not exist ('random' is accepted, as e2vid.run_reconstruction.load_model accepts it), auto-HDR (its
+    window belongs to a sequence, not to a shuffled batch), and e2vid_config.flip (the image would be rotated against the frame)."""
     import os
     src = getattr(settings, 'recon_sources', None)
     if src is None:
@@ -95,6 +95,9 @@ def online_recon_options(settings):
         raise ValueError(f"online_recon_model: E2VID checkpoint {model!r} not found ('random' builds seeded random weights)")
     if getattr(settings.e2vid_config, 'auto_hdr', False):
         raise ValueError(f"recon_sources: {ONLINE_E2VID} has no auto_hdr: its window is a property of a sequence, not of a batch")
+    if getattr(settings.e2vid_config, 'flip', False):
+        raise ValueError(f"recon_sources: {ONLINE_E2VID} cannot run with e2vid_config.flip: the reconstructed image would be rotated "
+                         "by 180 degrees against the teacher's frame (hot_pixels_file is served)")
     return {'precision': precision, 'model': model}
 
 

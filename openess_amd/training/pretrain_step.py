@@ -35,9 +35,13 @@ def _label_options(init):
                               stride-level logits); when given, front() calls it in place of online_teacher(frame).argmax(dim=1)
       switchable_train=False  if_switchable_train (pretrain_trainer.py:513-514, :556-557): while epoch_count >= switch_epoch the
       switch_epoch=5          dense-CLIP pseudo-labels are the argmax of the student's own logits; batch[3] and the online teacher
-                              (either form) are then unused.  epoch_count starts at 0; the trainer sets it every step."""
+                              (either form) are then unused.  epoch_count starts at 0; the trainer sets it every step.
+    and of K32:
+      e2vid_options=None      settings.e2vid_config (or any object with these attributes): its hot_pixels_file and flip reach the
+                              EventPreprocessor of the frame2voxel front end; nothing else of it is read."""
     @functools.wraps(init)
-    def with_options(self, *args, online_labels=None, switchable_train=False, switch_epoch=5, **kwargs):
+    def with_options(self, *args, online_labels=None, switchable_train=False, switch_epoch=5, e2vid_options=None, **kwargs):
+        self.e2vid_options = e2vid_options
         self.online_labels = online_labels
         self.switchable_train = bool(switchable_train)
         self.switch_epoch = int(switch_epoch)
@@ -72,7 +76,7 @@ class PretrainStep:
                  nr_temporal_bins=5, if_spatial_contrastive=False, if_dense_clip_supervision=True, superpixel_size=100,
                  lr=5e-4, weight_task_loss=1.0, task_loss=('dice', 'cross_entropy'), output_stride=32, device='cuda',
                  e2vid_config=None, text_embeddings=None, seed=1205, online_teacher=None, wavefront=False, precision='bf16'):
-        # keyword-only on top of these (see _label_options): online_labels=None, switchable_train=False, switch_epoch=5
+        # keyword-only on top of these (see _label_options): online_labels=None, switchable_train=False, switch_epoch=5, e2vid_options=None
         # precision: arithmetic of the whole step.  'bf16' (default) builds and runs exactly the bf16 step.  'fp32'
         # is the reference's arithmetic (use_amp: False in every YAML); what it cannot run is refused here, before any model is built
         if precision not in ('bf16', 'fp32'):
@@ -129,8 +133,10 @@ class PretrainStep:
         for m in self.models_dict.values():
             m.to(self.device)
         if config_option == 'frame2voxel':
+            # the event-side options of the front end's EventPreprocessor (hot_pixels_file, flip: DESIGN.md K32)
+            pre_opts = {k: getattr(self.e2vid_options, k) for k in ('hot_pixels_file', 'flip') if getattr(self.e2vid_options, k, None)}
             self.reconstructor = ImageReconstructor(self.front_end_sensor_b, self.input_height, self.input_width,
-                                                    nr_temporal_bins, self.device)
+                                                    nr_temporal_bins, self.device, SimpleNamespace(**pre_opts) if pre_opts else None)
             # wavefront schedule of the 20 recurrent sub-windows over one HIP stream per ConvLSTM level (e2vid/wavefront.py);
             # `self.wavefront = None` switches back to the single-stream order at any time (same results)
             self.wavefront = None
@@ -142,7 +148,7 @@ class PretrainStep:
                 # stage-2/3 trainers keep one, _supervised.buildModels): nothing the bf16 path reads is shared
                 self.task_backend.check_fp32(train=True)
                 self.reconstructor_fp32 = ImageReconstructor(self.front_end_sensor_b, self.input_height, self.input_width,
-                                                             nr_temporal_bins, self.device, SimpleNamespace(precision='fp32'))
+                                                             nr_temporal_bins, self.device, SimpleNamespace(precision='fp32', **pre_opts))
         self.task_loss = TaskLoss(losses=list(task_loss), gamma=2.0, num_classes=num_classes, ignore_index=255)
         self.nce_loss = NCELoss(temperature=0.07)
         # createOptimizerDict (pretrain_trainer.py:225-259)

@@ -77,7 +77,7 @@ class OpenESSPretrainModel(BaseTrainer):
                                  if_dense_clip_supervision=s.if_dense_clip_supervision, superpixel_size=s.superpixel_size,
                                  lr=s.lr_voxel, weight_task_loss=s.weight_task_loss, task_loss=tuple(s.task_loss),
                                  output_stride=s.output_stride, device=self.device, text_embeddings=text,
-                                 precision=self.train_precision)
+                                 precision=self.train_precision, e2vid_options=getattr(s, 'e2vid_config', None))
         self.models_dict = self.step.models_dict
         self.reconstructor = getattr(self.step, 'reconstructor', None)
 
