@@ -15,6 +15,8 @@ its fp32 forward; the student's step is not affected.
 that teacher's labels from MaskCLIP's refined output: prompt denoising and key smoothing.
 `recon_sources: 'online_e2vid'` there (with the optional `online_recon_precision` bf16 / fp32 and `online_recon_model`)
 reconstructs frame2recon's image from the sample's events on the GPU instead of reading `reconstructions/`.
+`e2vid_checkpoint`, `image_weights_path` and `require_pretrained: True` there name the frozen networks' pretrained weights and
+make a missing file an error; without them the trainers look for `path_to_model` and `weights/<image_weights>.pt`.
 Quirk reproduced on purpose: `if_linear_probing` is read from the `clip:` block only (settings.py:258), so the
 reference's config/linear_probe/** files, which put it at top level, dispatch to OpenESSModel.
 """
@@ -240,6 +242,18 @@ class Settings:
         # from `reconstructions/left/*.png`; None = the PNG tree.  `online_recon_precision` is the E2VID arithmetic there,
         # `online_recon_model` its checkpoint ('random': seeded random weights, as run_reconstruction.load_model accepts).  What
         # the key cannot serve is refused by the trainers (training/base_trainer_ov.py:online_recon_options).
+        # Pretrained weights of the frozen networks.  `e2vid_checkpoint`: the E2VID front end's checkpoint (absent:
+        # path_to_model, hard-coded above as in the reference's settings).  `image_weights_path`: the file the teacher loads
+        # `image_weights` from (absent: weights/<image_weights>.pt under the working directory).  `require_pretrained: True`:
+        # a named file that does not exist is an error instead of a warning and seeded random weights -- what a real run sets.
+        for key in ('e2vid_checkpoint', 'image_weights_path'):
+            v = c.get(key)
+            if v is not None and not (isinstance(v, str) and v):
+                raise ValueError(f"clip.{key} must be a path, got {v!r}")
+            setattr(self, key, v)
+        self.require_pretrained = c.get('require_pretrained', False)
+        if not isinstance(self.require_pretrained, bool):
+            raise ValueError(f"clip.require_pretrained must be True or False, got {self.require_pretrained!r}")
         self.recon_sources = c.get('recon_sources')
         self.online_recon_precision = c.get('online_recon_precision', 'bf16')
         self.online_recon_model = c.get('online_recon_model', self.path_to_model)

@@ -35,13 +35,8 @@ def load_model(path_to_model):
     if path_to_model == 'random':
         torch.manual_seed(1205)
         return E2VIDRecurrent(E2VID_LIGHTWEIGHT_CONFIG)
-    print('Loading model {}...'.format(path_to_model))
-    raw = torch.load(path_to_model, map_location='cpu')
-    assert raw['arch'] == 'E2VIDRecurrent', raw['arch']
-    cfg = raw['model'] if 'model' in raw else raw['config']['model']
-    model = E2VIDRecurrent(cfg)
-    model.load_state_dict(raw['state_dict'])
-    return model
+    from .utils.loading_utils import load_model as load_checkpoint       # the one checkpoint reader (returns (model, None))
+    return load_checkpoint(path_to_model)[0]
 
 
 def reconstruct(path_to_events, model, output_folder=None, window_size=None, fixed_duration=False, window_duration=33.33,

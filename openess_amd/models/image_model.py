@@ -24,13 +24,47 @@ class ResNetEncoder(ResNet):
         return super().load_state_dict(state_dict, **kwargs)
 
 
+# image_weights names -> (key of the state dict inside the file | None for the file itself, prefix kept and removed | None for
+# every key, prefix dropped although it starts with the kept one | None): the key rules of models/image_model.py:46-74
+IMAGE_WEIGHTS = {
+    'imagenet': (None, None, None),                 # plain torchvision ResNet-50 (fc.* dropped by ResNetEncoder.load_state_dict)
+    'dino': (None, None, None),
+    'moco_v1': ('state_dict', 'module.encoder_q.', 'module.encoder_q.fc'),
+    'moco_v2': ('state_dict', 'module.encoder_q.', 'module.encoder_q.fc'),
+    'moco_coco': ('state_dict', 'module.encoder_q.', 'module.encoder_q.fc'),
+    'swav': (None, 'module.', 'module.pro'),
+    'deepcluster_v2': (None, 'module.', 'module.pro'),
+    'obow': ('network', None, None),
+    'pixpro': ('model', 'module.encoder.', None),
+}
+
+
+def adapt_weights(architecture, path):
+    """The ResNet-50 state dict of the self-supervised checkpoint `path` in the layout `architecture` names (IMAGE_WEIGHTS), on
+    the CPU.  The file is local: the reference downloads it to weights/<architecture>.pt (image_model.py:38-42), nothing here
+    fetches anything."""
+    if architecture not in IMAGE_WEIGHTS:
+        raise ValueError(f"image_weights: {architecture!r} is none of {sorted(IMAGE_WEIGHTS)}")
+    inner, keep, drop = IMAGE_WEIGHTS[architecture]
+    weights = torch.load(path, map_location='cpu')
+    if inner is not None:
+        weights = weights[inner]
+    if keep is None:
+        return dict(weights)
+    # (the reference writes k.replace(keep, ""); on keys that start with `keep` and hold it once that is the prefix removed)
+    return {k.replace(keep, ""): v for k, v in weights.items()
+            if k.startswith(keep) and not (drop is not None and k.startswith(drop))}
+
+
 class DilationFeatureExtractor(nn.Module):
-    def __init__(self, image_weights=None, preprocessing=None):
+    def __init__(self, image_weights=None, preprocessing=None, weights_path=None):
+        """image_weights: None / '' / 'none' / 'random' load nothing; a name of IMAGE_WEIGHTS loads the frozen encoder (strict)
+        from `weights_path`, or -- None -- from weights/<image_weights>.pt under the working directory.  A file that does not
+        exist is an error here: training.pretrained.teacher_path is where a missing file is tolerated."""
         super().__init__()
-        if image_weights not in (None, '', 'none', 'random'):
-            # the reference downloads SSL checkpoints over HTTP (image_model.py:38-42); no network here
-            print(f"[openess_amd] image_weights='{image_weights}' not loaded (no network): load a state_dict instead")
         self.encoder = ResNetEncoder(block=Bottleneck, layers=[3, 4, 6, 3], replace_stride_with_dilation=[True, True, True])
+        if image_weights not in (None, '', 'none', 'random'):
+            self.encoder.load_state_dict(adapt_weights(image_weights, weights_path or f"weights/{image_weights}.pt"))
         for p in self.encoder.parameters():
             p.requires_grad = False
         self.decoder = nn.Sequential(HipConv2d(2048, 256, 1), nn.Upsample(scale_factor=4, mode="bilinear", align_corners=True))

@@ -13,6 +13,7 @@ from ..models.deeplabv3 import deeplabv3_resnet50
 from ..models.style_networks import SemSegE2VID
 from ..utils.loss_functions import TaskLoss
 from ..utils.optim import AdamW          # torch.optim.AdamW with its step on the multi-tensor HIP kernel
+from . import pretrained
 from .base_trainer_ov import BaseTrainer
 
 
@@ -43,7 +44,23 @@ class SupervisedTrainer(BaseTrainer):
                 raise NotImplementedError("train_precision: fp32 needs the frozen E2VID front end (unfrozen_e2vid: False): E2VID "
                                           "has no fp32 backward (5x5 stride-2 convolutions, ConvLSTM)")
             SemSegE2VID.check_fp32_config(settings.skip_connect_task_type, False)
+        # pretrained weights: a front-end checkpoint that cannot serve this run, or -- under
+        # require_pretrained: True -- a named file that does not exist, is refused here, before anything is built (quietly:
+        # buildModels resolves the same source again and is the one that warns or reports)
+        self._e2vid_source(settings, logger=None)
+        if settings.config_option == 'frame2recon':
+            pretrained.backbone_path(settings.pretrained_backbone, bool(getattr(settings, 'require_pretrained', False)))
         super().__init__(settings, train)
+
+    def _e2vid_source(self, settings, logger):
+        """(path, (config, state_dict) | None) of the frozen front end named by the YAML (`e2vid_checkpoint`, else path_to_model);
+        (None, None) for a config_option without one."""
+        if settings.config_option not in ('recon2voxel', 'frame2voxel'):
+            return None, None
+        key, path = pretrained.e2vid_path(settings)
+        fp32 = 'fp32' in (getattr(self, 'eval_precision', 'bf16'), getattr(self, 'train_precision', 'bf16'))
+        return path, pretrained.e2vid_source(path, key, settings.nr_temporal_bins_b, fp32,
+                                             bool(getattr(settings, 'require_pretrained', False)), logger)
 
     def backend_kwargs(self):
         return {}
@@ -78,7 +95,12 @@ class SupervisedTrainer(BaseTrainer):
         except OSError:
             text_path = ''
         if s.config_option in ('recon2voxel', 'frame2voxel'):
-            self.front_end_sensor_b = E2VIDRecurrent(E2VID_LIGHTWEIGHT_CONFIG)
+            # the front end named by the YAML (finetune_trainer.py: load_model(self.settings.path_to_model)): built from the
+            # checkpoint's own config, or -- no file -- E2VID_lightweight from the seed as before
+            ckpt_path, ckpt = self._e2vid_source(s, logger=s.logger)
+            self.front_end_sensor_b = E2VIDRecurrent(ckpt[0] if ckpt is not None else E2VID_LIGHTWEIGHT_CONFIG)
+            if ckpt is not None:
+                pretrained.load_e2vid(self.front_end_sensor_b, ckpt, ckpt_path, s.logger)
             if not s.unfrozen_e2vid:
                 for p in self.front_end_sensor_b.parameters():
                     p.requires_grad = False

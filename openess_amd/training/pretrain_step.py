@@ -11,6 +11,7 @@ from types import SimpleNamespace
 import torch
 
 from .. import hip
+from . import pretrained
 from ..e2vid.image_reconstructor import ImageReconstructor
 from ..e2vid.model.model import E2VID_LIGHTWEIGHT_CONFIG, E2VIDRecurrent
 from ..models.deeplabv3 import deeplabv3_resnet50
@@ -38,9 +39,22 @@ def _label_options(init):
                               (either form) are then unused.  epoch_count starts at 0; the trainer sets it every step.
     and of K32:
       e2vid_options=None      settings.e2vid_config (or any object with these attributes): its hot_pixels_file and flip reach the
-                              EventPreprocessor of the frame2voxel front end; nothing else of it is read."""
+                              EventPreprocessor of the frame2voxel front end; nothing else of it is read.
+    and of K33 (pretrained weights, training/pretrained.py; every default is the seeded network, no file is looked for):
+      e2vid_checkpoint=None   reference-format E2VID checkpoint of the frame2voxel front end: the model is built from the file's
+                              own config (it replaces e2vid_config) and its state dict is loaded
+      image_weights=None      name of the teacher's self-supervised weights (image_model.IMAGE_WEIGHTS), loaded from
+      image_weights_path=None   this file, or from weights/<image_weights>.pt under the working directory
+      pretrained_backbone=''  {'model_recon': state_dict} file of the frame2recon student (pre_trained_backbone of the YAML)
+      require_pretrained=False  a named file that does not exist: False = one warning, seeded weights; True = FileNotFoundError
+      logger=None             where the warnings and the "loaded" lines go (None: the openess_amd.pretrained logger)"""
     @functools.wraps(init)
-    def with_options(self, *args, online_labels=None, switchable_train=False, switch_epoch=5, e2vid_options=None, **kwargs):
+    def with_options(self, *args, online_labels=None, switchable_train=False, switch_epoch=5, e2vid_options=None,
+                     e2vid_checkpoint=None, image_weights=None, image_weights_path=None, pretrained_backbone='',
+                     require_pretrained=False, logger=None, **kwargs):
+        self.pretrained_options = SimpleNamespace(e2vid_checkpoint=e2vid_checkpoint, image_weights=image_weights,
+                                                  image_weights_path=image_weights_path, pretrained_backbone=pretrained_backbone,
+                                                  require=bool(require_pretrained), logger=logger or pretrained._DEFAULT_LOGGER)
         self.e2vid_options = e2vid_options
         self.online_labels = online_labels
         self.switchable_train = bool(switchable_train)
@@ -76,7 +90,8 @@ class PretrainStep:
                  nr_temporal_bins=5, if_spatial_contrastive=False, if_dense_clip_supervision=True, superpixel_size=100,
                  lr=5e-4, weight_task_loss=1.0, task_loss=('dice', 'cross_entropy'), output_stride=32, device='cuda',
                  e2vid_config=None, text_embeddings=None, seed=1205, online_teacher=None, wavefront=False, precision='bf16'):
-        # keyword-only on top of these (see _label_options): online_labels=None, switchable_train=False, switch_epoch=5, e2vid_options=None
+        # keyword-only on top of these (see _label_options): online_labels=None, switchable_train=False, switch_epoch=5, e2vid_options=None,
+        # e2vid_checkpoint=None, image_weights=None, image_weights_path=None, pretrained_backbone='', require_pretrained=False, logger=None
         # precision: arithmetic of the whole step.  'bf16' (default) builds and runs exactly the bf16 step.  'fp32'
         # is the reference's arithmetic (use_amp: False in every YAML); what it cannot run is refused here, before any model is built
         if precision not in ('bf16', 'fp32'):
@@ -93,6 +108,17 @@ class PretrainStep:
             SemSegE2VID.check_fp32_config('concat', 'pooled', train=True)
         self.precision = precision
         self.config_option = config_option
+        # pretrained weights (K33): every named file is resolved, and what cannot be loaded refused, before any model is built
+        po = self.pretrained_options
+        e2vid = teacher_file = None
+        backbone_file = ''
+        if config_option == 'frame2voxel':
+            e2vid = pretrained.e2vid_source(po.e2vid_checkpoint, 'e2vid_checkpoint', nr_temporal_bins, precision == 'fp32',
+                                            po.require, po.logger)
+        elif config_option == 'frame2recon':
+            backbone_file = pretrained.backbone_path(po.pretrained_backbone, po.require, po.logger)
+        if config_option in ('frame2voxel', 'frame2recon'):
+            teacher_file = pretrained.teacher_path(po.image_weights, po.image_weights_path, po.require, po.logger)
         # a frozen MaskCLIP tower as ONLINE teacher: pseudo-labels = argmax of its logits on the frame, computed inside
         # the step, instead of the offline `pl_*_rgb` PNGs (README.md:295).  None = the reference's behaviour (labels from the batch).
         self.online_teacher = online_teacher
@@ -105,7 +131,11 @@ class PretrainStep:
         torch.manual_seed(seed)
         self.models_dict = {}
         if config_option == 'frame2voxel':
-            self.front_end_sensor_b = E2VIDRecurrent(e2vid_config or E2VID_LIGHTWEIGHT_CONFIG)
+            # (a checkpoint brings its own config; construction comes first either way, so the seeded stream that initialises
+            # the trainable decoder below is the same with and without a file)
+            self.front_end_sensor_b = E2VIDRecurrent(e2vid[0] if e2vid is not None else (e2vid_config or E2VID_LIGHTWEIGHT_CONFIG))
+            if e2vid is not None:
+                pretrained.load_e2vid(self.front_end_sensor_b, e2vid, po.e2vid_checkpoint, po.logger)
             for p in self.front_end_sensor_b.parameters():
                 p.requires_grad = False
             self.front_end_sensor_b.eval()
@@ -119,12 +149,19 @@ class PretrainStep:
             self.models_dict['back_end'] = self.task_backend
         elif config_option == 'frame2recon':
             self.model_recon = deeplabv3_resnet50(num_classes=num_classes, text_embeddings_path='',
-                                                  output_stride=output_stride, pretrained_backbone='')
+                                                  output_stride=output_stride, pretrained_backbone=backbone_file)
+            if backbone_file:
+                pretrained.report_loaded(po.logger, 'the DeepLabv3 student', backbone_file, self.model_recon.state_dict())
             self.models_dict['model_recon'] = self.model_recon
             self.model_recon.lazy_feats = bool(if_spatial_contrastive and self.pooled_student_features)
         else:
             raise NotImplementedError(config_option)
-        self.model_frame = DilationFeatureExtractor(image_weights=None)
+        if teacher_file is None:
+            self.model_frame = DilationFeatureExtractor(image_weights=None)
+        else:
+            self.model_frame = DilationFeatureExtractor(image_weights=po.image_weights, weights_path=teacher_file)
+            pretrained.report_loaded(po.logger, f"the image teacher's {po.image_weights!r} encoder", teacher_file,
+                                     self.model_frame.encoder.state_dict())
         self.model_frame.lazy_features = bool(if_spatial_contrastive and self.pooled_teacher_features)
         self.models_dict['model_frame'] = self.model_frame
         if text_embeddings is not None:

@@ -27,7 +27,33 @@ class OpenESSPretrainModel(BaseTrainer):
             if getattr(settings, 'unfrozen_e2vid', False):
                 raise NotImplementedError("train_precision: fp32 needs the frozen E2VID front end (unfrozen_e2vid: False): E2VID "
                                           "has no fp32 backward (5x5 stride-2 convolutions, ConvLSTM)")
+        # pretrained weights: a checkpoint that cannot serve this run, or -- under require_pretrained: True -- a
+        # named file that does not exist, is refused here too, before anything is built; quietly: PretrainStep resolves the
+        # same sources again when it builds the networks and is the one that warns or reports
+        self._pretrained_kwargs(settings, logger=None, check=True)
         super().__init__(settings, train)
+
+    def _pretrained_kwargs(self, settings, logger, check=False):
+        """PretrainStep's keywords of the frozen networks' weights, from the YAML: the E2VID checkpoint (`e2vid_checkpoint`, else
+        path_to_model), the teacher's `image_weights` (+ `image_weights_path`), the frame2recon student's
+        `pre_trained_backbone`.  check=True resolves them the way the step will and returns nothing."""
+        from . import pretrained
+        s = settings
+        require = bool(getattr(s, 'require_pretrained', False))
+        kw = dict(image_weights=getattr(s, 'image_weights', None), image_weights_path=getattr(s, 'image_weights_path', None),
+                  require_pretrained=require, logger=logger)
+        if s.config_option == 'frame2voxel':
+            kw['e2vid_checkpoint'] = pretrained.e2vid_path(s)[1]
+        elif s.config_option == 'frame2recon':
+            kw['pretrained_backbone'] = s.pretrained_backbone or ''
+        if check:
+            if 'e2vid_checkpoint' in kw:
+                pretrained.e2vid_source(kw['e2vid_checkpoint'], pretrained.e2vid_path(s)[0], s.nr_temporal_bins_b,
+                                        self.train_precision == 'fp32', require)
+            pretrained.backbone_path(kw.get('pretrained_backbone', ''), require)
+            pretrained.teacher_path(kw['image_weights'], kw['image_weights_path'], require)
+            return None
+        return kw
 
     def init_fn(self):
         """pretrain_trainer.py:87-89: models, then optimisers, then the loss objects."""
@@ -77,7 +103,8 @@ class OpenESSPretrainModel(BaseTrainer):
                                  if_dense_clip_supervision=s.if_dense_clip_supervision, superpixel_size=s.superpixel_size,
                                  lr=s.lr_voxel, weight_task_loss=s.weight_task_loss, task_loss=tuple(s.task_loss),
                                  output_stride=s.output_stride, device=self.device, text_embeddings=text,
-                                 precision=self.train_precision, e2vid_options=getattr(s, 'e2vid_config', None))
+                                 precision=self.train_precision, e2vid_options=getattr(s, 'e2vid_config', None),
+                                 **self._pretrained_kwargs(s, logger=s.logger))
         self.models_dict = self.step.models_dict
         self.reconstructor = getattr(self.step, 'reconstructor', None)
 
