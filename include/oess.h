@@ -708,6 +708,32 @@ int oess_upsampled_l1_bwd_f32(const float* a, long long a_pix_stride, const floa
                               float* grad_b, long long gb_pix_stride, oess_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Cosine distance of two bilinearly resampled maps on a common output grid WITHOUT a full-resolution tensor (K34; the SAM
+ * distillation loss of training/pretrain_trainer.py:519-529):  loss = mean over B Ho Wo of (1 - cos_p),
+ *   cos_p = a_p . t_p / (max(|a_p|, eps) max(|t_p|, eps))                       (the rule of oess_cosine_mean_*)
+ *   a: student map [B x h x w x C] NHWC, fp32 or bf16 (a_is_bf16), pixel stride >= C (elements), upsampled to Ho x Wo by the index
+ *      rule and blend of oess_resize_bilinear_nhwc_fwd, either align_corners mode.
+ *   t: teacher map [B x ht x wt x C] NHWC fp32, pixel stride >= C, resized to a VIRTUAL Mh x Mw grid (align_corners = 0, two taps, no
+ *      antialiasing: ht, wt may be larger or smaller than Mh, Mw) of which only the top-left Ho x Wo is read.
+ *   fwd: workspace = oess_upsampled_cosine_workspace_bytes(...) bytes, 8-byte aligned (one double per workgroup, summed in a fixed
+ *        order by one block); loss: device scalar; planes: NULL, or oess_upsampled_cosine_planes_floats(B, Ho, Wo) floats that
+ *        receive two scalars per output pixel for the backward.
+ *   bwd: grad_a only (the teacher is data), [B x h x w x C] in a's dtype, pixel stride >= C; reads the forward's planes and
+ *        recomputes both interpolated vectors.  Gather form, no atomics: bit-repeatable.  Below the clamp (|a_p| <= eps) the norm
+ *        carries no gradient, as in oess_cosine_mean_bwd.
+ * Accepted: C % 4 == 0, C <= 1024, Ho >= h, Wo >= w, ht, wt >= 1, Mh >= Ho, Mw >= Wo, h or w of 1.  Anything else -- null pointers,
+ * strides below C, non-positive sizes, a workspace that is too small or misaligned -- is OESS_EINVAL before anything is launched.
+ * ------------------------------------------------------------------------------------------ */
+size_t oess_upsampled_cosine_workspace_bytes(int B, int h, int w, int C, int Ho, int Wo);   /* 0: geometry not accepted */
+size_t oess_upsampled_cosine_planes_floats(int B, int Ho, int Wo);
+int oess_upsampled_cosine_fwd(const void* a, int a_is_bf16, long long a_pix_stride, const float* t, long long t_pix_stride, int B, int h,
+                              int w, int C, int Ho, int Wo, int align_corners, int ht, int wt, int Mh, int Mw, float eps, void* workspace,
+                              size_t workspace_bytes, float* planes, float* loss, oess_stream_t stream);
+int oess_upsampled_cosine_bwd(const void* a, int a_is_bf16, long long a_pix_stride, const float* t, long long t_pix_stride, int B, int h,
+                              int w, int C, int Ho, int Wo, int align_corners, int ht, int wt, int Mh, int Mw, const float* planes,
+                              const float* grad_out, void* grad_a, long long ga_pix_stride, oess_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * Superpixel mean of a bilinearly upsampled map through its pooling matrix (models/deeplabv3.py:184 F.interpolate(feats, size=
  * input, bilinear, align_corners=False) followed by training/pretrain_trainer.py:445-465 on it): k[s] = (sum_q M[s][q] y[q]) /
  * (n[s] + 1e-6) with M[s][q] = the summed bilinear weights of superpixel row s's pixels on low-resolution pixel q.

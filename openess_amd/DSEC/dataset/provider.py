@@ -45,7 +45,8 @@ class DatasetProvider:
     def __init__(self, dataset_path, mode='train', event_representation='voxel_grid', nr_events_data=5, delta_t_per_data=20,
                  nr_events_window=-1, nr_bins_per_data=5, require_paired_data=False, normalize_event=False, separate_pol=False,
                  semseg_num_classes=11, augmentation=False, fixed_duration=False, resize=False, config_option='', pl_sources='',
-                 superpixel_sources='', skip_ratio=1, if_sam_distillation=False, device_png=False, recon_sources=None):
+                 superpixel_sources='', skip_ratio=1, if_sam_distillation=False, device_png=False, recon_sources=None,
+                 sam_feature_sources=''):
         dataset_path = Path(dataset_path)
         train_path, val_path = dataset_path / 'train', dataset_path / 'test'
         assert dataset_path.is_dir(), str(dataset_path)
@@ -60,7 +61,8 @@ class DatasetProvider:
                     for child in path.iterdir() if any(k in str(child) for k in names)]
         if mode == 'train':
             self.train_dataset = DSECConcat(sequences(train_path, TRAIN_SEQUENCES, 'train', superpixel_sources=superpixel_sources,
-                                                      skip_ratio=skip_ratio, if_sam_distillation=if_sam_distillation))
+                                                      skip_ratio=skip_ratio, if_sam_distillation=if_sam_distillation,
+                                                      sam_feature_sources=sam_feature_sources))
             self.train_dataset.require_paired_data = require_paired_data
         elif mode == 'val':
             self.val_dataset = DSECConcat(sequences(val_path, VAL_SEQUENCES, 'val', superpixel_sources='', skip_ratio=2,

@@ -46,7 +46,12 @@ class Sequence(Dataset):
                  nr_events_per_data=100000, nr_bins_per_data=5, require_paired_data=False, normalize_event=False,
                  separate_pol=False, semseg_num_classes=11, augmentation=False, fixed_duration=False, remove_time_window=250,
                  resize=False, config_option='', pl_sources='', superpixel_sources='', skip_ratio=1, if_sam_distillation=False,
-                 device_png=False, recon_sources=None):
+                 device_png=False, recon_sources=None, sam_feature_sources=''):
+        # sam_feature_sources (extension): folder of the per-frame SAM features `<stem>.npy` ([256, 64, 64], float16 or
+        # float32), found by the path rule of the superpixel maps; '' = the reference's ones.  Means nothing without the loss.
+        if sam_feature_sources and not if_sam_distillation:
+            raise ValueError("sam_feature_sources is set but if_sam_distillation is not True: nothing would read the features")
+        self.sam_feature_sources = sam_feature_sources or ''
         # recon_sources 'online_e2vid' (extension): with config_option frame2recon no file under reconstructions/ is
         # opened; slot 2 of the tuple carries the sample's raw events and the recon's augmentation draws, and the trainer
         # reconstructs and augments the image on the GPU (BaseTrainer.prepare_batch).  None = the PNG tree, as the reference.
@@ -200,6 +205,15 @@ class Sequence(Dataset):
             return dict(m, flip=not m['flip'])
         return torch.flip(m, [1])
 
+    def _sam_feat(self, file_path):
+        path = file_path.replace('semantic/', self.sam_feature_sources + '/').replace('11classes/', '').replace('.png', '.npy')
+        if not Path(path).is_file():
+            raise FileNotFoundError(f"sam_feature_sources: no SAM feature file '{path}'")
+        feat = np.load(path, allow_pickle=False)
+        if feat.shape != (256, 64, 64) or feat.dtype not in (np.float16, np.float32):
+            raise ValueError(f"sam_feature_sources: '{path}' holds {feat.dtype} {feat.shape}, expected float16 / float32 (256, 64, 64)")
+        return torch.from_numpy(feat.astype(np.float32, copy=False))
+
     def __getitem__(self, index):
         label_path = self.label_pathstrings[index]
         label_tensor = self._map(label_path) if self.device_png else torch.from_numpy(self.get_label(label_path)).long()
@@ -221,7 +235,7 @@ class Sequence(Dataset):
             superpixel = self._map(sp_path) if self.device_png else torch.tensor(_io.load_png(sp_path)).long()
         else:
             superpixel = self._ones_map(label_tensor)
-        sam_feat = torch.ones((256, 64, 64))
+        sam_feat = self._sam_feat(file_path) if self.sam_feature_sources else torch.ones((256, 64, 64))
         opt = self.config_option
         if opt not in ('recon2voxel', 'frame2voxel', 'frame2recon', 'recon_only'):
             return None                                                            # the reference falls off the end too

@@ -147,6 +147,12 @@ SIGNATURES = {
     "oess_upsampled_l1_fwd_f32": (c_int, [c_vp, c_ll, c_vp, c_ll, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_vp, c_sz, c_vp, c_vp]),
     "oess_upsampled_l1_bwd_f32": (c_int, [c_vp, c_ll, c_vp, c_ll, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_vp, c_vp, c_ll, c_vp,
                                           c_ll, c_vp]),
+    "oess_upsampled_cosine_workspace_bytes": (c_sz, [c_int, c_int, c_int, c_int, c_int, c_int]),
+    "oess_upsampled_cosine_planes_floats": (c_sz, [c_int, c_int, c_int]),
+    "oess_upsampled_cosine_fwd": (c_int, [c_vp, c_int, c_ll, c_vp, c_ll, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
+                                          c_int, c_int, c_f, c_vp, c_sz, c_vp, c_vp, c_vp]),
+    "oess_upsampled_cosine_bwd": (c_int, [c_vp, c_int, c_ll, c_vp, c_ll, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
+                                          c_int, c_int, c_vp, c_vp, c_vp, c_ll, c_vp]),
     "oess_pool_matrix_bytes": (c_sz, [c_int, c_int, c_int, c_int]),
     "oess_pool_matrix_build": (c_int, [c_vp, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_vp, c_sz, c_vp]),
     "oess_pool_matrix_fwd": (c_int, [c_vp, c_vp, c_ll, c_int, c_int, c_int, c_int, c_int, c_int, c_vp, c_vp, c_vp]),

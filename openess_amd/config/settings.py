@@ -183,6 +183,12 @@ class Settings:
             # `online_slic_connectivity: True` appends SLIC's connectivity pass (skimage's default, what the reference's files
             # were written with); only with `superpixel_sources: 'online_slic'`, which the trainers check
             self.online_slic_connectivity = bool(c.get('online_slic_connectivity', False))
+            # `sam_feature_sources: '<folder>'` (DSEC only): <folder>/<stem>.npy next to the frames holds the
+            # sample's SAM image-encoder features [256, 64, 64]; absent or '': the reference's ones (sequence_ov.py:351).  Only with
+            # `if_sam_distillation: True`, which the pre-training trainer checks
+            self.sam_feature_sources = c.get('sam_feature_sources', '')
+            if not isinstance(self.sam_feature_sources, str):
+                raise ValueError(f"clip.sam_feature_sources must be a folder name, got {self.sam_feature_sources!r}")
         if c.get('if_finetuning') is not None:
             self.if_finetuning = c['if_finetuning']
             for key in ('load_pretrained_weights', 'pretrained_file', 'if_switchable_train'):

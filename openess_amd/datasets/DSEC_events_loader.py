@@ -12,7 +12,7 @@ def DSECEvents(dsec_dir, nr_events_data=1, delta_t_per_data=50, nr_events_window
                task='segmentation', event_representation='voxel_grid', nr_bins_per_data=5, require_paired_data=False,
                separate_pol=False, normalize_event=False, semseg_num_classes=11, fixed_duration=False, resize=False,
                config_option='', pl_sources='', superpixel_sources='', skip_ratio=1, if_sam_distillation=False,
-               device_png=False, recon_sources=None):
+               device_png=False, recon_sources=None, sam_feature_sources=''):
     dsec_dir = Path(dsec_dir)
     assert dsec_dir.is_dir()
     provider = DatasetProvider(dsec_dir, mode, event_representation=event_representation, nr_events_data=nr_events_data,
@@ -22,7 +22,7 @@ def DSECEvents(dsec_dir, nr_events_data=1, delta_t_per_data=50, nr_events_window
                                augmentation=augmentation, fixed_duration=fixed_duration, resize=resize, config_option=config_option,
                                pl_sources=pl_sources, superpixel_sources=superpixel_sources, skip_ratio=skip_ratio,
                                if_sam_distillation=if_sam_distillation, device_png=device_png,
-                               recon_sources=recon_sources)
+                               recon_sources=recon_sources, sam_feature_sources=sam_feature_sources)
     return provider.get_train_dataset() if mode == 'train' else provider.get_val_dataset()
 
 
@@ -35,7 +35,8 @@ def build_from_settings(s):
               recon_sources=getattr(s, 'recon_sources', None))
     train = DSECEvents(augmentation=s.data_augmentation_train, mode='train', require_paired_data=s.require_paired_data_train_b,
                        superpixel_sources=dataset_superpixel_sources(s), skip_ratio=s.skip_ratio,
-                       if_sam_distillation=getattr(s, 'if_sam_distillation', False), **kw)
+                       if_sam_distillation=getattr(s, 'if_sam_distillation', False),
+                       sam_feature_sources=getattr(s, 'sam_feature_sources', ''), **kw)
     val = DSECEvents(augmentation=False, mode='val', require_paired_data=s.require_paired_data_val_b, superpixel_sources='',
                      skip_ratio=2, if_sam_distillation=False, **kw)
     return train, val

@@ -2008,6 +2008,78 @@ def upsampled_l1_mean(a, b):
     return _UpsampledL1Mean.apply(a.x, b.x, a.size[0], a.size[1], int(a.align_corners))
 
 
+class _UpsampledCosine(torch.autograd.Function):
+    """mean(1 - cos(up(a), resize(t)[:Ho, :Wo])) of a low-resolution student map and an fp32 teacher map as ONE node (DESIGN.md
+    K34): saves the two small maps and two fp32 scalars per output pixel, forms no full-resolution tensor in forward or backward.
+    The teacher is data: no gradient."""
+
+    @staticmethod
+    def forward(ctx, a, t, Ho, Wo, align, Mh, Mw, eps):
+        lib = _lib.load()
+        an, tn = _nhwc_any(a), _nhwc_any(t)
+        (B, h, w, C), (ht, wt) = an.shape, tn.shape[1:3]
+        ws = _workspace(lib.oess_upsampled_cosine_workspace_bytes(B, h, w, C, Ho, Wo), a.device, tag="upsampled_cosine")
+        planes = None
+        if ctx.needs_input_grad[0]:
+            planes = torch.empty(lib.oess_upsampled_cosine_planes_floats(B, Ho, Wo), dtype=torch.float32, device=a.device)
+        loss = torch.empty(1, dtype=torch.float32, device=a.device)
+        _lib.check(lib.oess_upsampled_cosine_fwd(_ptr(an), int(an.dtype == torch.bfloat16), _pix_stride(an), _ptr(tn), _pix_stride(tn),
+                                                 B, h, w, C, Ho, Wo, align, ht, wt, Mh, Mw, eps, _ptr(ws), ws.numel(), _ptr(planes),
+                                                 _ptr(loss), _stream()), "oess_upsampled_cosine_fwd")
+        if planes is not None:
+            ctx.save_for_backward(an, tn, planes)
+        ctx.meta = (Ho, Wo, align, Mh, Mw)
+        return loss[0]
+
+    @staticmethod
+    def backward(ctx, g):
+        if not ctx.needs_input_grad[0]:
+            return (None,) * 8
+        lib = _lib.load()
+        an, tn, planes = ctx.saved_tensors
+        (B, h, w, C), (ht, wt), (Ho, Wo, align, Mh, Mw) = an.shape, tn.shape[1:3], ctx.meta
+        ga = torch.empty((B, h, w, C), dtype=an.dtype, device=an.device)
+        gdev = g.reshape(1).float().contiguous()
+        _lib.check(lib.oess_upsampled_cosine_bwd(_ptr(an), int(an.dtype == torch.bfloat16), _pix_stride(an), _ptr(tn), _pix_stride(tn),
+                                                 B, h, w, C, Ho, Wo, align, ht, wt, Mh, Mw, _ptr(planes), _ptr(gdev), _ptr(ga), C,
+                                                 _stream()), "oess_upsampled_cosine_bwd")
+        return (ga.permute(0, 3, 1, 2),) + (None,) * 7
+
+
+def sam_distill_supported(C, in_hw, size):
+    """Geometry of the fused node's entries (include/oess.h, oess_upsampled_cosine_*); the teacher side takes any map."""
+    return C % 4 == 0 and C <= 1024 and size[0] >= in_hw[0] and size[1] >= in_hw[1]
+
+
+def sam_distill_loss(sam, feat, eps=1e-8):
+    """The SAM distillation loss of the frame2recon pre-training step (training/pretrain_trainer.py:519-529):
+        M = max(H, W);  sam_up = F.interpolate(sam, size=(M, M), mode='bilinear', align_corners=False)[:, :, :H, :]
+        loss = mean(1 - F.cosine_similarity(sam_up, feat, dim=1))
+    sam: [B, C, hs, ws] fp32 (data, no gradient is returned for it).  feat: [B, C, H, W] fp32 / bf16, a tensor or a
+    hip.UpsampledFeature.  H > W is refused: the reference crops rows only, so its cosine_similarity cannot broadcast there.
+    An UpsampledFeature whose map the entries accept runs one fused node on the two small maps (nothing of the
+    full-resolution size is allocated, forward or backward).  A plain tensor, or geometry the entries refuse, goes through
+    bilinear_resize, the crop and cosine_mean_loss in the reference's order, in fp32 as the reference computes it."""
+    lazy = isinstance(feat, UpsampledFeature)
+    fx = feat.x if lazy else feat
+    if not torch.is_tensor(sam) or not torch.is_tensor(fx) or not sam.is_cuda or not fx.is_cuda:
+        raise ValueError("sam_distill_loss needs CUDA/HIP tensors (no CPU fallback)")
+    if sam.ndim != 4 or fx.ndim != 4 or sam.dtype != torch.float32 or fx.dtype not in (torch.float32, torch.bfloat16):
+        raise ValueError("sam_distill_loss: sam must be 4-D float32 and feat 4-D float32 / bfloat16")
+    if sam.shape[:2] != fx.shape[:2]:
+        raise ValueError(f"sam_distill_loss: batch / channel counts differ: sam {tuple(sam.shape)}, feat {tuple(feat.shape)}")
+    H, W = int(feat.shape[2]), int(feat.shape[3])
+    if H > W:
+        raise ValueError(f"sam_distill_loss: H = {H} > W = {W}: the reference crops the rows of the (M, M) map only")
+    M = max(H, W)
+    sam = sam.detach()
+    if lazy and sam_distill_supported(fx.shape[1], fx.shape[2:], feat.size):
+        return _UpsampledCosine.apply(fx, sam, H, W, int(feat.align_corners), M, M, float(eps))
+    full = bilinear_resize(fx.float(), size=feat.size, align_corners=feat.align_corners) if lazy else feat.float()
+    sam_up = bilinear_resize(sam, size=(M, M), align_corners=False)[:, :, :H, :]
+    return cosine_mean_loss(sam_up, full, eps)
+
+
 def bilinear_l2norm_train(x, scale=4):
     """Differentiable form of bilinear_l2norm (normalisation on) for a channels_last bf16 tensor with C % 64 == 0."""
     _need_gpu(x)

@@ -484,7 +484,9 @@ class BaseTrainer(object):
         if self.online_recon:
             kw['recon_sources'] = ONLINE_E2VID          # slot 2 then carries raw events, no reconstructions/ file is opened
         train = builder(augmentation=augmentation, mode='train', require_paired_data=require_paired_data_train,
-                        superpixel_sources=superpixel_sources, skip_ratio=skip_ratio, if_sam_distillation=if_sam_distillation, **kw)
+                        superpixel_sources=superpixel_sources, skip_ratio=skip_ratio, if_sam_distillation=if_sam_distillation,
+                        **({'sam_feature_sources': self.settings.sam_feature_sources}
+                           if getattr(self.settings, 'sam_feature_sources', '') else {}), **kw)
         val = builder(augmentation=False, mode='val', require_paired_data=require_paired_data_val, superpixel_sources='', skip_ratio=2,
                       if_sam_distillation=False, **kw)                                              # :137-157: never augmented, every 2nd sample
         return train, val

@@ -47,11 +47,15 @@ def _label_options(init):
       image_weights_path=None   this file, or from weights/<image_weights>.pt under the working directory
       pretrained_backbone=''  {'model_recon': state_dict} file of the frame2recon student (pre_trained_backbone of the YAML)
       require_pretrained=False  a named file that does not exist: False = one warning, seeded weights; True = FileNotFoundError
-      logger=None             where the warnings and the "loaded" lines go (None: the openess_amd.pretrained logger)"""
+      logger=None             where the warnings and the "loaded" lines go (None: the openess_amd.pretrained logger)
+    and of K34:
+      sam_distillation=False  if_sam_distillation (pretrain_trainer.py:481-482, :519-529): frame2recon adds the cosine distance
+                              between the batch's SAM features and the student's upsampled feature (hip.sam_distill_loss) under the
+                              key 'sam_distillation_loss'; task_train_step then needs sam_feat.  Refused with frame2voxel."""
     @functools.wraps(init)
     def with_options(self, *args, online_labels=None, switchable_train=False, switch_epoch=5, e2vid_options=None,
                      e2vid_checkpoint=None, image_weights=None, image_weights_path=None, pretrained_backbone='',
-                     require_pretrained=False, logger=None, **kwargs):
+                     require_pretrained=False, logger=None, sam_distillation=False, **kwargs):
         self.pretrained_options = SimpleNamespace(e2vid_checkpoint=e2vid_checkpoint, image_weights=image_weights,
                                                   image_weights_path=image_weights_path, pretrained_backbone=pretrained_backbone,
                                                   require=bool(require_pretrained), logger=logger or pretrained._DEFAULT_LOGGER)
@@ -60,8 +64,20 @@ def _label_options(init):
         self.switchable_train = bool(switchable_train)
         self.switch_epoch = int(switch_epoch)
         self.epoch_count = 0
+        self.sam_distillation = bool(sam_distillation)
         init(self, *args, **kwargs)
     return with_options
+
+
+def refuse_sam_distillation(config_option, dataset_name=None):
+    """What if_sam_distillation cannot run, refused before any model is built (PretrainStep and OpenESSPretrainModel)."""
+    if config_option != 'frame2recon':
+        raise NotImplementedError(f"if_sam_distillation with config_option {config_option!r}: only frame2recon computes the loss. The "
+                                  "reference's trainEpoch reads out[0]['sam_distillation_loss'] (pretrain_trainer.py:300), which its "
+                                  "frame2voxel branch never writes: the run ends in a KeyError there")
+    if dataset_name is not None and dataset_name != 'DSEC_events':
+        raise NotImplementedError(f"if_sam_distillation with dataset {dataset_name!r}: its loader has no SAM feature slot "
+                                  "(ddd17_events_loader.py returns six items); only DSEC_events carries sam_feat")
 
 
 class PretrainStep:
@@ -91,7 +107,8 @@ class PretrainStep:
                  lr=5e-4, weight_task_loss=1.0, task_loss=('dice', 'cross_entropy'), output_stride=32, device='cuda',
                  e2vid_config=None, text_embeddings=None, seed=1205, online_teacher=None, wavefront=False, precision='bf16'):
         # keyword-only on top of these (see _label_options): online_labels=None, switchable_train=False, switch_epoch=5, e2vid_options=None,
-        # e2vid_checkpoint=None, image_weights=None, image_weights_path=None, pretrained_backbone='', require_pretrained=False, logger=None
+        # e2vid_checkpoint=None, image_weights=None, image_weights_path=None, pretrained_backbone='', require_pretrained=False, logger=None,
+        # sam_distillation=False
         # precision: arithmetic of the whole step.  'bf16' (default) builds and runs exactly the bf16 step.  'fp32'
         # is the reference's arithmetic (use_amp: False in every YAML); what it cannot run is refused here, before any model is built
         if precision not in ('bf16', 'fp32'):
@@ -106,6 +123,8 @@ class PretrainStep:
                 raise NotImplementedError("precision='fp32' has no wavefront schedule: fp32 E2VID runs on one stream "
                                           "(the per-level streams are a bf16-path option)")
             SemSegE2VID.check_fp32_config('concat', 'pooled', train=True)
+        if self.sam_distillation:
+            refuse_sam_distillation(config_option)
         self.precision = precision
         self.config_option = config_option
         # pretrained weights (K33): every named file is resolved, and what cannot be loaded refused, before any model is built
@@ -153,7 +172,8 @@ class PretrainStep:
             if backbone_file:
                 pretrained.report_loaded(po.logger, 'the DeepLabv3 student', backbone_file, self.model_recon.state_dict())
             self.models_dict['model_recon'] = self.model_recon
-            self.model_recon.lazy_feats = bool(if_spatial_contrastive and self.pooled_student_features)
+            # the pooling and the SAM loss read the same stride-level map (hip.UpsampledFeature); autograd sums their gradients
+            self.model_recon.lazy_feats = bool(self.pooled_student_features and (if_spatial_contrastive or self.sam_distillation))
         else:
             raise NotImplementedError(config_option)
         if teacher_file is None:
@@ -321,10 +341,13 @@ class PretrainStep:
     def _pool(self, feat, superpixels, S):
         return hip.superpixel_pool(feat, superpixels, self.superpixel_size, S=S)
 
-    def task_train_step(self, batch, front=None):
+    def task_train_step(self, batch, front=None, sam_feat=None):
         """batch: (event | frame, label, frame | recon, pl, superpixels) already on the device.
         `superpixel_rows` (optional 6th item) = max offset id + 1 computed by the loader on the host.
-        front: the handle of front(batch) when the caller pipelines the steps; None = the frozen half is enqueued here."""
+        front: the handle of front(batch) when the caller pipelines the steps; None = the frozen half is enqueued here.
+        sam_feat: [B, 256, hs, ws] fp32 on the device, the batch's SAM features; read (and required) with sam_distillation only."""
+        if self.sam_distillation and sam_feat is None:
+            raise ValueError("sam_distillation=True: task_train_step needs sam_feat (slot 5 of the prepared batch)")
         losses = {}
         t_loss = 0.
         self._set_modes()
@@ -367,13 +390,17 @@ class PretrainStep:
                 loss_dense = self.task_loss(logits_recon, pl) * self.weight_task_loss
                 losses['dense_clip_loss'] = loss_dense.detach()
                 t_loss = t_loss + loss_dense
+            if self.sam_distillation:                                           # :519-529
+                loss_sam = hip.sam_distill_loss(sam_feat, feat_recon)
+                losses['sam_distillation_loss'] = loss_sam.detach()
+                t_loss = t_loss + loss_sam
         return t_loss, losses, {}
 
     # ------------------------------------------------------------------ pretrain_trainer.py:324-361
-    def train_step(self, batch):
+    def train_step(self, batch, sam_feat=None):
         for opt in self.optimizers_dict.values():
             opt.zero_grad()
-        t_loss, losses, outputs = self.task_train_step(batch)
+        t_loss, losses, outputs = self.task_train_step(batch, sam_feat=sam_feat)
         t_loss.backward()
         for opt in self.optimizers_dict.values():
             opt.step()

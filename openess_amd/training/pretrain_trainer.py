@@ -5,7 +5,7 @@ import functools
 import torch
 
 from .base_trainer_ov import BaseTrainer, online_maskclip_refine
-from .pretrain_step import PretrainStep
+from .pretrain_step import PretrainStep, refuse_sam_distillation
 
 
 class OpenESSPretrainModel(BaseTrainer):
@@ -27,6 +27,12 @@ class OpenESSPretrainModel(BaseTrainer):
             if getattr(settings, 'unfrozen_e2vid', False):
                 raise NotImplementedError("train_precision: fp32 needs the frozen E2VID front end (unfrozen_e2vid: False): E2VID "
                                           "has no fp32 backward (5x5 stride-2 convolutions, ConvLSTM)")
+        # `if_sam_distillation: True` runs with frame2recon on DSEC; `sam_feature_sources` names the folder of the
+        # per-frame SAM features and means nothing without the loss
+        if getattr(settings, 'if_sam_distillation', False):
+            refuse_sam_distillation(settings.config_option, settings.dataset_name_b)
+        elif getattr(settings, 'sam_feature_sources', ''):
+            raise ValueError("sam_feature_sources is set but if_sam_distillation is not True: nothing would read the features")
         # pretrained weights: a checkpoint that cannot serve this run, or -- under require_pretrained: True -- a
         # named file that does not exist, is refused here too, before anything is built; quietly: PretrainStep resolves the
         # same sources again when it builds the networks and is the one that warns or reports
@@ -97,6 +103,7 @@ class OpenESSPretrainModel(BaseTrainer):
         self._switch_logged = False
         self.step = PretrainStep(config_option=s.config_option, online_teacher=online, online_labels=online_labels,
                                  switchable_train=bool(getattr(s, 'if_switchable_train', False)),
+                                 sam_distillation=bool(getattr(s, 'if_sam_distillation', False)),
                                  num_classes=s.semseg_num_classes, img_size=tuple(s.img_size_b),
                                  nr_events_data=s.nr_events_data_b, nr_temporal_bins=s.nr_temporal_bins_b,
                                  if_spatial_contrastive=s.if_spatial_contrastive,
@@ -121,8 +128,8 @@ class OpenESSPretrainModel(BaseTrainer):
                 for g in self.optimizers_dict[key].param_groups:
                     g['lr'] = lr
 
-    def task_train_step(self, batch, front=None):
-        return self.step.task_train_step(batch, front=front)
+    def task_train_step(self, batch, front=None, sam_feat=None):
+        return self.step.task_train_step(batch, front=front, sam_feat=sam_feat)
 
     def front_step(self, batch):
         """Frozen half of the step (teacher encoder, recurrent E2VID encoder) for `batch`, enqueued on its own HIP streams: trainEpoch
@@ -143,7 +150,8 @@ class OpenESSPretrainModel(BaseTrainer):
         for opt in self.optimizers_dict.values():
             opt.zero_grad()
         self.grad_reducer.prepare()          # N > 1: gradients accumulate straight into the all-reduce buckets
-        t_loss, losses, outputs = self.task_train_step((batch[0], batch[1], batch[2], batch[3], batch[4], batch[-1]), front=front)
+        t_loss, losses, outputs = self.task_train_step((batch[0], batch[1], batch[2], batch[3], batch[4], batch[-1]), front=front,
+                                                       sam_feat=batch[5] if self.step.sam_distillation else None)
         t_loss.backward()
         self.grad_reducer()
         for opt in self.optimizers_dict.values():
