@@ -583,6 +583,24 @@ int oess_argmax_labels(const void* logits, int is_bf16, long long pix_stride, in
                        int align_corners, int64_t* out, oess_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Segmentation maps from logits without the full-resolution tensor (K35, the inference path): per output pixel the class label,
+ * the softmax probability of that class and a colour.
+ *   logits, pix_stride, B, K, h, w, H, W, align_corners: as oess_argmax_labels; the class values v_k are that entry's values (raw
+ *     at the input size, otherwise the fp32 blend in its association) and the label is its label.  1 <= K <= 255.
+ *   conf  (fp32 [B x H x W] or null): 1 / sum_k exp(v_k - v_max) in fp32, one walk over K (running maximum and sum).
+ *   labels (u8 [B x H x W] or null): the label, or ignore_label where conf < min_conf (false for a NaN conf; min_conf = 0 ignores
+ *     nothing).  K <= ignore_label <= 255: it is not a class.
+ *   rgb   (u8 [B x H x W x 3] or null): c = palette[label] (palette: u8 [K x 3] on the device), (0, 0, 0) for ignore_label;
+ *     with grey (u8 [B x H x W] or null) every channel is (alpha256 * c + (256 - alpha256) * grey + 128) >> 8, 0 <= alpha256 <= 256.
+ *   An output that is null is not computed; two calls give the same bits (one lane owns a pixel, no atomics).
+ * OESS_EINVAL, nothing launched, outputs untouched: logits null, all three outputs null, rgb without palette, K outside 1 ... 255,
+ * ignore_label outside K ... 255, alpha256 outside 0 ... 256, a NaN or negative min_conf, a non-positive size, pix_stride < K,
+ * B * H or B * h above 2^31 - 1, or an element count that overflows 64-bit byte offsets. */
+int oess_segment_render(const void* logits, int is_bf16, long long pix_stride, int B, int K, int h, int w, int H, int W,
+                        int align_corners, const uint8_t* palette, const uint8_t* grey, int alpha256, float min_conf,
+                        int ignore_label, uint8_t* labels, float* conf, uint8_t* rgb, oess_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * MaskCLIP ViT-B/16 image tower (models/maskclip_model.py:448-541 TransformerEncoderLayer, :545-851 VisionTransformer):
  * the non-GEMM pieces.  The linear layers (patch embedding, in_proj, out_proj, FFN, proj) run on oess_conv2d_fwd_bf16 as
  * 1x1 / 16x16 convolutions over the token axis (bias, residual and GELU fused in the epilogue).

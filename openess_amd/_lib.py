@@ -103,6 +103,8 @@ SIGNATURES = {
     "oess_resize_bilinear_nhwc_bwd": (c_int, [c_vp, c_ll, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_vp, c_sz,
                                               c_vp, c_ll, c_vp]),
     "oess_argmax_labels": (c_int, [c_vp, c_int, c_ll, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_vp, c_vp]),
+    "oess_segment_render": (c_int, [c_vp, c_int, c_ll, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_vp, c_vp, c_int, c_f, c_int,
+                                    c_vp, c_vp, c_vp, c_vp]),
     "oess_l2norm_nhwc_fwd": (c_int, [c_vp, c_ll, c_i64, c_int, c_int, c_f, c_vp, c_ll, c_vp, c_vp]),
     "oess_l2norm_nhwc_bwd": (c_int, [c_vp, c_ll, c_vp, c_ll, c_vp, c_i64, c_int, c_int, c_f, c_vp, c_ll, c_vp]),
     "oess_zero_insert_nhwc_bf16": (c_int, [c_vp, c_ll, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_vp, c_ll, c_vp]),

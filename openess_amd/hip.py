@@ -2161,6 +2161,69 @@ def argmax_labels(logits, size=None, align_corners=False, out=None):
     return out
 
 
+SEGMENT_RENDER_OUTPUTS = ('labels', 'conf', 'rgb')
+
+
+def segment_render(logits, size=None, align_corners=False, palette=None, background=None, alpha=0.5, min_conf=0.0, ignore_label=255,
+                   want=SEGMENT_RENDER_OUTPUTS):
+    """Segmentation maps of logical B x K x h x w fp32 / bf16 logits at `size` (None: the input size) without the full-resolution
+    logit tensor: a dict of the tensors named in `want`,
+      'labels'  u8 [B, H, W]: argmax_labels' label, or ignore_label where the confidence is below min_conf,
+      'conf'    fp32 [B, H, W]: the softmax probability of the winning class,
+      'rgb'     u8 [B, H, W, 3]: palette[label] (palette: u8 [K, 3] on the device; black for ignore_label), blended over
+                `background` (u8 [B, H, W]) with weight alpha, in integers: (a * c + (256 - a) * grey + 128) >> 8, a = round(256 alpha).
+    No autograd."""
+    if not torch.is_tensor(logits) or not logits.is_cuda:
+        raise ValueError("segment_render needs a CUDA/HIP tensor (no CPU fallback)")
+    if logits.dtype not in (torch.float32, torch.bfloat16) or logits.ndim != 4:
+        raise ValueError("segment_render expects 4-D float32 / bfloat16 logits [B, K, h, w]")
+    B, K, h, w = logits.shape
+    if not 1 <= K <= 255:
+        raise ValueError(f"segment_render handles 1 <= K <= 255 classes, got {K}")
+    if min(B, h, w) < 1:
+        raise ValueError(f"segment_render needs a non-empty batch, got {tuple(logits.shape)}")
+    want = (want,) if isinstance(want, str) else tuple(want)
+    if not want or len(set(want)) != len(want) or any(name not in SEGMENT_RENDER_OUTPUTS for name in want):
+        raise ValueError(f"want must name at least one of {SEGMENT_RENDER_OUTPUTS}, each once, got {want!r}")
+    H, W = (h, w) if size is None else (int(size[0]), int(size[1]))
+    if H < 1 or W < 1:
+        raise ValueError(f"size must be positive, got {(H, W)}")
+    ignore_label = int(ignore_label)
+    if not K <= ignore_label <= 255:
+        raise ValueError(f"ignore_label must lie in K ... 255 (it is not a class), got {ignore_label} for K = {K}")
+    min_conf = float(min_conf)
+    if not min_conf >= 0.0:
+        raise ValueError(f"min_conf must be a number >= 0, got {min_conf}")
+    alpha = float(alpha)
+    if not 0.0 <= alpha <= 1.0:
+        raise ValueError(f"alpha must lie in 0 ... 1, got {alpha}")
+    if 'rgb' in want:
+        if (not torch.is_tensor(palette) or palette.dtype != torch.uint8 or tuple(palette.shape) != (K, 3)
+                or palette.device != logits.device or not palette.is_contiguous()):
+            raise ValueError(f"palette must be a contiguous uint8 tensor of shape {(K, 3)} on {logits.device}")
+        if background is not None and (not torch.is_tensor(background) or background.dtype != torch.uint8
+                                       or tuple(background.shape) != (B, H, W) or background.device != logits.device
+                                       or not background.is_contiguous()):
+            raise ValueError(f"background must be a contiguous uint8 tensor of shape {(B, H, W)} on {logits.device}")
+    else:
+        palette = background = None
+    out = {}
+    if 'labels' in want:
+        out['labels'] = torch.empty((B, H, W), dtype=torch.uint8, device=logits.device)
+    if 'conf' in want:
+        out['conf'] = torch.empty((B, H, W), dtype=torch.float32, device=logits.device)
+    if 'rgb' in want:
+        out['rgb'] = torch.empty((B, H, W, 3), dtype=torch.uint8, device=logits.device)
+    xn = _nhwc_any(logits.detach())
+    _lib.check(_lib.load().oess_segment_render(_ptr(xn), int(logits.dtype == torch.bfloat16), _pix_stride(xn), B, K, h, w, H, W,
+                                               int(bool(align_corners)), _ptr(palette), _ptr(background), int(round(alpha * 256)),
+                                               min_conf, ignore_label, _ptr(out.get('labels')), _ptr(out.get('conf')),
+                                               _ptr(out.get('rgb')), _stream()), "oess_segment_render")
+    for t in out.values():
+        _bump(t)
+    return out
+
+
 class _L2Normalize(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, eps):

@@ -286,6 +286,26 @@ class deeplabv3_resnet50(nn.Module):
         self.check_fp32()
         return self._forward_fp32('forward_fp32', x, False, True)
 
+    @torch.no_grad()
+    def logits_at_stride(self, x, precision='bf16'):
+        """The eval-mode network up to the classifier's output, fp32 [B, K, H / stride, W / stride]: what forward() ('bf16') and
+        forward_fp32() ('fp32') resize to the input size, from their own pieces and so with their bits.  Neither the
+        full-resolution logits nor the 256-channel feature map at the input size are formed: hip.segment_render /
+        hip.argmax_labels with size=x.shape[-2:] blend these logits exactly as the resize does.
+        Refused: a train-mode module (check_fp32's rule, in both precisions), and a linear probe, which sits behind the resize."""
+        if precision not in ('bf16', 'fp32'):
+            raise ValueError(f"precision must be 'bf16' or 'fp32', got {precision!r}")
+        if self.if_linear_probing:
+            raise NotImplementedError("logits_at_stride: the linear probe acts on the full-resolution logits (behind the resize); "
+                                      "use forward / forward_fp32 and the same-size render")
+        self.check_fp32()
+        if precision == 'fp32':
+            if x.dtype != torch.float32 or x.ndim != 4:
+                raise ValueError("logits_at_stride takes a float32 [B, 3, H, W] image batch")
+            return self.classifier.forward_fp32(self.backbone.forward_fp32(x))[0]
+        with engine.defer_bn_counters():
+            return self.classifier(self.backbone(x))[0].float()
+
     def _forward_fp32(self, name, x, train, want_feats):
         """What forward_fp32 (`name`, train=False) and forward_fp32_train share: the input check, the network in its mode, the two
         resizes to the input size and the linear probe."""
