@@ -601,6 +601,31 @@ int oess_segment_render(const void* logits, int is_bf16, long long pix_stride, i
                         int ignore_label, uint8_t* labels, float* conf, uint8_t* rgb, oess_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Open-vocabulary rendering (K36): K classes over a vocabulary of P >= K names; class k owns the contiguous channels
+ * class_offsets[k] ... class_offsets[k + 1] - 1 (int32 [K + 1] on the device: 0 first, strictly increasing, P last -- the caller's
+ * part; the kernels clamp every entry to 0 ... P, so a wrong list gives wrong classes and no read outside the P channels).
+ * The class value c_k is torch.amax over the group's name values (a NaN member makes it NaN); label, conf, threshold and rgb are
+ * oess_segment_render's over the K class values.  1 <= K <= 255, K <= P <= 1024.
+ *   oess_segment_render_grouped: name values = oess_segment_render's values of the P-channel logits.  Singleton groups give
+ *     oess_segment_render's bits.  OESS_EINVAL as oess_segment_render, and for null class_offsets, P outside K ... 1024 and
+ *     pix_stride < P.
+ *   oess_head_render: name values from the map in front of a linear head, without any [B x P x H x W] tensor:
+ *     v_p = fmaf(w[p][C-1], x[C-1], ... fmaf(w[p][0], x[0], bias_p) ...), ascending c from the bias (0 when bias is null), bf16 taps
+ *     widened first.  x: NHWC [B x H x W x C] fp32 or bf16 with a pixel stride, 1 <= C <= 64; weight fp32 [P x C], bias fp32 [P] or
+ *     null, both dense on the device.  class_offsets null: one name per class (P == K).  The weights and the bias sit in LDS:
+ *     OESS_EINVAL as well when P > oess_head_render_max_names(C) = 48 KB / (4 (C + 1)), and for pix_stride < C.
+ * Adding these entries left OESS_ABI_VERSION unchanged. */
+int oess_segment_render_grouped(const void* logits, int is_bf16, long long pix_stride, int B, int K, int P, int h, int w, int H, int W,
+                                int align_corners, const int32_t* class_offsets, const uint8_t* palette, const uint8_t* grey,
+                                int alpha256, float min_conf, int ignore_label, uint8_t* labels, float* conf, uint8_t* rgb,
+                                oess_stream_t stream);
+size_t oess_head_render_max_names(int C);
+int oess_head_render(const void* x, int is_bf16, long long pix_stride, int B, int C, int H, int W, const float* weight,
+                     const float* bias, int K, int P, const int32_t* class_offsets, const uint8_t* palette, const uint8_t* grey,
+                     int alpha256, float min_conf, int ignore_label, uint8_t* labels, float* conf, uint8_t* rgb,
+                     oess_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * MaskCLIP ViT-B/16 image tower (models/maskclip_model.py:448-541 TransformerEncoderLayer, :545-851 VisionTransformer):
  * the non-GEMM pieces.  The linear layers (patch embedding, in_proj, out_proj, FFN, proj) run on oess_conv2d_fwd_bf16 as
  * 1x1 / 16x16 convolutions over the token axis (bias, residual and GELU fused in the epilogue).

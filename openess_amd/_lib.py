@@ -105,6 +105,11 @@ SIGNATURES = {
     "oess_argmax_labels": (c_int, [c_vp, c_int, c_ll, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_vp, c_vp]),
     "oess_segment_render": (c_int, [c_vp, c_int, c_ll, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_vp, c_vp, c_int, c_f, c_int,
                                     c_vp, c_vp, c_vp, c_vp]),
+    "oess_segment_render_grouped": (c_int, [c_vp, c_int, c_ll, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_vp, c_vp,
+                                            c_vp, c_int, c_f, c_int, c_vp, c_vp, c_vp, c_vp]),
+    "oess_head_render_max_names": (c_sz, [c_int]),
+    "oess_head_render": (c_int, [c_vp, c_int, c_ll, c_int, c_int, c_int, c_int, c_vp, c_vp, c_int, c_int, c_vp, c_vp, c_vp, c_int, c_f,
+                                 c_int, c_vp, c_vp, c_vp, c_vp]),
     "oess_l2norm_nhwc_fwd": (c_int, [c_vp, c_ll, c_i64, c_int, c_int, c_f, c_vp, c_ll, c_vp, c_vp]),
     "oess_l2norm_nhwc_bwd": (c_int, [c_vp, c_ll, c_vp, c_ll, c_vp, c_i64, c_int, c_int, c_f, c_vp, c_ll, c_vp]),
     "oess_zero_insert_nhwc_bf16": (c_int, [c_vp, c_ll, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_vp, c_ll, c_vp]),

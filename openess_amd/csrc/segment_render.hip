@@ -21,69 +21,24 @@
 #include "oess.h"
 #include "oess_common.h"
 #include "bilinear_axis.h"
+#include "render_common.h"
 
 namespace {
 using namespace oess;
-constexpr int THREADS = 256;
+using namespace oess::render;              // Render, tap, take, emit, flush_chunk: render_common.h, shared with vocab_render.hip
 constexpr size_t LDS_BUDGET = 48 * 1024;     // two fp32 source rows; with the 2 KB of staging below the 64 KB a launch gets
-constexpr int MAX_K = 255;
 
 enum { RAW = 0, TAPS_LDS = 1, TAPS_GLOBAL = 2 };
-
-struct Render {
-    const uint8_t* palette;       // [K][3] or null (then rgb is null)
-    const uint8_t* grey;          // [B][H][W] or null
-    uint8_t* labels;              // [B][H][W] or null
-    float* conf;                  // [B][H][W] or null
-    uint8_t* rgb;                 // [B][H][W][3] or null
-    int alpha256, ignore_label;
-    float min_conf;
-};
-
-template <bool BF16>
-__device__ __forceinline__ float tap(const void* __restrict__ p, int64_t off) {
-    return BF16 ? bf16_to_f32(reinterpret_cast<const uint16_t*>(p)[off]) : reinterpret_cast<const float*>(p)[off];
-}
-
-// One class value into the running (maximum, index, sum of exp(v - maximum)).  The maximum moves under torch.argmax's order
-// (label_ops.hip take()): v replaces best when it is larger, or when it is the first NaN.
-__device__ __forceinline__ void take(float v, int k, float& best, int& idx, float& sum) {
-    if (v > best || (v != v && best == best)) {
-        sum = sum * __expf(best - v) + 1.f;
-        best = v; idx = k;
-    } else {
-        sum = sum + __expf(v - best);
-    }
-}
-
-// n staged bytes, stage[phase ... phase + n), to g (phase = g & 3): every dword that lies inside the range is one aligned
-// store; the at most two ragged dwords at the ends are written byte by byte (their other bytes belong to someone else).
-__device__ __forceinline__ void flush_bytes(const uint8_t* stage, uint8_t* g, int phase, int n) {
-    uint8_t* g0 = g - phase;                                               // 4-byte aligned
-    const int end = phase + n;
-    for (int lo = threadIdx.x * 4; lo < end; lo += THREADS * 4) {
-        if (lo >= phase && lo + 4 <= end) {
-            *reinterpret_cast<uint32_t*>(g0 + lo) = *reinterpret_cast<const uint32_t*>(stage + lo);
-        } else {
-            const int a = lo < phase ? phase : lo, b = lo + 4 < end ? lo + 4 : end;
-            for (int j = a; j < b; ++j) g0[j] = stage[j];
-        }
-    }
-}
 
 template <bool BF16, int MODE>
 __global__ __launch_bounds__(THREADS) void segment_render_kernel(const void* __restrict__ in, int64_t ips, int K, Axis ay, Axis ax,
                                                                  Render r) {
     extern __shared__ __attribute__((aligned(16))) float rows[];            // TAPS_LDS: [2][ax.in][K]
-    __shared__ __attribute__((aligned(4))) uint8_t lab_stage[THREADS + 4];
-    __shared__ __attribute__((aligned(4))) uint8_t rgb_stage[3 * THREADS + 4];
-    __shared__ uint8_t pal[3 * MAX_K + 3];                                  // the palette, then (0, 0, 0) for ignore_label
+    __shared__ Stage st;
     const int oy = blockIdx.x % ay.out;
     const int64_t b = blockIdx.x / ay.out;
     const int64_t opix = (b * ay.out + oy) * (int64_t)ax.out;               // first output pixel of this row
-    if (r.rgb) {
-        for (int j = threadIdx.x; j < 3 * K + 3; j += THREADS) pal[j] = j < 3 * K ? r.palette[j] : (uint8_t)0;
-    }
+    load_palette(st, r, K);
     int y0 = 0, y1 = 0; float wy = 0.f;
     if constexpr (MODE != RAW) src_index(ay, oy, y0, y1, wy);
     const float hy = 1.f - wy;
@@ -128,27 +83,9 @@ __global__ __launch_bounds__(THREADS) void segment_render_kernel(const void* __r
                     if (k == 0) best = v; else take(v, k, best, idx, sum);
                 }
             }
-            const float conf = 1.f / sum;
-            int label = idx;
-            if (conf < r.min_conf) label = r.ignore_label;                  // false for a NaN confidence: the label stays
-            if (r.conf) r.conf[opix + ox] = conf;
-            if (r.labels) lab_stage[lphase + threadIdx.x] = (uint8_t)label;
-            if (r.rgb) {
-                const uint8_t* c = pal + 3 * (label == r.ignore_label ? K : label);
-                int c0 = c[0], c1 = c[1], c2 = c[2];
-                if (r.grey) {
-                    const int g = (256 - r.alpha256) * (int)r.grey[opix + ox] + 128;
-                    c0 = (r.alpha256 * c0 + g) >> 8; c1 = (r.alpha256 * c1 + g) >> 8; c2 = (r.alpha256 * c2 + g) >> 8;
-                }
-                uint8_t* s = rgb_stage + cphase + 3 * threadIdx.x;
-                s[0] = (uint8_t)c0; s[1] = (uint8_t)c1; s[2] = (uint8_t)c2;
-            }
+            emit(st, r, K, opix + ox, lphase, cphase, idx, sum);
         }
-        __syncthreads();
-        const int n = ax.out - base < THREADS ? ax.out - base : THREADS;
-        if (r.labels) flush_bytes(lab_stage, r.labels + opix + base, lphase, n);
-        if (r.rgb) flush_bytes(rgb_stage, r.rgb + 3 * (opix + base), cphase, 3 * n);
-        __syncthreads();                                                    // the next chunk overwrites the staging
+        flush_chunk(st, r, opix + base, lphase, cphase, ax.out - base < THREADS ? ax.out - base : THREADS);
     }
 }
 

@@ -2164,28 +2164,23 @@ def argmax_labels(logits, size=None, align_corners=False, out=None):
 SEGMENT_RENDER_OUTPUTS = ('labels', 'conf', 'rgb')
 
 
-def segment_render(logits, size=None, align_corners=False, palette=None, background=None, alpha=0.5, min_conf=0.0, ignore_label=255,
-                   want=SEGMENT_RENDER_OUTPUTS):
-    """Segmentation maps of logical B x K x h x w fp32 / bf16 logits at `size` (None: the input size) without the full-resolution
-    logit tensor (DESIGN.md K35): a dict of the tensors named in `want`,
-      'labels'  u8 [B, H, W]: argmax_labels' label, or ignore_label where the confidence is below min_conf,
-      'conf'    fp32 [B, H, W]: the softmax probability of the winning class,
-      'rgb'     u8 [B, H, W, 3]: palette[label] (palette: u8 [K, 3] on the device; black for ignore_label), blended over
-                `background` (u8 [B, H, W]) with weight alpha, in integers: (a * c + (256 - a) * grey + 128) >> 8, a = round(256 alpha).
-    No autograd."""
-    if not torch.is_tensor(logits) or not logits.is_cuda:
-        raise ValueError("segment_render needs a CUDA/HIP tensor (no CPU fallback)")
-    if logits.dtype not in (torch.float32, torch.bfloat16) or logits.ndim != 4:
-        raise ValueError("segment_render expects 4-D float32 / bfloat16 logits [B, K, h, w]")
-    B, K, h, w = logits.shape
+def _class_offsets(what, class_offsets, P, device):
+    """(int32 [K + 1] on the device, K) of a list / tensor of offsets checked on the host: 0 first, strictly increasing, P last"""
+    offs = class_offsets.tolist() if torch.is_tensor(class_offsets) else list(class_offsets)
+    if (len(offs) < 2 or any(not isinstance(o, int) or isinstance(o, bool) for o in offs) or offs[0] != 0
+            or any(b <= a for a, b in zip(offs, offs[1:])) or offs[-1] != P):
+        raise ValueError(f"{what}: class_offsets must start at 0, increase strictly and end at the channel count {P}, got {offs!r}")
+    K = len(offs) - 1
     if not 1 <= K <= 255:
-        raise ValueError(f"segment_render handles 1 <= K <= 255 classes, got {K}")
-    if min(B, h, w) < 1:
-        raise ValueError(f"segment_render needs a non-empty batch, got {tuple(logits.shape)}")
+        raise ValueError(f"{what} handles 1 <= K <= 255 classes, got {K}")
+    return h2d_async(torch.tensor(offs, dtype=torch.int32), device), K
+
+
+def _render_args(what, like, B, K, H, W, palette, background, alpha, min_conf, ignore_label, want):
+    """The checks every render shares; returns (want, palette, background, alpha256, min_conf, ignore_label, outputs)."""
     want = (want,) if isinstance(want, str) else tuple(want)
     if not want or len(set(want)) != len(want) or any(name not in SEGMENT_RENDER_OUTPUTS for name in want):
         raise ValueError(f"want must name at least one of {SEGMENT_RENDER_OUTPUTS}, each once, got {want!r}")
-    H, W = (h, w) if size is None else (int(size[0]), int(size[1]))
     if H < 1 or W < 1:
         raise ValueError(f"size must be positive, got {(H, W)}")
     ignore_label = int(ignore_label)
@@ -2199,26 +2194,116 @@ def segment_render(logits, size=None, align_corners=False, palette=None, backgro
         raise ValueError(f"alpha must lie in 0 ... 1, got {alpha}")
     if 'rgb' in want:
         if (not torch.is_tensor(palette) or palette.dtype != torch.uint8 or tuple(palette.shape) != (K, 3)
-                or palette.device != logits.device or not palette.is_contiguous()):
-            raise ValueError(f"palette must be a contiguous uint8 tensor of shape {(K, 3)} on {logits.device}")
+                or palette.device != like.device or not palette.is_contiguous()):
+            raise ValueError(f"palette must be a contiguous uint8 tensor of shape {(K, 3)} on {like.device}")
         if background is not None and (not torch.is_tensor(background) or background.dtype != torch.uint8
-                                       or tuple(background.shape) != (B, H, W) or background.device != logits.device
+                                       or tuple(background.shape) != (B, H, W) or background.device != like.device
                                        or not background.is_contiguous()):
-            raise ValueError(f"background must be a contiguous uint8 tensor of shape {(B, H, W)} on {logits.device}")
+            raise ValueError(f"background must be a contiguous uint8 tensor of shape {(B, H, W)} on {like.device}")
     else:
         palette = background = None
     out = {}
     if 'labels' in want:
-        out['labels'] = torch.empty((B, H, W), dtype=torch.uint8, device=logits.device)
+        out['labels'] = torch.empty((B, H, W), dtype=torch.uint8, device=like.device)
     if 'conf' in want:
-        out['conf'] = torch.empty((B, H, W), dtype=torch.float32, device=logits.device)
+        out['conf'] = torch.empty((B, H, W), dtype=torch.float32, device=like.device)
     if 'rgb' in want:
-        out['rgb'] = torch.empty((B, H, W, 3), dtype=torch.uint8, device=logits.device)
+        out['rgb'] = torch.empty((B, H, W, 3), dtype=torch.uint8, device=like.device)
+    return palette, background, int(round(alpha * 256)), min_conf, ignore_label, out
+
+
+def segment_render(logits, size=None, align_corners=False, palette=None, background=None, alpha=0.5, min_conf=0.0, ignore_label=255,
+                   want=SEGMENT_RENDER_OUTPUTS, class_offsets=None):
+    """Segmentation maps of logical B x K x h x w fp32 / bf16 logits at `size` (None: the input size) without the full-resolution
+    logit tensor (DESIGN.md K35): a dict of the tensors named in `want`,
+      'labels'  u8 [B, H, W]: argmax_labels' label, or ignore_label where the confidence is below min_conf,
+      'conf'    fp32 [B, H, W]: the softmax probability of the winning class,
+      'rgb'     u8 [B, H, W, 3]: palette[label] (palette: u8 [K, 3] on the device; black for ignore_label), blended over
+                `background` (u8 [B, H, W]) with weight alpha, in integers: (a * c + (256 - a) * grey + 128) >> 8, a = round(256 alpha).
+    class_offsets (K36): a list / tensor of K + 1 offsets (0 first, strictly increasing, the channel count P <= 1024 last): the
+    logits are those of P NAMES, class k owns the channels class_offsets[k] ... class_offsets[k + 1] - 1 and its value is
+    torch.amax over them; labels, conf and rgb are over the K class values.  Singleton groups give the bits of class_offsets=None.
+    No autograd."""
+    if not torch.is_tensor(logits) or not logits.is_cuda:
+        raise ValueError("segment_render needs a CUDA/HIP tensor (no CPU fallback)")
+    if logits.dtype not in (torch.float32, torch.bfloat16) or logits.ndim != 4:
+        raise ValueError("segment_render expects 4-D float32 / bfloat16 logits [B, K, h, w]")
+    B, P, h, w = logits.shape
+    offs = None
+    if class_offsets is None:
+        K = P
+        if not 1 <= K <= 255:
+            raise ValueError(f"segment_render handles 1 <= K <= 255 classes, got {K}")
+    else:
+        if not 1 <= P <= 1024:
+            raise ValueError(f"segment_render handles 1 <= P <= 1024 names, got {P}")
+        offs, K = _class_offsets("segment_render", class_offsets, P, logits.device)
+    if min(B, h, w) < 1:
+        raise ValueError(f"segment_render needs a non-empty batch, got {tuple(logits.shape)}")
+    H, W = (h, w) if size is None else (int(size[0]), int(size[1]))
+    palette, background, alpha256, min_conf, ignore_label, out = _render_args("segment_render", logits, B, K, H, W, palette, background,
+                                                                              alpha, min_conf, ignore_label, want)
     xn = _nhwc_any(logits.detach())
-    _lib.check(_lib.load().oess_segment_render(_ptr(xn), int(logits.dtype == torch.bfloat16), _pix_stride(xn), B, K, h, w, H, W,
-                                               int(bool(align_corners)), _ptr(palette), _ptr(background), int(round(alpha * 256)),
-                                               min_conf, ignore_label, _ptr(out.get('labels')), _ptr(out.get('conf')),
-                                               _ptr(out.get('rgb')), _stream()), "oess_segment_render")
+    if offs is None:
+        _lib.check(_lib.load().oess_segment_render(_ptr(xn), int(logits.dtype == torch.bfloat16), _pix_stride(xn), B, K, h, w, H, W,
+                                                   int(bool(align_corners)), _ptr(palette), _ptr(background), alpha256,
+                                                   min_conf, ignore_label, _ptr(out.get('labels')), _ptr(out.get('conf')),
+                                                   _ptr(out.get('rgb')), _stream()), "oess_segment_render")
+    else:
+        _lib.check(_lib.load().oess_segment_render_grouped(_ptr(xn), int(logits.dtype == torch.bfloat16), _pix_stride(xn), B, K, P, h, w,
+                                                           H, W, int(bool(align_corners)), _ptr(offs), _ptr(palette),
+                                                           _ptr(background), alpha256, min_conf, ignore_label,
+                                                           _ptr(out.get('labels')), _ptr(out.get('conf')), _ptr(out.get('rgb')),
+                                                           _stream()), "oess_segment_render_grouped")
+    for t in out.values():
+        _bump(t)
+    return out
+
+
+def vocab_render_max_names(C):
+    """The largest name count P hip.vocab_render takes at C channels: its weights [P, C] and bias [P] sit in 48 KB of LDS."""
+    return int(_lib.load().oess_head_render_max_names(int(C)))
+
+
+def vocab_render(x, weight, bias=None, class_offsets=None, palette=None, background=None, alpha=0.5, min_conf=0.0, ignore_label=255,
+                 want=SEGMENT_RENDER_OUTPUTS):
+    """A linear head and its render in one pass: the outputs of segment_render(conv1x1(x, weight, bias),
+    class_offsets=...) at the input size without any [B, P, H, W] tensor.  x: logical B x C x H x W fp32 / bf16, 1 <= C <= 64 (read
+    where it is when its channels are dense and its pixels uniformly strided); weight: fp32 [P, C]; bias: fp32 [P] or None, on the
+    device.  The value of name p is fmaf(w[p][C-1], x[C-1], ... fmaf(w[p][0], x[0], bias[p]) ...), ascending c, bf16 widened first.
+    class_offsets=None: one name per class (K = P <= 255).  ValueError when P exceeds vocab_render_max_names(C) (the weights' LDS
+    budget): the caller then forms the logits and calls segment_render(class_offsets=...).  No autograd."""
+    if not torch.is_tensor(x) or not x.is_cuda:
+        raise ValueError("vocab_render needs a CUDA/HIP tensor (no CPU fallback)")
+    if x.dtype not in (torch.float32, torch.bfloat16) or x.ndim != 4:
+        raise ValueError("vocab_render expects a 4-D float32 / bfloat16 map [B, C, H, W]")
+    B, C, H, W = x.shape
+    if not 1 <= C <= 64:
+        raise ValueError(f"vocab_render handles 1 <= C <= 64 channels, got {C}")
+    if min(B, H, W) < 1:
+        raise ValueError(f"vocab_render needs a non-empty batch, got {tuple(x.shape)}")
+    if (not torch.is_tensor(weight) or weight.dtype != torch.float32 or weight.ndim != 2 or weight.shape[1] != C
+            or weight.device != x.device or not weight.is_contiguous()):
+        raise ValueError(f"weight must be a contiguous float32 tensor of shape [P, {C}] on {x.device}")
+    P = int(weight.shape[0])
+    if not 1 <= P <= 1024:
+        raise ValueError(f"vocab_render handles 1 <= P <= 1024 names, got {P}")
+    if bias is not None and (not torch.is_tensor(bias) or bias.dtype != torch.float32 or tuple(bias.shape) != (P,)
+                             or bias.device != x.device or not bias.is_contiguous()):
+        raise ValueError(f"bias must be a contiguous float32 tensor of shape {(P,)} on {x.device}, or None")
+    offs, K = (None, P) if class_offsets is None else _class_offsets("vocab_render", class_offsets, P, x.device)
+    if not 1 <= K <= 255:
+        raise ValueError(f"vocab_render handles 1 <= K <= 255 classes, got {K}")
+    limit = vocab_render_max_names(C)
+    if P > limit:
+        raise ValueError(f"vocab_render keeps the weights in LDS: at C = {C} at most {limit} names, got {P}")
+    palette, background, alpha256, min_conf, ignore_label, out = _render_args("vocab_render", x, B, K, H, W, palette, background, alpha,
+                                                                              min_conf, ignore_label, want)
+    xn = _nhwc_any(x.detach())
+    _lib.check(_lib.load().oess_head_render(_ptr(xn), int(x.dtype == torch.bfloat16), _pix_stride(xn), B, C, H, W, _ptr(weight.detach()),
+                                            _ptr(bias.detach() if bias is not None else None), K, P, _ptr(offs), _ptr(palette),
+                                            _ptr(background), alpha256, min_conf, ignore_label, _ptr(out.get('labels')),
+                                            _ptr(out.get('conf')), _ptr(out.get('rgb')), _stream()), "oess_head_render")
     for t in out.values():
         _bump(t)
     return out

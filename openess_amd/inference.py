@@ -8,6 +8,11 @@ trainers' saver, puts every module in eval mode and renders the logits on hip.se
                                               resolution but the outputs is formed); with a linear probe, the full-resolution logits
                                               and the same-size render
 
+An open vocabulary: set_vocabulary / set_vocabulary_embeddings replace the classes at run time -- K classes over
+P >= K names, a class's value the maximum over its names.  The event students then go head_features -> hip.vocab_render (head and
+render in one pass; above its LDS budget the head conv on the composed operator -> the grouped hip.segment_render), frame2recon
+goes logits_at_stride(text_embeddings=T) -> the grouped upsampling render; reset_vocabulary returns to the checkpoint's classes.
+
 The event path runs on a reconstructor of the Segmenter's own, in its precision: it shares no recurrent state with the trainer's
 steps or validation, and never touches an optimiser."""
 import math
@@ -22,6 +27,33 @@ from .e2vid.image_reconstructor import ImageReconstructor, PostProcessor
 
 EVENT_OPTIONS = ('frame2voxel', 'recon2voxel')
 CONFIG_OPTIONS = EVENT_OPTIONS + ('frame2recon',)
+
+
+EMBED_DIM = 512                                 # CLIP ViT-B/16's text width, the width of both students' classifiers
+MAX_CLASSES, MAX_NAMES = 255, 1024              # the render kernels' limits (include/oess.h)
+
+
+def voc_palette(K):
+    """uint8 [K, 3] numpy: the PASCAL-VOC colour map (class id bits reversed into the three channels); colour 0 is black"""
+    import numpy as np
+    pal = np.zeros((K, 3), np.uint8)
+    for i in range(K):
+        c = i
+        for j in range(8):
+            for ch in range(3):
+                pal[i, ch] |= ((c >> ch) & 1) << (7 - j)
+            c >>= 3
+    return pal
+
+
+def check_class_offsets(class_offsets, P):
+    """list of K + 1 ints of a list / tensor of offsets over P names: 0 first, strictly increasing, P last, K <= 255"""
+    offs = [int(o) for o in (class_offsets.tolist() if torch.is_tensor(class_offsets) else class_offsets)]
+    if len(offs) < 2 or offs[0] != 0 or offs[-1] != P or any(b <= a for a, b in zip(offs, offs[1:])):
+        raise ValueError(f"class_offsets must start at 0, increase strictly and end at the number of names {P}, got {offs!r}")
+    if len(offs) - 1 > MAX_CLASSES:
+        raise ValueError(f"a vocabulary holds at most {MAX_CLASSES} classes (labels are bytes, 255 is the ignore label), got {len(offs) - 1}")
+    return offs
 
 
 def _train_module():
@@ -69,6 +101,8 @@ class Segmenter:
             m.eval()
         self.num_classes, self.ignore_label = s.semseg_num_classes, s.semseg_ignore_label
         self.palette = torch.from_numpy(s.semseg_color_map.copy()).to(self.device).contiguous()
+        self._own = (self.num_classes, self.palette)          # the checkpoint's vocabulary, for reset_vocabulary()
+        self._vocab = None                       # the run-time vocabulary (set_vocabulary_embeddings), None: the checkpoint's own
         self._states = None                      # recurrent states of the stateful path
         self.render_events = None                # (start, end) HIP events around the last render, for the CLI's timing
         self._rec = self._post = None
@@ -79,22 +113,121 @@ class Segmenter:
                 self.trainer.models_dict['back_end'].check_fp32()
             self._rec = ImageReconstructor(self.trainer.models_dict['front_sensor_b'], H, W, s.nr_temporal_bins_b, self.device, opts)
 
-    def _render(self, logits, **kw):
+    def _render(self, logits, fn=None, **kw):
+        """hip.segment_render (or fn: hip.vocab_render) between two timing events, with this object's palette and ignore label"""
         start, end = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         start.record()
-        out = hip.segment_render(logits, palette=self.palette, ignore_label=self.ignore_label, **kw)
+        out = (fn or hip.segment_render)(logits, palette=self.palette, ignore_label=self.ignore_label, **kw)
         end.record()
         self.render_events = (start, end)
         return out
+
+    # ---------------------------------------------------------------------------------------------------------------- vocabulary
+    def _classifier(self):
+        return self.trainer.models_dict['back_end' if self.is_event else 'model_recon']
+
+    def _refuse_probe(self):
+        if getattr(self._classifier(), 'if_linear_probing', False):
+            raise ValueError("a linear-probe checkpoint keeps its vocabulary: the probe's K x K conv is tied to the trained classes")
+
+    def set_vocabulary_embeddings(self, T, class_offsets=None, names=None, palette=None):
+        """Classify into the vocabulary of the text embeddings T: float [P, 512] unit rows, one per NAME.  class_offsets: K + 1
+        offsets grouping the names into K classes (contiguous groups; None: one name per class); a class's value is the maximum
+        over its names.  names: K lists of names (kept for `vocabulary`); palette: uint8 [K, 3] (None: voc_palette(K)).
+        num_classes and palette follow.  Refused before any launch: a linear-probe checkpoint, a width other than 512, more than
+        255 classes or 1024 names, an ignore label that would be a class."""
+        import numpy as np
+        self._refuse_probe()
+        if not torch.is_tensor(T) or T.ndim != 2 or not T.is_floating_point() or T.shape[0] < 1:
+            raise ValueError("text embeddings must be a float [P, 512] tensor, one row per name")
+        P = int(T.shape[0])
+        if T.shape[1] != EMBED_DIM:
+            raise ValueError(f"the classifiers multiply with embeddings of width {EMBED_DIM}, got width {T.shape[1]}")
+        if P > MAX_NAMES:
+            raise ValueError(f"a vocabulary holds at most {MAX_NAMES} names, got {P}")
+        offs = check_class_offsets(range(P + 1) if class_offsets is None else class_offsets, P)
+        K = len(offs) - 1
+        if K > self.ignore_label:
+            raise ValueError(f"{K} classes: the settings' ignore label {self.ignore_label} would be a class")
+        if names is not None:
+            names = [[n] if isinstance(n, str) else list(n) for n in names]
+            if len(names) != K:
+                raise ValueError(f"names must hold one entry per class ({K}), got {len(names)}")
+        if palette is None:
+            palette = voc_palette(K)
+        pal = torch.as_tensor(np.asarray(palette.cpu() if torch.is_tensor(palette) else palette))
+        if pal.dtype != torch.uint8 or tuple(pal.shape) != (K, 3):
+            raise ValueError(f"palette must be uint8 [{K}, 3], got {pal.dtype} {tuple(pal.shape)}")
+        v = SimpleNamespace(T=T.detach().to(self.device, torch.float32).contiguous(), offsets=offs, K=K, P=P, names=names,
+                            grouped=P != K, weight=None, bias=None, fused=False, pw=None)
+        if self.is_event:
+            back = self._classifier()
+            v.weight, v.bias = back.compose_vocabulary(v.T)
+            v.fused = P <= hip.vocab_render_max_names(v.weight.shape[1])
+            if not v.fused:                       # the weights exceed vocab_render's LDS budget: the head as a conv of its own
+                from . import engine
+                w4 = v.weight[:, :, None, None]
+                v.pw = (engine.PackedWeightF32().get(w4, v.bias) if self.precision == 'fp32'
+                        else engine.PackedWeight().get(w4, v.bias, None, cin_pad=w4.shape[1]))
+        self._vocab = v
+        self.num_classes, self.palette = K, pal.to(self.device).contiguous()
+
+    def set_vocabulary(self, classes, merge='max', templates='single', palette=None, clip_text_checkpoint=None, clip_bpe_path=None):
+        """Classify into `classes`: a list whose entries are a name or a list of names of one class (clip_text.parse_classes
+        reads the `a|b` syntax).  CLIP's text tower (clip_text_checkpoint, clip_bpe_path; default: the settings' keys) embeds
+        every name under `templates` ('single', 'none' or a file).  merge='max': one embedding per name, a class's value the
+        maximum over its names (what the reference's pseudo-label writer does); merge='mean': one embedding per class, its names
+        pooled by CLIP's ensemble (K29's text_classes)."""
+        from .models import clip_text
+        from .models.clip_tokenizer import CLIPTokenizer
+        self._refuse_probe()
+        if merge not in ('max', 'mean'):
+            raise ValueError(f"merge must be 'max' or 'mean', got {merge!r}")
+        ckpt = clip_text_checkpoint or getattr(self.settings, 'clip_text_checkpoint', None)
+        bpe = clip_bpe_path or getattr(self.settings, 'clip_bpe_path', None)
+        if not ckpt or not bpe:
+            raise ValueError("set_vocabulary needs clip_text_checkpoint (CLIP weights) and clip_bpe_path (the BPE merges file), "
+                             "as arguments or in the settings file")
+        for key, path in (('clip_text_checkpoint', ckpt), ('clip_bpe_path', bpe)):
+            if not os.path.isfile(path):
+                raise ValueError(f"{key}: file not found: {path}")
+        classes = list(classes)
+        prompts, name_offsets, class_offsets, names = clip_text.build_vocabulary(classes, clip_text.read_templates(templates))
+        if len(names) > MAX_CLASSES:
+            raise ValueError(f"a vocabulary holds at most {MAX_CLASSES} classes, got {len(names)}")
+        if merge == 'mean':
+            T, class_offsets = clip_text.compute_text_embeddings(ckpt, bpe, classes, templates, self.device), None
+        else:
+            model = clip_text.load_clip_text_checkpoint(ckpt, self.device)
+            ids = CLIPTokenizer(bpe).tokenize(prompts, context_length=model.context_length)
+            T = model.encode_classes(ids, name_offsets)
+        self.set_vocabulary_embeddings(T, class_offsets, names, palette)
+
+    def reset_vocabulary(self):
+        """Back to the checkpoint's own vocabulary."""
+        self._vocab = None
+        self.num_classes, self.palette = self._own
+
+    @property
+    def vocabulary(self):
+        """[{'id', 'names', 'color'}] of the classes in use (names: None where nobody gave them)"""
+        pal = self.palette.cpu().tolist()
+        if self._vocab is not None:
+            names = self._vocab.names
+        else:
+            own = getattr(self.settings, 'semseg_class_names', None)
+            names = [[str(n)] for n in own] if own is not None and len(own) == self.num_classes else None
+        return [{'id': k, 'names': None if names is None else names[k], 'color': pal[k]} for k in range(self.num_classes)]
 
     # ------------------------------------------------------------------------------------------------------------ event students
     def reset(self):
         """Forget the recording: the next stateful call starts from empty states."""
         self._states = None
 
-    def _event_logits(self, event, stateful, want_recon):
+    def _event_logits(self, event, stateful, want_recon, head_operand=False):
         """(logits fp32 [B, K, H, W], grey u8 [B, H, W] | None) of fp32 events [B, n * C, H, W]: the sub-windows through the E2VID
-        encoder in order (_latents / _latents_fp32 of the trainers, on this object's reconstructor), the decoder on the last."""
+        encoder in order (_latents / _latents_fp32 of the trainers, on this object's reconstructor), the decoder on the last.
+        head_operand=True: the decoder_scale_4 map [B, 32, H, W] takes the logits' place (a vocabulary's head follows in the render)."""
         s, rec = self.settings, self._rec
         C = s.input_channels_b
         if (not torch.is_tensor(event) or event.ndim != 4 or event.dtype != torch.float32 or not event.is_cuda
@@ -116,7 +249,10 @@ class Segmenter:
                     img, _, latent = rec.update_reconstruction(event, channel_slice=(i * C, C), need_latents=last,
                                                                reconstruct=last and want_recon)
             back = self.trainer.models_dict['back_end']
-            logits = (back.forward_fp32(latent) if self.precision == 'fp32' else back(latent))[0][1]
+            if head_operand:
+                logits = back.head_features(latent, self.precision)
+            else:
+                logits = (back.forward_fp32(latent) if self.precision == 'fp32' else back(latent))[0][1].float()
             if stateful:
                 self._states = rec.last_states_for_each_channel['grayscale']
         finally:
@@ -128,7 +264,20 @@ class Segmenter:
             if self._post is None:
                 self._post = PostProcessor(self.device)              # the reference's defaults
             grey = self._post.process_u8(img[:, :1])                 # the crop view goes in as it is, as in run_reconstruction
-        return logits.float(), grey
+        return logits, grey
+
+    def _render_vocabulary(self, x, **kw):
+        """The event students under a vocabulary: x is the head's operand [B, 32, H, W]"""
+        v = self._vocab
+        offs = v.offsets if v.grouped else None
+        if v.fused:
+            return self._render(x, fn=hip.vocab_render, weight=v.weight, bias=v.bias, class_offsets=offs, **kw)
+        if self.precision == 'fp32':
+            logits = hip.conv2d_f32(x, v.pw.packed, v.pw.bias, v.P, 1, 1)
+        else:
+            from . import engine
+            logits = engine.conv2d_infer(x, v.pw, v.P, 1, out_f32=True)
+        return self._render(logits, class_offsets=v.offsets, **kw)
 
     @torch.no_grad()
     def predict_events(self, event_tensor, stateful=False, want_recon=False, min_conf=0.0, background=None, alpha=0.5):
@@ -142,11 +291,12 @@ class Segmenter:
         over_recon = isinstance(background, str)
         if over_recon and background != 'recon':
             raise ValueError(f"background must be a uint8 tensor, None or 'recon', got {background!r}")
-        logits, grey = self._event_logits(event_tensor, bool(stateful), bool(want_recon) or over_recon)
+        logits, grey = self._event_logits(event_tensor, bool(stateful), bool(want_recon) or over_recon, self._vocab is not None)
         if grey is not None and tuple(grey.shape[1:]) != tuple(logits.shape[2:]):
             raise ValueError("the reconstruction is cropped to the sensor, the logits are at the padded size: no overlay for sizes "
                              "that are not multiples of 8")
-        out = self._render(logits, background=grey if over_recon else background, alpha=alpha, min_conf=min_conf)
+        render = self._render if self._vocab is None else self._render_vocabulary
+        out = render(logits, background=grey if over_recon else background, alpha=alpha, min_conf=min_conf)
         if want_recon:
             out['recon'] = grey
         return out
@@ -161,4 +311,8 @@ class Segmenter:
         kw = dict(background=background, alpha=alpha, min_conf=min_conf)
         if model.if_linear_probing:                           # the probe sits behind the resize: full-resolution logits
             return self._render(self.trainer.val_logits(batch, self.precision), **kw)
+        if self._vocab is not None:               # (never with a probe: set_vocabulary_embeddings refuses it)
+            v = self._vocab
+            low = model.logits_at_stride(batch[2], self.precision, text_embeddings=v.T)
+            return self._render(low, size=tuple(batch[2].shape[-2:]), class_offsets=v.offsets if v.grouped else None, **kw)
         return self._render(model.logits_at_stride(batch[2], self.precision), size=tuple(batch[2].shape[-2:]), **kw)

@@ -11,6 +11,8 @@ Inference only, fp32 only: the result is computed once per run and becomes class
   -> layer norm -> linear (c_fc, QuickGELU epilogue) -> linear (c_proj, + x)
 then hip.clip_text_eot_norm on the N end-of-text rows alone and the projection as one more token GEMM.  Packed operands are
 cached per parameter version (engine.PackedWeightF32), as in the image tower."""
+import os
+
 import torch
 import torch.nn as nn
 
@@ -219,6 +221,25 @@ def read_templates(spec):
     return lines
 
 
+def parse_classes(spec):
+    """A comma list, or a file with one class per line; `a|b|c` names several names of one class -> the list build_prompts and
+    build_vocabulary take (a name, or a list of names)"""
+    if os.path.isfile(spec):
+        with open(spec) as f:
+            entries = [ln.strip() for ln in f if ln.strip()]
+    else:
+        entries = [e.strip() for e in spec.split(',') if e.strip()]
+    classes = []
+    for e in entries:
+        names = [n.strip() for n in e.split('|') if n.strip()]
+        if not names:
+            raise ValueError(f"--classes: empty class in {e!r}")
+        classes.append(names[0] if len(names) == 1 else names)
+    if not classes:
+        raise ValueError("--classes: no class")
+    return classes
+
+
 def build_prompts(classes, templates):
     """classes: list whose entries are a name or a list of synonyms -> (prompts, offsets): for class k every synonym under every
     template (synonym-major), offsets[k] .. offsets[k + 1] its rows"""
@@ -232,6 +253,26 @@ def build_prompts(classes, templates):
     if len(offsets) < 2:
         raise ValueError("no classes")
     return prompts, torch.tensor(offsets, dtype=torch.int64)
+
+
+def build_vocabulary(classes, templates):
+    """An open vocabulary with several names per class.  classes: as build_prompts.  Returns
+    (prompts, name_offsets int64 [P + 1], class_offsets int64 [K + 1], names): one row PER NAME -- encode_classes(ids,
+    name_offsets) pools a name's templates, CLIP's ensemble -- and class k owns the names class_offsets[k] ... class_offsets[k + 1]
+    - 1, the contiguous groups hip.segment_render / hip.vocab_render merge by their maximum.  names: the K lists of names."""
+    names = []
+    for c in classes:
+        group = [c] if isinstance(c, str) else list(c)
+        if not group or any(not isinstance(n, str) or not n.strip() for n in group):
+            raise ValueError(f"class entry {c!r} must be a non-empty name or a list of them")
+        names.append([n.strip() for n in group])
+    if not names:
+        raise ValueError("no classes")
+    prompts, name_offsets = build_prompts([n for group in names for n in group], templates)
+    class_offsets = [0]
+    for group in names:
+        class_offsets.append(class_offsets[-1] + len(group))
+    return prompts, name_offsets, torch.tensor(class_offsets, dtype=torch.int64), names
 
 
 @torch.no_grad()

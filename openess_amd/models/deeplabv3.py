@@ -182,10 +182,29 @@ class DeepLabHead(nn.Module):
         self._pw_text = engine.PackedWeight()
         self._pw_text32 = engine.PackedWeightF32()
         self._pw_text32_train = engine.PackedWeightF32()      # fp32 training operands (forward_fp32_autograd)
+        self._vocab_text = None                               # the run-time vocabulary the two operands below were packed from
+        self._pw_vocab, self._pw_vocab32 = engine.PackedWeight(), engine.PackedWeightF32()
 
-    def forward_fp32(self, feature):
+    def _vocabulary(self, text):
+        """Operand caches of a run-time vocabulary (K36), apart from those of the registered text_embeddings: fresh ones whenever
+        another matrix arrives.  text: fp32 [P, 512] on the module's device."""
+        te = self.text_embeddings
+        if (not torch.is_tensor(text) or text.ndim != 2 or text.shape[1] != te.shape[1] or text.shape[0] < 1
+                or text.dtype != torch.float32 or text.device != te.device):
+            raise ValueError(f"text_embeddings must be a float32 [P, {te.shape[1]}] matrix on {te.device}")
+        if text is not self._vocab_text:
+            self._vocab_text = text
+            self._pw_vocab, self._pw_vocab32 = engine.PackedWeight(), engine.PackedWeightF32()
+        return text.detach()
+
+    def forward_fp32(self, feature, text=None):
+        """text: a run-time vocabulary [P, 512] in place of text_embeddings (K36); None: the registered matrix and its operand."""
         feature = self.ASPP.forward_fp32(feature['out'])
         x = conv_bn_f32(self.classifier[0], self.classifier[1], feature, relu=True)
+        if text is not None:
+            te = self._vocabulary(text)
+            op = self._pw_vocab32.get_composed([te], lambda: (te.double()[:, :, None, None], None))
+            return hip.conv2d_f32(x, op.packed, None, te.shape[0], 1, 1), feature
         te = self.text_embeddings
         op = self._pw_text32.get_composed([te], lambda: (te.detach().double()[:, :, None, None], None))
         return hip.conv2d_f32(x, op.packed, None, te.shape[0], 1, 1), feature
@@ -199,9 +218,13 @@ class DeepLabHead(nn.Module):
         logits = hip.conv2d_dilated_f32_train(x, te[:, :, None, None], None, pw=self._pw_text32_train, ver=te._version)
         return logits, feature
 
-    def forward(self, feature):
+    def forward(self, feature, text=None):
         feature = self.ASPP(feature['out'])
         x = conv_bn(self.classifier[0], self.classifier[1], feature, relu=True)
+        if text is not None:                                  # a run-time vocabulary (K36): its own operand, no autograd
+            te = self._vocabulary(text)
+            with torch.no_grad():
+                return engine.conv2d_train(x, te[:, :, None, None], None, self._pw_vocab, 1, ver=te._version), feature
         logits = engine.conv2d_train(x, self.text_embeddings[:, :, None, None].float(), None, self._pw_text, 1,
                                      ver=self.text_embeddings._version)
         return logits, feature
@@ -287,11 +310,13 @@ class deeplabv3_resnet50(nn.Module):
         return self._forward_fp32('forward_fp32', x, False, True)
 
     @torch.no_grad()
-    def logits_at_stride(self, x, precision='bf16'):
+    def logits_at_stride(self, x, precision='bf16', text_embeddings=None):
         """The eval-mode network up to the classifier's output, fp32 [B, K, H / stride, W / stride]: what forward() ('bf16') and
         forward_fp32() ('fp32') resize to the input size, from their own pieces and so with their bits.  Neither the
         full-resolution logits nor the 256-channel feature map at the input size are formed: hip.segment_render /
         hip.argmax_labels with size=x.shape[-2:] blend these logits exactly as the resize does.
+        text_embeddings (K36): a float32 [P, 512] matrix on the device; the logits are then [B, P, ...] against IT, from operands
+        of its own (the registered buffer and its cached operands are not touched).  None is the path above, bit for bit.
         Refused: a train-mode module (check_fp32's rule, in both precisions), and a linear probe, which sits behind the resize."""
         if precision not in ('bf16', 'fp32'):
             raise ValueError(f"precision must be 'bf16' or 'fp32', got {precision!r}")
@@ -302,9 +327,9 @@ class deeplabv3_resnet50(nn.Module):
         if precision == 'fp32':
             if x.dtype != torch.float32 or x.ndim != 4:
                 raise ValueError("logits_at_stride takes a float32 [B, 3, H, W] image batch")
-            return self.classifier.forward_fp32(self.backbone.forward_fp32(x))[0]
+            return self.classifier.forward_fp32(self.backbone.forward_fp32(x), text_embeddings)[0]
         with engine.defer_bn_counters():
-            return self.classifier(self.backbone(x))[0].float()
+            return self.classifier(self.backbone(x), text_embeddings)[0].float()
 
     def _forward_fp32(self, name, x, train, want_feats):
         """What forward_fp32 (`name`, train=False) and forward_fp32_train share: the input check, the network in its mode, the two

@@ -204,7 +204,8 @@ class SemSegE2VID(nn.Module):
         tw2 = t @ w2
         return (tw2 @ w1)[:, :, None, None], t @ b2 + tw2 @ b1
 
-    def forward(self, input_dict):
+    def _decoder(self, input_dict):
+        """THE bf16 decoder walk of forward and head_features: (out with the keys 8, 4 and 2, the decoder_scale_4 map)."""
         sz_in = input_dict[1].shape[3]
         x = input_dict[8]
         out = {8: x}
@@ -218,7 +219,36 @@ class SemSegE2VID(nn.Module):
         x = self.decoder_scale_3(x)
         self.update_skip_dict(out, x, sz_in)
         x = hip.upsample2x_concat(x)
-        x = self.decoder_scale_4(x)
+        return out, self.decoder_scale_4(x)
+
+    @torch.no_grad()
+    def head_features(self, input_dict, precision='bf16'):
+        """The decoder_scale_4 map [B, 32, H, W], the operand of the composed head: bf16 from forward's pieces
+        ('bf16'), fp32 from forward_fp32's ('fp32', under check_fp32's rules).  With compose_vocabulary's operator the logits of
+        ANY vocabulary follow from it; neither method touches text_embeddings or the cached packed operands."""
+        if precision not in ('bf16', 'fp32'):
+            raise ValueError(f"precision must be 'bf16' or 'fp32', got {precision!r}")
+        if precision == 'fp32':
+            self.check_fp32()
+            return self._decoder_f32('head_features', input_dict, F32_EVAL)[1]
+        return self._decoder(input_dict)[1]
+
+    @torch.no_grad()
+    def compose_vocabulary(self, text):
+        """(fp32 [P, 32], fp32 [P]): decoder_ch256 -> decoder_ch512 -> text [P, 512] as one operator, composed in float64
+        (compose_head_f64) and rounded once -- forward_fp32's head for any vocabulary.  A linear probe is tied to the trained
+        classes: refused."""
+        if self.if_linear_probing:
+            raise NotImplementedError("compose_vocabulary: the linear probe's K x K conv is tied to the trained classes")
+        if not torch.is_tensor(text) or text.ndim != 2 or text.shape[1] != self.decoder_ch512[0].out_channels or text.shape[0] < 1:
+            raise ValueError(f"compose_vocabulary takes text embeddings [P, {self.decoder_ch512[0].out_channels}]")
+        c256, c512 = self.decoder_ch256[0], self.decoder_ch512[0]
+        w, b = compose_head_f64(c256.weight, c256.bias, c512.weight, c512.bias, text.to(c256.weight.device))
+        return w.flatten(1).float().contiguous(), b.float().contiguous()
+
+    def forward(self, input_dict):
+        sz_in = input_dict[1].shape[3]
+        out, x = self._decoder(input_dict)
         # 'pooled': the 256-channel map only feeds the superpixel mean, which commutes with the 1x1 convolution (hip.PointwiseFeature)
         if self.materialize_ch256 == 'pooled':
             x_ch256 = hip.PointwiseFeature(x, self.decoder_ch256[0])

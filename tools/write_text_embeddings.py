@@ -19,20 +19,8 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 
 def parse_classes(spec):
-    if os.path.isfile(spec):
-        with open(spec) as f:
-            entries = [ln.strip() for ln in f if ln.strip()]
-    else:
-        entries = [e.strip() for e in spec.split(',') if e.strip()]
-    classes = []
-    for e in entries:
-        names = [n.strip() for n in e.split('|') if n.strip()]
-        if not names:
-            raise ValueError(f"--classes: empty class in {e!r}")
-        classes.append(names[0] if len(names) == 1 else names)
-    if not classes:
-        raise ValueError("--classes: no class")
-    return classes
+    from openess_amd.models.clip_text import parse_classes as parse
+    return parse(spec)
 
 
 def main(argv=None):
