@@ -690,6 +690,36 @@ int oess_png_decode_gray8_batch(const uint8_t* files, const int64_t* offsets, lo
                                 int* status, oess_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * GPU-side encode of 8-bit grey / RGB maps into PNG files: oess_segment_render's `labels` and `rgb`, SLIC's
+ * superpixel ids.  Replaces Image.fromarray(map).save(path) for a whole batch; the host writes the returned bytes as they are.
+ *   images   contiguous u8 [n_images][H][W] (channels = 1) or [n_images][H][W][3] (channels = 3)
+ *   files    [n_images][slot_bytes]; image i's file is files[i][0 ... sizes[i]); the bytes of a slot beyond that are
+ *            unspecified; nothing outside the n slots and sizes[n_images] is written
+ *   scratch  oess_png_encode_scratch_bytes(n_images, H, W, channels) bytes, 16-byte aligned
+ * The format is a fixed subset of PNG, so that the bytes are the same from any implementation of this text:
+ *   signature; IHDR (W, H, bit depth 8, colour type 0 or 2, no interlace); an IDAT holding 78 01; one IDAT per segment; an IDAT
+ *   holding the Adler-32 of the filtered stream; IEND.  Every scanline has filter type 4 (Paeth, ties in the order a, b, c,
+ *   pixels outside the image 0).  The filtered stream of S = H (1 + W channels) bytes is cut into segments of
+ *   OESS_PNG_ENCODE_SEGMENT bytes (the last one shorter); each is one DEFLATE block that starts on a byte, BFINAL on the last.
+ *   Coded form (BTYPE 01, the fixed Huffman code): runs of equal bytes are found inside the segment only; a run of L bytes is
+ *   one literal, then matches at distance 1 over the other L - 1 bytes, each as long as fits (at most 258) while at least 3
+ *   remain, then the 0 ... 2 bytes left as literals; then end-of-block; a segment that is not the last is closed by an empty
+ *   stored block (000, zero bits to the byte, 00 00 FF FF), the last one is padded to the byte with zero bits.
+ *   Stored form (BTYPE 00: the header byte, LEN, NLEN, the bytes): used exactly when the coded form with its closing bytes would
+ *   not be shorter than 5 + the segment's length.
+ * So a file is at most oess_png_encode_bound = 75 + S + 17 ceil(S / OESS_PNG_ENCODE_SEGMENT) bytes (host only; 0 for a size the
+ * encoder refuses).  The bytes depend on the input alone: two calls give the same files.
+ * OESS_EINVAL before any HIP call, outputs untouched: a null pointer, n_images < 1, channels not 1 or 3, H or W outside
+ * 1 ... 16384, slot_bytes below the bound, scratch_bytes below the query, scratch off 16 bytes, n_images times the segments of
+ * an image above 2^31 - 1 (the scratch query answers 0 there).  Adding these entries left OESS_ABI_VERSION unchanged.
+ * ------------------------------------------------------------------------------------------ */
+#define OESS_PNG_ENCODE_SEGMENT 16384
+long long oess_png_encode_bound(int H, int W, int channels);
+size_t oess_png_encode_scratch_bytes(int n_images, int H, int W, int channels);
+int oess_png_encode_batch(const uint8_t* images, int n_images, int H, int W, int channels, uint8_t* files, long long slot_bytes,
+                          int* sizes, void* scratch, size_t scratch_bytes, oess_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * Linear probe: nn.Conv2d(K, K, 1) on the fp32 logits (models/style_networks.py:113-133,169-170; models/deeplabv3.py:162-170,
  * 186-187), K <= 32.  x, y, grad_*: dense NHWC fp32 [P x K]; w: [K x K] (Conv2d.weight viewed [out, in]); bias nullable in the
  * forward.  Backward: grad_x nullable (frozen producer); grad_w / grad_bias from per-workgroup double partial rows added in a fixed order (bit-repeatable);

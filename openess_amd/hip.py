@@ -199,6 +199,71 @@ def png_decode_gray8_batch(files, lengths, H, W, flips=None, out=None):
     return out, status
 
 
+PNG_ENCODE_SEGMENT = 16384              # OESS_PNG_ENCODE_SEGMENT of include/oess.h
+
+
+def png_encode_bound(H, W, channels):
+    """The largest file png_encode_batch writes for an H x W map of 1 or 3 channels: the slot size it allocates."""
+    n = int(_lib.load().oess_png_encode_bound(int(H), int(W), int(channels)))
+    if n <= 0:
+        raise ValueError(f"png_encode handles 1 <= H, W <= 16384 and 1 or 3 channels, got {(H, W, channels)}")
+    return n
+
+
+def _png_encode_geom(images):
+    if (not torch.is_tensor(images) or not images.is_cuda or images.dtype != torch.uint8 or not images.is_contiguous()
+            or images.ndim not in (3, 4) or (images.ndim == 4 and images.shape[3] != 3)):
+        raise ValueError("png_encode needs a contiguous CUDA/HIP uint8 tensor [n, H, W] or [n, H, W, 3] (no CPU fallback)")
+    n, H, W = images.shape[:3]
+    ch = 1 if images.ndim == 3 else 3
+    if n < 1:
+        raise ValueError("png_encode needs at least one image")
+    return n, H, W, ch, png_encode_bound(H, W, ch)
+
+
+def png_encode_batch(images, out=None):
+    """Encode a batch of 8-bit maps as PNG files on the GPU.  images: contiguous u8 [n, H, W] (grey) or
+    [n, H, W, 3] (RGB) on the device, e.g. segment_render's 'labels' and 'rgb'.  Returns (files u8 [n, slot], sizes int32 [n]),
+    both on the device: image i's file is files[i, :sizes[i]], the rest of a slot is unspecified.  out: a (files, sizes) pair
+    of an earlier call on the same shape to write into."""
+    lib = _lib.load()
+    n, H, W, ch, bound = _png_encode_geom(images)
+    if out is None:
+        files = torch.empty((n, bound), dtype=torch.uint8, device=images.device)
+        sizes = torch.empty(n, dtype=torch.int32, device=images.device)
+    else:
+        files, sizes = out
+        if (not torch.is_tensor(files) or files.dtype != torch.uint8 or files.device != images.device or files.ndim != 2
+                or files.shape[0] != n or files.shape[1] < bound or not files.is_contiguous()):
+            raise ValueError(f"out[0] must be a contiguous uint8 tensor [{n}, >= {bound}] on {images.device}")
+        if (not torch.is_tensor(sizes) or sizes.dtype != torch.int32 or sizes.device != images.device or tuple(sizes.shape) != (n,)
+                or not sizes.is_contiguous()):
+            raise ValueError(f"out[1] must be a contiguous int32 tensor [{n}] on {images.device}")
+    need = lib.oess_png_encode_scratch_bytes(n, H, W, ch)
+    if need == 0:
+        raise ValueError(f"png_encode: a batch of {n} maps of {H} x {W} x {ch} has too many segments for one call")
+    ws = _workspace(need, images.device, tag="png_encode")
+    _lib.check(lib.oess_png_encode_batch(_ptr(images), n, H, W, ch, _ptr(files), files.shape[1], _ptr(sizes), _ptr(ws), ws.numel(),
+                                         _stream()), "oess_png_encode_batch")
+    _bump(files)
+    _bump(sizes)
+    return files, sizes
+
+
+def png_encode_files(images):
+    """png_encode_batch, then the files as a list of bytes.  The sizes cross first (pinned memory, the call's one wait on the
+    stream); then only the first max(sizes) columns of the slots follow, in one blocking copy into pinned memory."""
+    files, sizes = png_encode_batch(images)
+    host_sizes = torch.empty(sizes.shape, dtype=torch.int32, pin_memory=True)
+    host_sizes.copy_(sizes, non_blocking=True)
+    torch.cuda.current_stream(images.device).synchronize()
+    lens = host_sizes.tolist()
+    host = torch.empty((files.shape[0], max(lens)), dtype=torch.uint8, pin_memory=True)
+    host.copy_(files[:, :max(lens)])
+    rows = host.numpy()
+    return [rows[i, :n].tobytes() for i, n in enumerate(lens)]
+
+
 # ------------------------------------------------------------------------------------------ K2
 class EventPre:
     """EventPreprocessor's event-side options (e2vid/utils/inference_utils.py:71-75) for the kernels that read the raw event

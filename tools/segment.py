@@ -4,8 +4,8 @@ and, on request, confidence maps, rendered by hip.segment_render from openess_am
 
     python tools/segment.py -o OUT [--settings YAML] [--config-option frame2voxel | recon2voxel | frame2recon]
                             [--checkpoint FILE] [--precision bf16 | fp32] [--min-conf 0] [--alpha 0.5] [--max-frames N]
-                            [--save-confidence] [--split val | -i events.txt [-N EVENTS] [--skipevents N] [--stateful]
-                            [--overlay recon]]
+                            [--save-confidence] [--png-encoder host | gpu]
+                            [--split val | -i events.txt [-N EVENTS] [--skipevents N] [--stateful] [--overlay recon]]
                             [--classes "road,car|vehicle,person" | --classes FILE [--merge max | mean] [--templates single]
                             [--clip-text-checkpoint FILE] [--bpe FILE]]
 
@@ -17,6 +17,9 @@ and, on request, confidence maps, rendered by hip.segment_render from openess_am
                          nr_events_data windows becomes one event tensor (the DSEC loader's VoxelGrid per window, no rectification)
                          and one frame.  --stateful feeds one window per prediction and carries the recurrent states.
   --overlay recon        blend the colours over the E2VID image of the last window (event students).
+
+  --png-encoder gpu      the label and colour PNGs are encoded on the device (hip.png_encode_files) and written
+                         as they come; host (default): the maps cross to the host and Pillow encodes them.  The same pixels.
 
   --classes              an open vocabulary: a comma list, or a file with one class per line; `a|b` gives one
                          class several names.  CLIP's text tower (--clip-text-checkpoint, --bpe; default: the settings' keys)
@@ -57,6 +60,7 @@ def build_parser():
     ap.add_argument("--min-conf", default=0.0, type=float, help="labels below this confidence become 255")
     ap.add_argument("--max-frames", default=None, type=int)
     ap.add_argument("--save-confidence", action="store_true")
+    ap.add_argument("--png-encoder", default="host", choices=("host", "gpu"), help="who encodes the label and colour PNGs: Pillow (default) or the GPU")
     ap.add_argument("--classes", default=None, help="open vocabulary: comma list or file, one class per line; a|b = two names of one class")
     ap.add_argument("--merge", default=None, choices=("max", "mean"), help="several names of a class: largest logit (default) or pooled embedding")
     ap.add_argument("--templates", default=None, help="single (default), none, or a file with one template containing {} per line")
@@ -132,7 +136,8 @@ def check_args(ap, a):
 
 
 class Writer:
-    def __init__(self, out, save_confidence):
+    def __init__(self, out, save_confidence, png_encoder="host"):
+        self.png_encoder = png_encoder
         self.dirs = {k: os.path.join(out, k) for k in ("labels", "color") + (("confidence",) if save_confidence else ())}
         for d in self.dirs.values():
             os.makedirs(d, exist_ok=True)
@@ -143,11 +148,21 @@ class Writer:
         import numpy as np
         from PIL import Image
         t0 = time.perf_counter()
-        labels, rgb = out['labels'].cpu().numpy(), out['rgb'].cpu().numpy()
+        on_gpu = self.png_encoder == "gpu"
+        if on_gpu and stems:
+            # the files are encoded on the device (K37); only their bytes cross, and they are written as they are
+            from openess_amd import hip
+            for key, sub in (('labels', 'labels'), ('rgb', 'color')):
+                for stem, data in zip(stems, hip.png_encode_files(out[key].contiguous())):
+                    with open(os.path.join(self.dirs[sub], stem + ".png"), "wb") as f:
+                        f.write(data)
+        elif not on_gpu:
+            labels, rgb = out['labels'].cpu().numpy(), out['rgb'].cpu().numpy()
         conf = out['conf'].cpu().numpy() if 'confidence' in self.dirs else None
         for j, stem in enumerate(stems):
-            Image.fromarray(labels[j]).save(os.path.join(self.dirs['labels'], stem + ".png"))
-            Image.fromarray(rgb[j]).save(os.path.join(self.dirs['color'], stem + ".png"))
+            if not on_gpu:
+                Image.fromarray(labels[j]).save(os.path.join(self.dirs['labels'], stem + ".png"))
+                Image.fromarray(rgb[j]).save(os.path.join(self.dirs['color'], stem + ".png"))
             if conf is not None:
                 np.save(os.path.join(self.dirs['confidence'], stem + ".npy"), conf[j])
         self.seconds += time.perf_counter() - t0
@@ -241,7 +256,7 @@ def main(argv=None):
     seg = Segmenter(a.settings, a.config_option, a.checkpoint, a.precision)
     if a.vocabulary is not None:
         seg.set_vocabulary(**a.vocabulary)
-    writer = Writer(a.output, a.save_confidence)
+    writer = Writer(a.output, a.save_confidence, a.png_encoder)
     with open(os.path.join(a.output, "vocabulary.json"), "w") as f:
         json.dump(seg.vocabulary, f, indent=1)
     res = run_events(seg, a, writer) if a.input_file is not None else run_val(seg, a, writer)
@@ -251,6 +266,8 @@ def main(argv=None):
            "ms_per_frame": {"network": round(res["network_render_ms"][0] / n, 3), "render": round(res.pop("network_render_ms")[1] / n, 3), "write": round(1e3 * writer.seconds / n, 3)},
            "output": a.output, "checkpoint": a.checkpoint, "classes": seg.num_classes,
            "vocabulary": None if a.vocabulary is None else {"merge": a.vocabulary["merge"], "templates": a.vocabulary["templates"]}, "device": torch.cuda.get_device_name(0)}
+    if a.png_encoder == "gpu":
+        out["png_encoder"] = "gpu"
     out.update(res)
     print(json.dumps(out))
     return out

@@ -2,6 +2,7 @@
 data_preparation/superpixel_segmenter_dsec_slic.py:
 
     python tools/write_slic_superpixels.py --root DATA --num_segments 100 [--dataset DSEC|DDD17] [--batch 8] [--enforce-connectivity]
+                                           [--png-encoder host|gpu]
 
 DSEC:  every <seq>/images_aligned/left/<name>.png under DATA -> <seq>/sp_slic_rgb/left/<name>_slic_<n>.png
 DDD17: every <dir>/images_aligned/<name>.png under DATA      -> <dir>/sp_slic_rgb/<name>_slic_<n>.png
@@ -10,7 +11,9 @@ this project and of the reference read them.  Frames are read with Pillow and go
 --enforce-connectivity appends SLIC's connectivity pass (skimage's default, which the reference's files were written with): the
 labels then run up to hip.slic_connectivity_sizes' bound, about twice the centres, and a frame size whose bound exceeds the
 256 values of a uint8 map is refused.  Not skimage bit for bit: fp32 arithmetic, and a component of max_size pixels or more
-stays whole (hip.slic_superpixels)."""
+stays whole (hip.slic_superpixels).
+--png-encoder gpu encodes the maps on the device (hip.png_encode_files) and writes the bytes as they come; host
+(default) takes the maps to the host and encodes them with Pillow.  The same pixels either way."""
 import argparse
 import os
 import sys
@@ -44,6 +47,7 @@ def main(argv=None):
     ap.add_argument("--dataset", choices=("DSEC", "DDD17"), default="DSEC")
     ap.add_argument("--batch", type=int, default=8)
     ap.add_argument("--enforce-connectivity", action="store_true", help="append SLIC's connectivity pass (skimage's default)")
+    ap.add_argument("--png-encoder", default="host", choices=("host", "gpu"), help="who encodes the PNGs: Pillow (default) or the GPU")
     args = ap.parse_args(argv)
     import torch
     from PIL import Image
@@ -69,8 +73,14 @@ def main(argv=None):
         frames = torch.from_numpy(np.stack([b[0] for b in batch])).cuda(non_blocking=True)
         frames = frames.permute(0, 3, 1, 2).float() * (1.0 / 255.0)                 # a channels-last view: the kernel takes strides
         labels = hip.slic_superpixels(frames, args.num_segments, enforce_connectivity=args.enforce_connectivity)
-        labels = labels.to(torch.uint8).cpu().numpy()
-        for (_, out), seg in zip(batch, labels):
+        labels = labels.to(torch.uint8)
+        if args.png_encoder == "gpu":
+            for (_, out), data in zip(batch, hip.png_encode_files(labels.contiguous())):
+                os.makedirs(os.path.dirname(out), exist_ok=True)
+                with open(out, "wb") as f:
+                    f.write(data)
+            return len(batch)
+        for (_, out), seg in zip(batch, labels.cpu().numpy()):
             os.makedirs(os.path.dirname(out), exist_ok=True)
             Image.fromarray(seg).save(out)
         return len(batch)
