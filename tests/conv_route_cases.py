@@ -120,8 +120,9 @@ ROUTE_CASES = [
     ("dma32_tiny", (1, 1, 9, 64, 4, 1, 1, 0, 1), _all("DMA32_FASTK"), "H = 1, nine pixels, four channels"),
 ]
 
-# ConvLSTM (hip.convlstm_fused): ((B, H, W, Cx + C), C, k, pad) -> route.  The gate epilogue is not an exact function, so these
-# rows are route assertions only; parity stays with test_convlstm_fused_step_matches_torch.
+# ConvLSTM (hip.convlstm_fused): ((B, H, W, Cx + C), C, k, pad) -> route.  These rows are route assertions only; parity is
+# tests/test_hip_convlstm.py's, which runs every one of these routes (and the grouped, w128 and unfused gate kernels) on exact
+# cases whose gate epilogue saturates -- bit for bit -- and under a float64 bound (cases and their routes: tests/convlstm_cases.py).
 LSTM_ROUTE_CASES = [
     ("lstm_halo", ((1, 9, 20, 128), 64, 3, 1), "HALO3X3_LSTM", "3x3, Cin % 64 == 0: row-halo kernel with the fused cell update"),
     ("lstm_5x5", ((1, 9, 20, 128), 64, 5, 2), "LSTM_FASTK", "5x5 gates: general kernel with the fused cell update"),
