@@ -230,6 +230,12 @@ int oess_conv2d_fwd_bf16(const void* in, long long in_pix_stride, int B, int H, 
                          const void* residual, long long res_pix_stride, void* out_bf16, float* out_f32,
                          long long out_pix_stride, float* tile_stats, void* workspace, size_t workspace_bytes,
                          oess_stream_t stream);
+/* Statistics only: the 1x1 stride-1 bias-free convolution in front of a train-mode BatchNorm whose RESULT nobody reads (a frozen
+ * network run for its running statistics).  tile_stats gets what oess_conv2d_fwd_bf16 would write there (sums of the bf16-rounded
+ * results), no result is stored.  Exists where that call, with a dense aligned output, takes OESS_ROUTE_CONV1X1_W128
+ * (oess_conv2d_fwd_route says so); OESS_EINVAL elsewhere: run the storing call. */
+int oess_conv2d_stats_only_bf16(const void* in, long long in_pix_stride, int B, int H, int W, int Cin, const void* w_packed, int Cout,
+                                float* tile_stats, oess_stream_t stream);
 /* workspace (nullable): oess_conv2d_fwd_workspace_bytes(...) bytes of scratch for the split-K form that small-M / long-K layers
  * take (ASPP dilated 3x3 at output stride 16, models/deeplabv3.py:295-348: 140 workgroups x 288 K-slabs otherwise); the query
  * returns 0 for layers that run in one pass.  Without a workspace every layer runs in one pass (same result up to the
@@ -506,6 +512,13 @@ int oess_norm_apply_nhwc_bf16(const void* x, long long x_pix_stride, const float
                               const void* residual, long long res_pix_stride, int relu, int G, long long pixels_per_group,
                               int C, void* out, long long out_pix_stride, oess_stream_t stream);
 /* affine-free InstanceNorm (+ReLU) backward; s1/s2 are [G x C] scratch */
+/* The two-branch apply: out = act(x * scale + shift + bf16(x2 * scale2 + shift2)), G = 1.  x2 is the RAW result of a second
+ * branch (a bottleneck's downsample conv) with its own scale / shift; it is normalised and rounded to bf16 in registers, so the
+ * result carries the bits of oess_norm_apply_nhwc_bf16(x2 -> id) followed by oess_norm_apply_nhwc_bf16(x, residual = id) while
+ * id is never written.  x may alias out.  C % 8 == 0, C <= 2048; pixel strides in elements, multiples of 8. */
+int oess_norm_apply2_nhwc_bf16(const void* x, long long x_pix_stride, const float* scale, const float* shift, const void* x2,
+                               long long x2_pix_stride, const float* scale2, const float* shift2, int relu, long long pixels, int C,
+                               void* out, long long out_pix_stride, oess_stream_t stream);
 int oess_instnorm_bwd_nhwc_bf16(const void* x, long long x_pix_stride, const void* dy, long long dy_pix_stride,
                                 const float* mean, const float* rstd, int relu, int G, long long pixels_per_group, int C,
                                 float* s1, float* s2, void* dx, long long dx_pix_stride, float* partials, size_t partials_bytes,
@@ -839,6 +852,11 @@ int oess_pool_matrix_bwd(const void* matrix, const float* grad_k, int B, int h, 
  * ------------------------------------------------------------------------------------------ */
 int oess_maxpool3x3s2_fwd_nhwc_bf16(const void* in, long long in_pix_stride, int B, int H, int W, int C, void* out, long long out_pix_stride,
                                     unsigned char* idx, oess_stream_t stream);
+/* oess_maxpool3x3s2_fwd_nhwc_bf16 over a RAW map in front of a BatchNorm + ReLU: every tap is bf16(relu(x * scale + shift)) before
+ * the comparison (any sign of scale), out-of-range taps are skipped.  The bits of oess_norm_apply_nhwc_bf16(relu = 1) followed by
+ * the plain pool; the normalised map is never written.  Forward only, no winner index (the no-autograd path). */
+int oess_maxpool3x3s2_affine_relu_fwd_nhwc_bf16(const void* in, long long in_pix_stride, int B, int H, int W, int C, const float* scale,
+                                                const float* shift, void* out, long long out_pix_stride, oess_stream_t stream);
 int oess_maxpool3x3s2_bwd_nhwc_bf16(const void* grad_out, long long go_pix_stride, const unsigned char* idx, int B, int H, int W, int C,
                                     void* grad_in, long long gi_pix_stride, oess_stream_t stream);
 int oess_dropout_nhwc_bf16(const void* x, long long x_pix_stride, void* y, long long y_pix_stride, long long P, int C, float p,

@@ -134,6 +134,7 @@ SIGNATURES = {
     "oess_norm_stats_finalize_nhwc_bf16": (c_int, [c_vp, c_ll, c_int, c_ll, c_int, c_f, c_vp, c_vp, c_vp, c_vp, c_f, c_vp, c_vp,
                                                    c_vp, c_vp, c_vp, c_sz, c_vp]),
     "oess_norm_apply_nhwc_bf16": (c_int, [c_vp, c_ll, c_vp, c_vp, c_vp, c_ll, c_int, c_int, c_ll, c_int, c_vp, c_ll, c_vp]),
+    "oess_norm_apply2_nhwc_bf16": (c_int, [c_vp, c_ll, c_vp, c_vp, c_vp, c_ll, c_vp, c_vp, c_int, c_ll, c_int, c_vp, c_ll, c_vp]),
     "oess_instnorm_bwd_nhwc_bf16": (c_int, [c_vp, c_ll, c_vp, c_ll, c_vp, c_vp, c_int, c_int, c_ll, c_int, c_vp, c_vp, c_vp,
                                             c_ll, c_vp, c_sz, c_vp]),
     "oess_upsample_nearest2x_nhwc_bf16": (c_int, [c_vp, c_ll, c_int, c_int, c_int, c_int, c_vp, c_ll, c_vp]),
@@ -175,6 +176,7 @@ SIGNATURES = {
     "oess_e2vid_head_enc0_bf16": (c_int, [c_vp, c_ll, c_int, c_int, c_int, c_vp, c_vp, c_int, c_vp, c_vp, c_int, c_vp, c_ll, c_vp]),
     "oess_conv2d_fwd_bf16": (c_int, [c_vp, c_ll, c_int, c_int, c_int, c_int, c_vp, c_vp, c_int, c_int, c_int, c_int,
                                      c_int, c_int, c_int, c_vp, c_ll, c_vp, c_vp, c_ll, c_vp, c_vp, c_sz, c_vp]),
+    "oess_conv2d_stats_only_bf16": (c_int, [c_vp, c_ll, c_int, c_int, c_int, c_int, c_vp, c_int, c_vp, c_vp]),
     "oess_conv2d_fwd_workspace_bytes": (c_sz, [c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int]),
     "oess_conv2d_fwd_route": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
                                       c_int, c_ll, c_ll, c_ll, c_int, c_sz]),
@@ -191,6 +193,7 @@ SIGNATURES = {
     "oess_norm_reduce_finalize_tile_stats": (c_int, [c_vp, c_int, c_int, c_vp, c_vp, c_f, c_f, c_vp, c_vp, c_vp, c_vp, c_f,
                                                      c_vp, c_vp, c_vp, c_vp, c_vp]),
     "oess_maxpool3x3s2_fwd_nhwc_bf16": (c_int, [c_vp, c_ll, c_int, c_int, c_int, c_int, c_vp, c_ll, c_vp, c_vp]),
+    "oess_maxpool3x3s2_affine_relu_fwd_nhwc_bf16": (c_int, [c_vp, c_ll, c_int, c_int, c_int, c_int, c_vp, c_vp, c_vp, c_ll, c_vp]),
     "oess_maxpool3x3s2_bwd_nhwc_bf16": (c_int, [c_vp, c_ll, c_vp, c_int, c_int, c_int, c_int, c_vp, c_ll, c_vp]),
     "oess_dropout_nhwc_bf16": (c_int, [c_vp, c_ll, c_vp, c_ll, c_ll, c_int, c_f, c_u64, c_u64, c_vp]),
     "oess_aspp_pool_fwd_f32": (c_int, [c_vp, c_f, c_vp, c_vp, c_vp, c_vp, c_vp, c_f, c_f, c_int, c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_vp]),

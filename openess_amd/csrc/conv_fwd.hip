@@ -114,7 +114,7 @@ void conv_set_attrs() {
                              (const void*)&conv_fwd_dma_kernel<64, 128, 2, false>, (const void*)&conv_fwd_dma_kernel<64, 128, 2, true>,
                              (const void*)&conv_fwd_dma_kernel<128, 128, 2, false, 1>, (const void*)&conv_fwd_dma_kernel<128, 128, 2, true, 1>,
                              (const void*)&conv3x3_halo_kernel<0>, (const void*)&conv3x3_halo_kernel<1>, (const void*)&conv3x3_halo_group_kernel<1>,
-                             (const void*)&conv3x3_halo256_group_kernel, (const void*)&conv3x3_lstm_w128_kernel, (const void*)&conv1x1_w128_kernel, (const void*)&conv3x3_w128_kernel,
+                             (const void*)&conv3x3_halo256_group_kernel, (const void*)&conv3x3_lstm_w128_kernel, (const void*)&conv1x1_w128_kernel<true>, (const void*)&conv1x1_w128_kernel<false>, (const void*)&conv3x3_w128_kernel,
                              (const void*)&conv_fwd_dma_kernel<256, 256, 2, true>,
                              (const void*)&conv_fwd_dma_kernel<128, 128, 4, true, 0, 512>,
                              (const void*)&conv_fwd_dma32_kernel<128, true, 0, 3>, (const void*)&conv5x5s2_halo_kernel<false>,
@@ -391,7 +391,7 @@ int conv_launch(const ConvPlan& p, const ConvPtrs& q, oess_stream_t stream) {
         OESS_CASE(OESS_ROUTE_LSTM_SLOWK, conv_fwd_dma_kernel<128, 128, 2, false, 1>)
         OESS_CASE(OESS_ROUTE_SPLITK_FASTK, conv_fwd_dma_kernel<128, 128, 2, true>)        // (+ the reduce below)
         OESS_CASE(OESS_ROUTE_SPLITK_SLOWK, conv_fwd_dma_kernel<128, 128, 2, false>)
-        OESS_CASE(OESS_ROUTE_CONV1X1_W128, conv1x1_w128_kernel)
+        OESS_CASE(OESS_ROUTE_CONV1X1_W128, conv1x1_w128_kernel<true>)
         OESS_CASE(OESS_ROUTE_TILE256, conv_fwd_dma_kernel<256, 256, 2, true>)
         OESS_CASE(OESS_ROUTE_RING32, conv_fwd_dma32_kernel<128, true, 0, 3>)
         OESS_CASE(OESS_ROUTE_TILE64_FASTK, conv_fwd_dma_kernel<64, 128, 2, true>)
@@ -470,6 +470,21 @@ int oess_conv2d_fwd_bf16(const void* in, long long in_pix_stride, int B, int H, 
                                        in_pix_stride, out_pix_stride, res_pix_stride, workspace ? workspace_bytes : 0), &p);
     if (rc != OESS_OK) return rc;
     return conv_launch(p, ConvPtrs{in, w_packed, bias, residual, out_bf16, out_f32, tile_stats, nullptr, nullptr, nullptr, workspace}, stream);
+}
+
+int oess_conv2d_stats_only_bf16(const void* in, long long in_pix_stride, int B, int H, int W, int Cin, const void* w_packed, int Cout,
+                                float* tile_stats, oess_stream_t stream) {
+    if (!in || !w_packed || !tile_stats) return OESS_EINVAL;
+    // the plan of the storing call with a dense, aligned output: only where that is the w128 GEMM does the store-free form exist
+    ConvPlan p;
+    const int rc = conv_plan(conv_call(B, H, W, Cin, Cout, 1, 1, 1, 0, 1, 0, false, false, false, true, true, in_pix_stride, Cout, 0, 0), &p);
+    if (rc != OESS_OK) return rc;
+    if (p.route != OESS_ROUTE_CONV1X1_W128) return OESS_EINVAL;
+    conv_set_attrs();
+    const ConvArgs a = conv_bind(p, ConvPtrs{in, w_packed, nullptr, nullptr, nullptr, nullptr, tile_stats, nullptr, nullptr, nullptr, nullptr});
+    hipLaunchKernelGGL((conv1x1_w128_kernel<false>), p.grid, p.block, p.lds, (hipStream_t)stream, a);
+    OESS_HIP(hipGetLastError());
+    return OESS_OK;
 }
 
 size_t oess_conv2d_fwd_workspace_bytes(int B, int H, int W, int Cin, int Cout, int R, int S, int stride, int pad, int dil,

@@ -30,6 +30,9 @@ constexpr int G128_STAGE = 256 * 128;                     // 32 768 bytes: one o
 constexpr int G128_LDS = 5 * G128_STAGE;                  // 163 840: [pixels 0][pixels 1][weights 0][weights 1][pixels 2] (ds_read immediates are 16 bits)
 constexpr int g128_pstage_byte(int st) { return st == 2 ? 4 * G128_STAGE : st * G128_STAGE; }
 
+// STORE = false: the statistics-only form (a frozen layer whose result nobody reads, run for its BatchNorm's running statistics):
+// the result is rounded to bf16 and summed as ever, but never stored; a.out is not looked at.
+template <bool STORE>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) void conv1x1_w128_kernel(ConvArgs a) {
     extern __shared__ __attribute__((aligned(128))) unsigned char smem[];
     constexpr int MT = 4, NT = 4, P_INSTR = 8, B_INSTR = 8;
@@ -196,7 +199,11 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
     while (li < cnt) {
         // the tile's first operands (32 pieces, issued before the previous tile's result stores) have landed
         // (issued before the previous tile's 32 output + 32 statistics stores, which may stay in flight: vmcnt is 6 bits)
+        if constexpr (STORE) {
         if (stores_in_flight) { if (with_stats) asm volatile("s_waitcnt vmcnt(63)" ::: "memory"); else asm volatile("s_waitcnt vmcnt(32)" ::: "memory"); }
+        } else {                 // no output stores: the 32 statistics stores are all that is younger than the tile's first operands
+        if (stores_in_flight) { if (with_stats) asm volatile("s_waitcnt vmcnt(32)" ::: "memory"); else asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
+        }
         asm volatile("s_barrier" ::: "memory");
         W128_FOR(8, q, { frag_read(w128_c<0>{}, q, w128_c<0>{}, w128_c<0>{}, w128_c<0>{}); });
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
@@ -258,7 +265,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
                     __builtin_amdgcn_raw_buffer_store_b128(u32x4_t{pk[0][0], pk[0][1], pk[1][0], pk[1][1]}, rsO, cb + (i * 8 + j * 2) * 1024, 0, G128_AUX);
                     __builtin_amdgcn_raw_buffer_store_b128(u32x4_t{pk[2][0], pk[2][1], pk[3][0], pk[3][1]}, rsO, cb + (i * 8 + j * 2 + 1) * 1024, 0, G128_AUX);
                 } else
-                if (G128_ABL & 1) asm volatile("" :: "v"(pk[0][0]), "v"(pk[0][1]), "v"(pk[1][0]), "v"(pk[1][1]), "v"(pk[2][0]), "v"(pk[2][1]), "v"(pk[3][0]), "v"(pk[3][1]));
+                if ((G128_ABL & 1) || !STORE) asm volatile("" :: "v"(pk[0][0]), "v"(pk[0][1]), "v"(pk[1][0]), "v"(pk[1][1]), "v"(pk[2][0]), "v"(pk[2][1]), "v"(pk[3][0]), "v"(pk[3][1]));
                 else if (nt_out) {       // 4 x-expanding layers: the result (4 x the input) streams past the L2s (R6-8: -6 ... -10 %)
                 __builtin_amdgcn_raw_buffer_store_b128(u32x4_t{pk[0][0], pk[0][1], pk[1][0], pk[1][1]}, rsO, ov_t[i] + (j * 32) * 2, 0, 2);
                 __builtin_amdgcn_raw_buffer_store_b128(u32x4_t{pk[2][0], pk[2][1], pk[3][0], pk[3][1]}, rsO, ov_t[i] + (j * 32 + 16) * 2, 0, 2);

@@ -220,6 +220,42 @@ __global__ __launch_bounds__(THREADS) void apply_kernel(const uint16_t* __restri
     }
 }
 
+// apply_kernel with the residual still RAW: out = act(x*scale + shift + bf16(x2*scale2 + shift2)).  The second branch (the
+// bottleneck's downsample conv in front of its own BatchNorm) is normalised and rounded to bf16 in registers exactly as a
+// pass of apply_kernel over it would have stored it, so the result carries the bits of the two passes and the normalised
+// branch is never written or read back.  Same thread layout; G = 1.  NT2: x2 is dead after this pass -- streaming load.
+template <int NT2>
+__global__ __launch_bounds__(THREADS) void apply2_kernel(const uint16_t* __restrict__ x, int64_t xps,
+                                                         const float* __restrict__ scale, const float* __restrict__ shift,
+                                                         const uint16_t* __restrict__ x2, int64_t x2ps,
+                                                         const float* __restrict__ scale2, const float* __restrict__ shift2, int relu,
+                                                         int64_t pixels, int C, uint16_t* __restrict__ out, int64_t ops) {
+    const int cl = C >> 3;
+    const int rows = THREADS / cl;
+    const int lane_c = threadIdx.x % cl, row = threadIdx.x / cl;
+    if (row >= rows) return;
+    const int c0 = lane_c * 8;
+    float sc[8], sh[8], sc2[8], sh2[8];
+#pragma unroll
+    for (int k = 0; k < 8; ++k) { sc[k] = scale[c0 + k]; sh[k] = shift[c0 + k]; sc2[k] = scale2[c0 + k]; sh2[k] = shift2[c0 + k]; }
+    for (int64_t pix = (int64_t)blockIdx.x * rows + row; pix < pixels; pix += (int64_t)gridDim.x * rows) {
+        Pack8 v, r, id;
+        float f[8];
+        v.q = *reinterpret_cast<const uint4*>(x + pix * xps + c0);
+        if (NT2) r.q = nt_load16(x2 + pix * x2ps + c0); else r.q = *reinterpret_cast<const uint4*>(x2 + pix * x2ps + c0);
+#pragma unroll
+        for (int k = 0; k < 8; ++k) f[k] = bf16_to_f32(r.h[k]) * sc2[k] + sh2[k];
+        id.q = pack_bf16x8(f);                       // the rounding the first of the two passes stores with
+#pragma unroll
+        for (int k = 0; k < 8; ++k) {
+            f[k] = bf16_to_f32(v.h[k]) * sc[k] + sh[k];
+            f[k] += bf16_to_f32(id.h[k]);
+            if (relu) f[k] = fmaxf(f[k], 0.f);
+        }
+        *reinterpret_cast<uint4*>(out + pix * ops + c0) = pack_bf16x8(f);
+    }
+}
+
 // Normalisation backward: g = dy * mask;  dx = gamma * rstd * (g - s1/N - xhat * s2/N);  d(residual) = g
 // (gamma == nullptr: affine-free InstanceNorm; yout != nullptr: ReLU mask taken from the stored output)
 __global__ __launch_bounds__(THREADS) void in_bwd_apply_kernel(const uint16_t* __restrict__ x, int64_t xps,
@@ -848,6 +884,24 @@ int oess_norm_apply_nhwc_bf16(const void* x, long long x_pix_stride, const float
     if (nt == 1) OESS_APPLY_LAUNCH(1); else if (nt == 2) OESS_APPLY_LAUNCH(2); else if (nt == 3) OESS_APPLY_LAUNCH(3);
     else if (nt == 6) OESS_APPLY_LAUNCH(6); else if (nt == 4) OESS_APPLY_LAUNCH(4); else OESS_APPLY_LAUNCH(0);
 #undef OESS_APPLY_LAUNCH
+    OESS_HIP(hipGetLastError());
+    return OESS_OK;
+}
+
+int oess_norm_apply2_nhwc_bf16(const void* x, long long x_pix_stride, const float* scale, const float* shift, const void* x2,
+                               long long x2_pix_stride, const float* scale2, const float* shift2, int relu, long long pixels, int C,
+                               void* out, long long out_pix_stride, oess_stream_t stream) {
+    if (!x || !scale || !shift || !x2 || !scale2 || !shift2 || !out || pixels <= 0 || C <= 0 || (C & 7) || (x_pix_stride & 7) ||
+        (x2_pix_stride & 7) || (out_pix_stride & 7) || x_pix_stride < C || x2_pix_stride < C || out_pix_stride < C)
+        return OESS_EINVAL;
+    if ((C >> 3) > THREADS) return OESS_EINVAL;
+    // load policy of x2 (OESS_APPLY2_NT = 0 / 1 for A/B): EXPERIMENTS.md R6-13 has the measurement behind the default
+    static const int nt2 = [] { const char* e = getenv("OESS_APPLY2_NT"); return e ? atoi(e) : 1; }();
+#define OESS_APPLY2_LAUNCH(NT2) hipLaunchKernelGGL(apply2_kernel<NT2>, apply_grid(pixels, 1, C), dim3(THREADS), 0, (hipStream_t)stream, \
+                       (const uint16_t*)x, (int64_t)x_pix_stride, scale, shift, (const uint16_t*)x2, (int64_t)x2_pix_stride, scale2, shift2, \
+                       relu, (int64_t)pixels, C, (uint16_t*)out, (int64_t)out_pix_stride)
+    if (nt2) OESS_APPLY2_LAUNCH(1); else OESS_APPLY2_LAUNCH(0);
+#undef OESS_APPLY2_LAUNCH
     OESS_HIP(hipGetLastError());
     return OESS_OK;
 }

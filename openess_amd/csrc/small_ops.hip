@@ -71,6 +71,54 @@ __global__ __launch_bounds__(THREADS) void maxpool3x3s2_fwd_kernel(const uint16_
     }
 }
 
+// The same pool over a RAW map in front of a BatchNorm + ReLU (the ResNet stem without autograd): every tap is
+// bf16(relu(x * scale + shift)) -- the value a normalisation pass would have stored, rounding included (pack_bf16x8) -- before
+// it is compared, so the normalised map is never written.  No monotonicity is assumed (scale may be negative or zero: the
+// affine map runs per tap, not on the maximum).  Out-of-range taps are skipped, not zero.  Forward only, no winner index.
+__global__ __launch_bounds__(THREADS) void maxpool3x3s2_affine_relu_kernel(const uint16_t* __restrict__ in, int64_t ips, int B, int H, int W,
+                                                                           int C, int Ho, int Wo, const float* __restrict__ scale,
+                                                                           const float* __restrict__ shift, uint16_t* __restrict__ out,
+                                                                           int64_t ops) {
+    const int c8 = C >> 3;
+    const int64_t total = (int64_t)B * Ho * Wo * c8;
+    for (int64_t i = (int64_t)blockIdx.x * THREADS + threadIdx.x; i < total; i += (int64_t)gridDim.x * THREADS) {
+        const int c0 = (int)(i % c8) * 8;
+        int64_t p = i / c8;
+        const int ox = (int)(p % Wo); p /= Wo;
+        const int oy = (int)(p % Ho);
+        const int b = (int)(p / Ho);
+        float sc[8], sh[8], mx[8];
+#pragma unroll
+        for (int k = 0; k < 8; ++k) { sc[k] = scale[c0 + k]; sh[k] = shift[c0 + k]; mx[k] = -__builtin_inff(); }
+#pragma unroll
+        for (int dy = 0; dy < 3; ++dy) {
+            const int iy = oy * 2 - 1 + dy;
+            if ((unsigned)iy >= (unsigned)H) continue;
+#pragma unroll
+            for (int dx = 0; dx < 3; ++dx) {
+                const int ix = ox * 2 - 1 + dx;
+                if ((unsigned)ix >= (unsigned)W) continue;
+                V8 v, t;
+                v.q = *reinterpret_cast<const uint4*>(in + (((int64_t)b * H + iy) * W + ix) * ips + c0);
+                float f[8];
+#pragma unroll
+                for (int k = 0; k < 8; ++k) f[k] = fmaxf(bf16_to_f32(v.h[k]) * sc[k] + sh[k], 0.f);
+                t.q = pack_bf16x8(f);
+#pragma unroll
+                for (int k = 0; k < 8; ++k) {
+                    const float g = bf16_to_f32(t.h[k]);
+                    if (g > mx[k] || g != g) mx[k] = g;
+                }
+            }
+        }
+        V8 o;
+#pragma unroll
+        for (int k = 0; k < 8; ++k) o.h[k] = f32_to_bf16(mx[k]);        // exact: the maximum is one of the bf16 taps
+        const int64_t po = ((int64_t)b * Ho + oy) * Wo + ox;
+        *reinterpret_cast<uint4*>(out + po * ops + c0) = o.q;
+    }
+}
+
 // dx[b, y, x, c] = sum over the (at most four) windows that contain (y, x) of dy[window, c] where that window's winner is
 // this pixel: a gather, every input pixel written once, fixed summation order (oy, then ox).
 __global__ __launch_bounds__(THREADS) void maxpool3x3s2_bwd_kernel(const uint16_t* __restrict__ dy, int64_t dps, const uint8_t* __restrict__ idx,
@@ -254,6 +302,18 @@ int oess_maxpool3x3s2_fwd_nhwc_bf16(const void* in, long long in_pix_stride, int
     const int Ho = (H - 1) / 2 + 1, Wo = (W - 1) / 2 + 1;
     hipLaunchKernelGGL(maxpool3x3s2_fwd_kernel, dim3(grid_for((int64_t)B * Ho * Wo * (C >> 3))), dim3(THREADS), 0, (hipStream_t)stream,
                        (const uint16_t*)in, (int64_t)in_pix_stride, B, H, W, C, Ho, Wo, (uint16_t*)out, (int64_t)out_pix_stride, idx);
+    OESS_HIP(hipGetLastError());
+    return OESS_OK;
+}
+
+int oess_maxpool3x3s2_affine_relu_fwd_nhwc_bf16(const void* in, long long in_pix_stride, int B, int H, int W, int C, const float* scale,
+                                                const float* shift, void* out, long long out_pix_stride, oess_stream_t stream) {
+    if (!in || !out || !scale || !shift || B <= 0 || H <= 0 || W <= 0 || C <= 0 || (C & 7) || (in_pix_stride & 7) || (out_pix_stride & 7) ||
+        in_pix_stride < C || out_pix_stride < C || ((uintptr_t)in & 15) || ((uintptr_t)out & 15))
+        return OESS_EINVAL;
+    const int Ho = (H - 1) / 2 + 1, Wo = (W - 1) / 2 + 1;
+    hipLaunchKernelGGL(maxpool3x3s2_affine_relu_kernel, dim3(grid_for((int64_t)B * Ho * Wo * (C >> 3))), dim3(THREADS), 0, (hipStream_t)stream,
+                       (const uint16_t*)in, (int64_t)in_pix_stride, B, H, W, C, Ho, Wo, scale, shift, (uint16_t*)out, (int64_t)out_pix_stride);
     OESS_HIP(hipGetLastError());
     return OESS_OK;
 }

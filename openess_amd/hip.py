@@ -6,6 +6,7 @@ raises if the library is missing or a tensor is not on the GPU -- there is no CP
 """
 import ctypes
 import operator
+from typing import NamedTuple
 
 import torch
 
@@ -2571,25 +2572,64 @@ def channel_sum(x_nhwc):
     return st[0]
 
 
-def conv_bn_train_nhwc(x, packed, Cout, R, S, stride, pad, dil, bn, relu=False, residual=None, out=None):
+ROUTE_CONV1X1_W128 = 14       # OESS_ROUTE_CONV1X1_W128 of include/oess.h (values are stable)
+BN_FUSED_MAX_TILES = 320      # up to here conv_bn_train_nhwc takes the one-launch statistics + apply kernel (Cout % 64 == 0)
+
+
+def conv_bn_train_separate_apply(M, Cout):
+    """True where conv_bn_train_nhwc over M output pixels runs conv + reduce_finalize + apply as separate launches with the
+    scale / shift in memory between them: the only route on which an apply can be deferred, fused elsewhere or dropped
+    (`defer`, `residual_affine`, `want_output`).  Small maps take ONE statistics + apply launch that has no such seam."""
+    return (M + 127) // 128 > BN_FUSED_MAX_TILES
+
+
+class RawBN(NamedTuple):
+    """conv_bn_train_nhwc(defer=True): the raw conv result (NHWC bf16) and the BatchNorm's fp32 [1, C] scale / shift for it.  The
+    running statistics have moved and the batch counter is bumped; only y * scale + shift is still to be applied."""
+    y: torch.Tensor
+    scale: torch.Tensor
+    shift: torch.Tensor
+
+
+def conv_bn_train_nhwc(x, packed, Cout, R, S, stride, pad, dil, bn, relu=False, residual=None, out=None, defer=False,
+                       residual_affine=None, want_output=True):
     """Bias-free conv + nn.BatchNorm2d in TRAIN mode [+ residual] [+ ReLU], inference form (frozen teacher): the batch
     statistics come from the conv epilogue's fp32 accumulators (no separate statistics pass over the activation).
-    `out`: optional NHWC bf16 destination view (e.g. a channel slice of a concat buffer)."""
+    `out`: optional NHWC bf16 destination view (e.g. a channel slice of a concat buffer).
+    Three forms exist only where conv_bn_train_separate_apply(M, Cout) holds (ValueError elsewhere: the caller asks first):
+      defer=True            no apply: returns RawBN(raw result, scale, shift) for a consumer that applies them itself;
+      residual_affine=RawBN the residual is another layer's deferred result: ONE pass normalises both branches
+                            (oess_norm_apply2_nhwc_bf16: the bits of that layer's apply followed by this one's);
+      want_output=False     nobody reads the result, the call is made for the running statistics: no apply, returns None; a 1x1
+                            layer on the w128 GEMM does not store its result either (oess_conv2d_stats_only_bf16)."""
     lib = _lib.load()
-    B, H, W, _, _ = _nhwc_geom(x)
+    B, H, W, _, xps = _nhwc_geom(x)
     Ho = (H + 2 * pad - dil * (R - 1) - 1) // stride + 1
     Wo = (W + 2 * pad - dil * (S - 1) - 1) // stride + 1
     M = B * Ho * Wo
     tiles = (M + 127) // 128
+    special = defer or residual_affine is not None or not want_output
+    if special:
+        if not conv_bn_train_separate_apply(M, Cout):
+            raise ValueError(f"conv_bn_train_nhwc: M = {M} takes the one-launch statistics + apply kernel: nothing to defer or drop")
+        if defer + (residual_affine is not None) + (not want_output) > 1 or (residual_affine is not None and residual is not None):
+            raise ValueError("conv_bn_train_nhwc: defer, residual_affine and want_output=False exclude each other")
     part = torch.empty((tiles, 2, Cout), dtype=torch.float32, device=x.device)
-    y = conv2d_nhwc(x, packed, None, Cout, R, S, stride, pad, dil, tile_stats=part, out=out)
-    _, _, _, _, yps = _nhwc_geom(y)
+    y = None
+    if not want_output and R == 1 and S == 1 and stride == 1 and pad == 0 and out is None and \
+            conv2d_route((B, H, W, x.shape[3]), None, False, Cout, 1, 1, tile_stats=True, in_pix_stride=xps) == ROUTE_CONV1X1_W128:
+        _need_gpu(x, packed)
+        _lib.check(lib.oess_conv2d_stats_only_bf16(_ptr(x), xps, B, H, W, x.shape[3], _ptr(packed), Cout, _ptr(part), _stream()),
+                   "oess_conv2d_stats_only_bf16")
+    else:
+        y = conv2d_nhwc(x, packed, None, Cout, R, S, stride, pad, dil, tile_stats=part, out=out)
+        _, _, _, _, yps = _nhwc_geom(y)
     mom = 0.0 if bn.momentum is None else bn.momentum
     rps = 0
     if residual is not None:
         _, _, _, _, rps = _nhwc_geom(residual)
     from . import engine as _engine
-    if tiles <= 320 and Cout % 64 == 0:
+    if not special and tiles <= BN_FUSED_MAX_TILES and Cout % 64 == 0:
         # small map: statistics + apply in ONE launch (every workgroup reduces the partials of its 64 channels itself)
         _lib.check(lib.oess_norm_tile_stats_apply_nhwc_bf16(_ptr(part), tiles, Cout, float(M), float(bn.eps), _ptr(bn.weight.detach()),
                                                             _ptr(bn.bias.detach()), _ptr(bn.running_mean), _ptr(bn.running_var),
@@ -2603,10 +2643,44 @@ def conv_bn_train_nhwc(x, packed, Cout, R, S, stride, pad, dil, bn, relu=False, 
                                                         float(M), float(bn.eps), _ptr(bn.weight.detach()), _ptr(bn.bias.detach()),
                                                         _ptr(bn.running_mean), _ptr(bn.running_var), float(mom), _ptr(st[2]), _ptr(st[3]),
                                                         _ptr(st[4]), _ptr(st[5]), _stream()), "oess_norm_reduce_finalize_tile_stats")
+    if not want_output:
+        _engine.bump_bn_counter(bn)
+        return None
+    if defer:
+        _engine.bump_bn_counter(bn)
+        return RawBN(y, st[4], st[5])
+    if residual_affine is not None:
+        r = residual_affine
+        if tuple(r.y.shape) != tuple(y.shape) or r.scale.numel() != Cout or r.shift.numel() != Cout:
+            raise ValueError(f"conv_bn_train_nhwc: residual_affine of shape {tuple(r.y.shape)} for a result of {tuple(y.shape)}")
+        _, _, _, _, r2ps = _nhwc_geom(r.y)
+        _lib.check(lib.oess_norm_apply2_nhwc_bf16(_ptr(y), yps, _ptr(st[4]), _ptr(st[5]), _ptr(r.y), r2ps, _ptr(r.scale), _ptr(r.shift),
+                                                  int(relu), M, Cout, _ptr(y), yps, _stream()), "oess_norm_apply2_nhwc_bf16")
+        _engine.bump_bn_counter(bn)
+        return y
     _lib.check(lib.oess_norm_apply_nhwc_bf16(_ptr(y), yps, _ptr(st[4]), _ptr(st[5]), _ptr(residual), rps, int(relu), 1, M, Cout,
                                              _ptr(y), yps, _stream()), "oess_norm_apply_nhwc_bf16")
     _engine.bump_bn_counter(bn)
     return y
+
+
+def max_pool_3x3s2_affine_relu(x, scale, shift):
+    """max_pool_3x3s2(relu(x * scale + shift) rounded to bf16) on a logical NCHW channels_last bf16 tensor, C % 8 == 0, without
+    writing the normalised map: the ResNet stem behind a deferred train-mode BatchNorm (conv_bn_train_nhwc(defer=True)).
+    scale / shift: fp32, C elements.  No autograd (no winner index is kept)."""
+    _need_gpu(x, scale, shift)
+    if x.dtype != torch.bfloat16 or x.stride(1) != 1 or x.shape[1] % 8:
+        raise ValueError("max_pool_3x3s2_affine_relu needs a channels_last bf16 tensor with C % 8 == 0")
+    lib = _lib.load()
+    xn = x.permute(0, 2, 3, 1)
+    B, H, W, C, ps = _nhwc_geom(xn)
+    if scale.dtype != torch.float32 or shift.dtype != torch.float32 or scale.numel() != C or shift.numel() != C or \
+            not scale.is_contiguous() or not shift.is_contiguous():
+        raise ValueError("max_pool_3x3s2_affine_relu: scale / shift are contiguous fp32 tensors of C elements")
+    y = torch.empty((B, (H - 1) // 2 + 1, (W - 1) // 2 + 1, C), dtype=torch.bfloat16, device=x.device)
+    _lib.check(lib.oess_maxpool3x3s2_affine_relu_fwd_nhwc_bf16(_ptr(xn), ps, B, H, W, C, _ptr(scale), _ptr(shift), _ptr(y), C, _stream()),
+               "oess_maxpool3x3s2_affine_relu_fwd_nhwc_bf16")
+    return y.permute(0, 3, 1, 2)
 
 
 # ------------------------------------------------------------------------------------------ small ops of the DeepLabv3 path (round 5)

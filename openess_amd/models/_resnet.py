@@ -45,11 +45,30 @@ class HipMaxPool2d(nn.MaxPool2d):
         return super().forward(x)
 
 
-def conv_bn(conv, bn, x, relu=False, residual=None, out=None, skip_in=None, skip_out=None):
+def conv_bn_separable(conv, bn, x):
+    """True where conv_bn(conv, bn, x) runs as conv + BatchNorm finalize + apply pass with scale / shift in memory in between:
+    no autograd, train-mode BatchNorm, bias-free conv, and a map too large for the one-launch statistics + apply kernel
+    (hip.conv_bn_train_separate_apply).  Only there does conv_bn take defer / residual_affine / want_output=False; every other
+    route (autograd, eval-mode fold, small maps) has no apply pass of its own to move."""
+    if torch.is_grad_enabled() and (conv.weight.requires_grad or x.requires_grad or bn.weight.requires_grad):
+        return False
+    if conv.bias is not None or not bn.training or not x.is_cuda:
+        return False
+    k, s, p, d = conv.kernel_size[0], conv.stride[0], conv.padding[0], conv.dilation[0]
+    B, _, H, W = x.shape
+    Ho, Wo = (H + 2 * p - d * (k - 1) - 1) // s + 1, (W + 2 * p - d * (k - 1) - 1) // s + 1
+    return hip.conv_bn_train_separate_apply(B * Ho * Wo, conv.out_channels)
+
+
+def conv_bn(conv, bn, x, relu=False, residual=None, out=None, skip_in=None, skip_out=None, defer=False, residual_affine=None,
+            want_output=True):
     """conv -> BatchNorm2d [-> + residual] [-> ReLU] with nn.BatchNorm2d semantics for both bn.training states.
     No autograd needed (frozen teacher, validation): train-mode BN takes its batch statistics from the conv
     epilogue (no statistics pass); eval-mode BN is folded into the packed weights and the whole tail is the
-    conv epilogue.  With autograd: MFMA conv + library BatchNorm."""
+    conv epilogue.  With autograd: MFMA conv + library BatchNorm.
+    defer / residual_affine / want_output: the forms of hip.conv_bn_train_nhwc, legal where conv_bn_separable() holds."""
+    if (defer or residual_affine is not None or not want_output) and not conv_bn_separable(conv, bn, x):
+        raise ValueError("conv_bn: defer / residual_affine / want_output=False need the separate-apply route (conv_bn_separable)")
     needs_grad = torch.is_grad_enabled() and (conv.weight.requires_grad or x.requires_grad or bn.weight.requires_grad)
     if needs_grad and conv.bias is None and bn.training and bn.weight is not None and bn.running_mean is not None and \
             conv.out_channels % 8 == 0 and conv.out_channels <= 2048:
@@ -80,7 +99,10 @@ def conv_bn(conv, bn, x, relu=False, residual=None, out=None, skip_in=None, skip
         pw = conv._pw.get(conv.weight, None, None, cin_pad=x.shape[1])
         y = hip.conv_bn_train_nhwc(engine.nhwc(x), pw.packed, conv.out_channels, k, k, s, p, d, bn, relu=relu,
                                    residual=None if residual is None else engine.nhwc(residual),
-                                   out=None if out is None else engine.nhwc(out))
+                                   out=None if out is None else engine.nhwc(out), defer=defer, residual_affine=residual_affine,
+                                   want_output=want_output)
+        if y is None or defer:                       # nothing to read / hip.RawBN (NHWC) for residual_affine or the stem's pool
+            return y
         return engine.from_nhwc(y)
     pw = conv._pw_folded.get(conv.weight, None, bn, cin_pad=x.shape[1])
     return engine.conv2d_infer(x, pw, conv.out_channels, k, s, p, d, relu=relu, residual=residual, out=out)
@@ -182,6 +204,12 @@ def conv1x1(in_planes, out_planes, stride=1):
 
 class Bottleneck(nn.Module):
     expansion = 4
+    # No autograd, train-mode BatchNorm, large maps (conv_bn_separable): the downsample branch's BatchNorm is applied inside the
+    # block-end pass instead of by a pass of its own (False: two passes, A/B).  Same bits either way.
+    fuse_downsample_bn = True
+    # forward(x, want_output=False) on the same route: conv3 keeps its BatchNorm side effects but stores no result and the
+    # block-end pass is not run (False: the whole block runs and its result is dropped, A/B).
+    skip_dead_output = True
 
     def __init__(self, inplanes, planes, stride=1, downsample=None, groups=1, base_width=64, dilation=1, norm_layer=None):
         super().__init__()
@@ -209,7 +237,9 @@ class Bottleneck(nn.Module):
                 return False
         return True
 
-    def forward(self, x):
+    def forward(self, x, want_output=True):
+        """want_output=False: the caller reads nothing of the result (a frozen network run for its running statistics); every
+        BatchNorm of the block still moves as in a full forward.  Returns None then."""
         identity = x
         # no downsample: x feeds conv1 AND the residual add -> one shared hand-over slot instead of autograd's gradient sum
         skip = {} if (self.downsample is None and self._one_node_path(x)) else None
@@ -223,9 +253,20 @@ class Bottleneck(nn.Module):
         self._skip_slot = skip
         out = conv_bn(self.conv1, self.bn1, x, relu=True, skip_in=skip)
         out = conv_bn(self.conv2, self.bn2, out, relu=True)
+        separable = conv_bn_separable(self.conv3, self.bn3, out)
+        dead = not want_output and self.skip_dead_output and separable
         if self.downsample is not None:
+            if self.fuse_downsample_bn and separable and not dead and conv_bn_separable(self.downsample[0], self.downsample[1], x):
+                raw = conv_bn(self.downsample[0], self.downsample[1], x, defer=True)
+                return self._out(conv_bn(self.conv3, self.bn3, out, relu=True, residual_affine=raw), want_output)
             identity = conv_bn(self.downsample[0], self.downsample[1], x)
-        return conv_bn(self.conv3, self.bn3, out, relu=True, residual=identity, skip_out=skip)
+        if dead:
+            return conv_bn(self.conv3, self.bn3, out, want_output=False)
+        return self._out(conv_bn(self.conv3, self.bn3, out, relu=True, residual=identity, skip_out=skip), want_output)
+
+    @staticmethod
+    def _out(y, want_output):
+        return y if want_output else None
 
     def forward_f32(self, x, layers):
         """The block in fp32 on one F32Layers set: three conv + BatchNorm steps, four with a downsample conv (the residual's
@@ -301,17 +342,32 @@ class ResNet(nn.Module):
                                 dilation=self.dilation, norm_layer=norm_layer))
         return nn.Sequential(*layers)
 
+    # No autograd, train-mode BatchNorm, large maps (conv_bn_separable): bn1 + ReLU are applied by the max pool to each tap as it
+    # loads, the normalised stem map is never written (False: apply pass, then the plain pool, A/B).  Same bits either way.
+    fuse_stem_pool = True
+
     def stem(self, x):
+        mp = self.maxpool
+        if self.fuse_stem_pool and isinstance(mp, HipMaxPool2d) and conv_bn_separable(self.conv1, self.bn1, x) and \
+                (mp.kernel_size, mp.stride, mp.padding, mp.dilation, mp.ceil_mode) == (3, 2, 1, 1, False):
+            raw = conv_bn(self.conv1, self.bn1, x, defer=True)
+            return hip.max_pool_3x3s2_affine_relu(engine.from_nhwc(raw.y), raw.scale.view(-1), raw.shift.view(-1))
         x = conv_bn(self.conv1, self.bn1, x, relu=True)
         return self.maxpool(x)
 
-    def features(self, x):
+    def features(self, x, want_output=True):
+        """want_output=False: the call is made for the train-mode BatchNorm updates alone (nobody reads the layer4 map): the last
+        block skips what only its result needs (Bottleneck.forward) and None comes back."""
         with engine.defer_bn_counters():             # 53 num_batches_tracked bumps -> one multi-tensor add
             x = self.stem(x)
             x = self.layer1(x)
             x = self.layer2(x)
             x = self.layer3(x)
-            return self.layer4(x)
+            if want_output:
+                return self.layer4(x)
+            for block in self.layer4[:-1]:
+                x = block(x)
+            return self.layer4[-1](x, want_output=False)
 
     def features_fp32(self, x):
         """features() in fp32: x fp32 [B, 3, H, W], any layout -> the fp32 channels_last layer4 map.  Per BatchNorm the folded

@@ -15,8 +15,8 @@ class ResNetEncoder(ResNet):
         del self.fc
         del self.avgpool
 
-    def forward(self, x):
-        return self.features(x)
+    def forward(self, x, want_output=True):
+        return self.features(x, want_output=want_output)
 
     def load_state_dict(self, state_dict, **kwargs):
         state_dict.pop("fc.bias", None)
@@ -78,14 +78,16 @@ class DilationFeatureExtractor(nn.Module):
     def forward(self, x):
         return self.head(self.encode(x))
 
-    def encode(self, x):
+    def encode(self, x, want_output=True):
         """The frozen part (preprocessing + dilated ResNet-50, train-mode BatchNorm side effects included): depends on no trainable
-        weight, so a training loop may run it for the NEXT batch while the current one is still in its backward pass."""
+        weight, so a training loop may run it for the NEXT batch while the current one is still in its backward pass.
+        want_output=False: the caller reads no features and runs the encoder for those side effects alone (pixel distillation);
+        every running statistic and batch counter moves as ever, the last block's result is not produced, None comes back."""
         if self.preprocessing:
             x = self.preprocessing(x)
         x = engine.to_cl_bf16(x)
         with torch.no_grad():                      # encoder params are frozen (image_model.py:113-114)
-            return self.encoder(x)
+            return self.encoder(x, want_output=want_output)
 
     def head(self, x):
         """The trainable 1x1 decoder + x4 bilinear + L2 normalisation on the encoder's output."""

@@ -275,7 +275,8 @@ class PretrainStep:
                 # Pixel distillation: nothing reads the teacher's features (pretrain_trainer.py:434 computes them and drops them).
                 # What the call leaves behind are the train-mode BatchNorm updates of the ENCODER; the head (1x1 conv, x4 bilinear,
                 # L2 normalise: no state) is dead code here exactly like the E2VID decoder whose outputs every caller discards.
-                h.teacher_enc = self.model_frame.encode(frame)
+                # So is the encoder's own last normalisation pass: want_output=False (h.teacher_enc stays None).
+                self.model_frame.encode(frame, want_output=False)
         if self.config_option == 'frame2voxel':
             event = batch[0]
             with ctx(F if cuda else None):
