@@ -639,6 +639,27 @@ int oess_head_render(const void* x, int is_bf16, long long pix_stride, int B, in
                      oess_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Flip and multi-scale inference (K39): oess_segment_render's outputs from the MEAN class probability of V logit maps of the same
+ * B and K, without any full-resolution [B x K x H x W] tensor.  1 <= V <= OESS_RENDER_MAX_VIEWS.
+ *   logits, pix_strides, hs, ws, flips: HOST arrays of V entries (copied into the kernel's arguments, nothing is uploaded); view v
+ *     is NHWC [B x hs[v] x ws[v] x K] on the device, fp32 or bf16 (is_bf16, one type for all views), with its pixel stride.
+ *   Class values of view v at output pixel (oy, ox): oess_segment_render's values at (oy, ox'), ox' = flips[v] ? W - 1 - ox : ox
+ *     (raw at the output size, otherwise the fp32 blend): a flipped view is the view rendered as given and then mirrored.
+ *   q_vk = exp(v_vk - m_v) / S_v (m_v the view's maximum, S_v = sum_k exp(v_vk - m_v), fp32), p_k = (sum_v q_vk) * (1.0f / V) in
+ *     ascending v.  The label is torch.argmax's over p_k (first index among equal maxima, a NaN above everything), conf = p_label;
+ *     threshold, ignore_label, palette, grey and the integer blend are oess_segment_render's.
+ *   A view with a NaN, a +inf or only -inf at a pixel makes every p_k NaN there: label 0, NaN conf (which keeps its label).
+ *   One lane owns a pixel, no atomics: two calls give the same bits.
+ * OESS_EINVAL, nothing launched, outputs untouched: a null array or view pointer, V outside 1 ... 8, a flip other than 0 / 1, a
+ * non-positive size, a stride below K, what oess_segment_render refuses of the shared arguments, B * H or B * hs[v] above
+ * 2^31 - 1, or an element count that overflows 64-bit byte offsets.  Adding this entry left OESS_ABI_VERSION unchanged. */
+#define OESS_RENDER_MAX_VIEWS 8
+int oess_segment_render_ensemble(const void* const* logits, const long long* pix_strides, const int* hs, const int* ws,
+                                 const int* flips, int V, int is_bf16, int B, int K, int H, int W, int align_corners,
+                                 const uint8_t* palette, const uint8_t* grey, int alpha256, float min_conf, int ignore_label,
+                                 uint8_t* labels, float* conf, uint8_t* rgb, oess_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * MaskCLIP ViT-B/16 image tower (models/maskclip_model.py:448-541 TransformerEncoderLayer, :545-851 VisionTransformer):
  * the non-GEMM pieces.  The linear layers (patch embedding, in_proj, out_proj, FFN, proj) run on oess_conv2d_fwd_bf16 as
  * 1x1 / 16x16 convolutions over the token axis (bias, residual and GELU fused in the epilogue).

@@ -107,6 +107,8 @@ SIGNATURES = {
                                     c_vp, c_vp, c_vp, c_vp]),
     "oess_segment_render_grouped": (c_int, [c_vp, c_int, c_ll, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_vp, c_vp,
                                             c_vp, c_int, c_f, c_int, c_vp, c_vp, c_vp, c_vp]),
+    "oess_segment_render_ensemble": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_vp, c_vp,
+                                             c_int, c_f, c_int, c_vp, c_vp, c_vp, c_vp]),
     "oess_head_render_max_names": (c_sz, [c_int]),
     "oess_head_render": (c_int, [c_vp, c_int, c_ll, c_int, c_int, c_int, c_int, c_vp, c_vp, c_int, c_int, c_vp, c_vp, c_vp, c_int, c_f,
                                  c_int, c_vp, c_vp, c_vp, c_vp]),

@@ -73,10 +73,9 @@ __device__ __forceinline__ void load_palette(Stage& s, const Render& r, int K) {
     }
 }
 
-// A pixel's outputs from its (index, sum): conf as one dword, the label and colour bytes into the staging rows at the byte phase
-// of the row's global address.  pix: the pixel's index in [B][H][W].
-__device__ __forceinline__ void emit(Stage& s, const Render& r, int K, int64_t pix, int lphase, int cphase, int idx, float sum) {
-    const float conf = 1.f / sum;
+// A pixel's outputs from its (index, confidence): conf as one dword, the label and colour bytes into the staging rows at the byte
+// phase of the row's global address.  pix: the pixel's index in [B][H][W].
+__device__ __forceinline__ void emit_conf(Stage& s, const Render& r, int K, int64_t pix, int lphase, int cphase, int idx, float conf) {
     int label = idx;
     if (conf < r.min_conf) label = r.ignore_label;                  // false for a NaN confidence: the label stays
     if (r.conf) r.conf[pix] = conf;
@@ -91,6 +90,11 @@ __device__ __forceinline__ void emit(Stage& s, const Render& r, int K, int64_t p
         uint8_t* d = s.rgb + cphase + 3 * threadIdx.x;
         d[0] = (uint8_t)c0; d[1] = (uint8_t)c1; d[2] = (uint8_t)c2;
     }
+}
+
+// The same from a pixel's (index, sum of exp(v - maximum)): the confidence is 1 / sum.
+__device__ __forceinline__ void emit(Stage& s, const Render& r, int K, int64_t pix, int lphase, int cphase, int idx, float sum) {
+    emit_conf(s, r, K, pix, lphase, cphase, idx, 1.f / sum);
 }
 
 // n staged bytes, stage[phase ... phase + n), to g (phase = g & 3): every dword that lies inside the range is one aligned

@@ -2326,6 +2326,57 @@ def segment_render(logits, size=None, align_corners=False, palette=None, backgro
     return out
 
 
+RENDER_MAX_VIEWS = 8                            # OESS_RENDER_MAX_VIEWS of include/oess.h
+
+
+def ensemble_render(views, flips=None, size=None, align_corners=False, palette=None, background=None, alpha=0.5, min_conf=0.0,
+                    ignore_label=255, want=SEGMENT_RENDER_OUTPUTS):
+    """segment_render's outputs from the MEAN class probability of 1 ... 8 views (flip and multi-scale inference)
+    without any full-resolution [B, K, H, W] tensor.  views: logical B x K x h_v x w_v fp32 / bf16 logits of one dtype, device, B
+    and K, each of its own size; flips: one bool per view (None: none) -- a flipped view is the logits of the MIRRORED input and
+    counts as resize(view).flip(-1).  size=None is view 0's size.  Per view the probabilities are softmax over segment_render's
+    class values, the mean runs over the views in order, the label is argmax of the mean and 'conf' its value; min_conf,
+    ignore_label, palette, background and alpha as segment_render.  One unflipped view IS segment_render.  No autograd."""
+    views = list(views) if isinstance(views, (list, tuple)) else None
+    if not views or len(views) > RENDER_MAX_VIEWS:
+        raise ValueError(f"ensemble_render takes a list of 1 ... {RENDER_MAX_VIEWS} views, got "
+                         f"{'no list' if views is None else len(views)}")
+    flips = [False] * len(views) if flips is None else list(flips)
+    if len(flips) != len(views) or any(f not in (False, True, 0, 1) for f in flips):
+        raise ValueError(f"flips must hold one bool per view ({len(views)}), got {flips!r}")
+    x0 = views[0]
+    for x in views:
+        if not torch.is_tensor(x) or x.dtype not in (torch.float32, torch.bfloat16) or x.ndim != 4:
+            raise ValueError("ensemble_render expects 4-D float32 / bfloat16 logits [B, K, h, w]")
+        if x.dtype != x0.dtype or x.device != x0.device or x.shape[:2] != x0.shape[:2]:
+            raise ValueError("ensemble_render: every view must share view 0's dtype, device, B and K, got "
+                             f"{[(str(v.dtype), str(v.device), tuple(v.shape)) for v in views if torch.is_tensor(v)]}")
+    if not x0.is_cuda:
+        raise ValueError("ensemble_render needs CUDA/HIP tensors (no CPU fallback)")
+    B, K = x0.shape[:2]
+    if not 1 <= K <= 255:
+        raise ValueError(f"ensemble_render handles 1 <= K <= 255 classes, got {K}")
+    if min(min(x.shape) for x in views) < 1:
+        raise ValueError(f"ensemble_render needs non-empty views, got {[tuple(x.shape) for x in views]}")
+    H, W = tuple(x0.shape[2:]) if size is None else (int(size[0]), int(size[1]))
+    if len(views) == 1 and not flips[0]:
+        return segment_render(x0, size=(H, W), align_corners=align_corners, palette=palette, background=background, alpha=alpha,
+                              min_conf=min_conf, ignore_label=ignore_label, want=want)
+    palette, background, alpha256, min_conf, ignore_label, out = _render_args("ensemble_render", x0, B, K, H, W, palette, background,
+                                                                              alpha, min_conf, ignore_label, want)
+    xs = [_nhwc_any(x.detach()) for x in views]
+    V = len(xs)
+    _lib.check(_lib.load().oess_segment_render_ensemble(
+        (ctypes.c_void_p * V)(*[_ptr(x) for x in xs]), (ctypes.c_longlong * V)(*[_pix_stride(x) for x in xs]),
+        (ctypes.c_int * V)(*[x.shape[1] for x in xs]), (ctypes.c_int * V)(*[x.shape[2] for x in xs]),
+        (ctypes.c_int * V)(*[int(bool(f)) for f in flips]), V, int(x0.dtype == torch.bfloat16), B, K, H, W, int(bool(align_corners)),
+        _ptr(palette), _ptr(background), alpha256, min_conf, ignore_label, _ptr(out.get('labels')), _ptr(out.get('conf')),
+        _ptr(out.get('rgb')), _stream()), "oess_segment_render_ensemble")
+    for t in out.values():
+        _bump(t)
+    return out
+
+
 def vocab_render_max_names(C):
     """The largest name count P hip.vocab_render takes at C channels: its weights [P, C] and bias [P] sit in 48 KB of LDS."""
     return int(_lib.load().oess_head_render_max_names(int(C)))

@@ -56,6 +56,25 @@ def check_class_offsets(class_offsets, P):
     return offs
 
 
+def tta_views(flip=False, scales=(1.0,)):
+    """The views of flip / multi-scale inference as [(scale, mirrored)]: scale 1.0 first, then the other scales
+    in the order given, each followed by its mirrored copy when `flip` is set.  Scale 1.0 unflipped is always view 0 (its logits
+    are the plain path's).  Refused: scales that are not finite positive numbers, repeat or lack 1.0, and more than 8 views."""
+    try:
+        scales = [float(v) for v in scales]
+    except (TypeError, ValueError):
+        raise ValueError(f"scales must be a sequence of numbers, got {scales!r}") from None
+    if not scales or any(not (math.isfinite(v) and v > 0.0) for v in scales):
+        raise ValueError(f"scales must be finite and positive, got {scales!r}")
+    if len(set(scales)) != len(scales) or 1.0 not in scales:
+        raise ValueError(f"scales must hold 1.0 (view 0 is the plain prediction) and no scale twice, got {scales!r}")
+    views = [(v, m) for v in [1.0] + [v for v in scales if v != 1.0] for m in ((False, True) if flip else (False,))]
+    if len(views) > hip.RENDER_MAX_VIEWS:
+        raise ValueError(f"flip / multi-scale inference takes at most {hip.RENDER_MAX_VIEWS} views, got {len(views)} "
+                         f"({len(scales)} scales{' x 2 for the flip' if flip else ''})")
+    return views
+
+
 def _train_module():
     """train.py at the repository root (build_trainer, seed_everything)."""
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -104,6 +123,7 @@ class Segmenter:
         self._own = (self.num_classes, self.palette)          # the checkpoint's vocabulary, for reset_vocabulary()
         self._vocab = None                       # the run-time vocabulary (set_vocabulary_embeddings), None: the checkpoint's own
         self._states = None                      # recurrent states of the stateful path
+        self._mirror_states = None               # the same for the mirrored recording of predict_events(flip=True)
         self.render_events = None                # (start, end) HIP events around the last render, for the CLI's timing
         self._rec = self._post = None
         if self.is_event:
@@ -121,6 +141,20 @@ class Segmenter:
         end.record()
         self.render_events = (start, end)
         return out
+
+    def _render_views(self, views, flips, **kw):
+        """hip.ensemble_render of the views' logits between two timing events, with this object's palette and ignore label"""
+        start, end = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        start.record()
+        out = hip.ensemble_render(views, flips=flips, palette=self.palette, ignore_label=self.ignore_label, **kw)
+        end.record()
+        self.render_events = (start, end)
+        return out
+
+    def _refuse_vocabulary_tta(self):
+        if self._vocab is not None:
+            raise ValueError("flip / multi-scale inference under a run-time vocabulary is a follow-up (the ensemble render "
+                             "kernel takes no grouped classes): call reset_vocabulary(), or predict without flip / scales")
 
     # ---------------------------------------------------------------------------------------------------------------- vocabulary
     def _classifier(self):
@@ -222,12 +256,13 @@ class Segmenter:
     # ------------------------------------------------------------------------------------------------------------ event students
     def reset(self):
         """Forget the recording: the next stateful call starts from empty states."""
-        self._states = None
+        self._states = self._mirror_states = None
 
-    def _event_logits(self, event, stateful, want_recon, head_operand=False):
+    def _event_logits(self, event, stateful, want_recon, head_operand=False, mirrored=False):
         """(logits fp32 [B, K, H, W], grey u8 [B, H, W] | None) of fp32 events [B, n * C, H, W]: the sub-windows through the E2VID
         encoder in order (_latents / _latents_fp32 of the trainers, on this object's reconstructor), the decoder on the last.
-        head_operand=True: the decoder_scale_4 map [B, 32, H, W] takes the logits' place (a vocabulary's head follows in the render)."""
+        head_operand=True: the decoder_scale_4 map [B, 32, H, W] takes the logits' place (a vocabulary's head follows in the render).
+        mirrored=True: `event` is the mirrored recording of flip inference; its stateful calls carry a state set of their own."""
         s, rec = self.settings, self._rec
         C = s.input_channels_b
         if (not torch.is_tensor(event) or event.ndim != 4 or event.dtype != torch.float32 or not event.is_cuda
@@ -238,7 +273,8 @@ class Segmenter:
             raise ValueError(f"a stateless prediction takes nr_events_data_b = {s.nr_events_data_b} sub-windows, got {n}")
         if stateful and event.shape[0] != 1:
             raise ValueError("a stateful prediction follows ONE recording: batch size 1")
-        rec.last_states_for_each_channel = {'grayscale': self._states if stateful else None}
+        states = self._mirror_states if mirrored else self._states
+        rec.last_states_for_each_channel = {'grayscale': states if stateful else None}
         img = latent = None
         try:
             for i in range(n):
@@ -253,7 +289,9 @@ class Segmenter:
                 logits = back.head_features(latent, self.precision)
             else:
                 logits = (back.forward_fp32(latent) if self.precision == 'fp32' else back(latent))[0][1].float()
-            if stateful:
+            if stateful and mirrored:
+                self._mirror_states = rec.last_states_for_each_channel['grayscale']
+            elif stateful:
                 self._states = rec.last_states_for_each_channel['grayscale']
         finally:
             rec.last_states_for_each_channel = {'grayscale': None}
@@ -280,35 +318,77 @@ class Segmenter:
         return self._render(logits, class_offsets=v.offsets, **kw)
 
     @torch.no_grad()
-    def predict_events(self, event_tensor, stateful=False, want_recon=False, min_conf=0.0, background=None, alpha=0.5):
+    def predict_events(self, event_tensor, stateful=False, want_recon=False, min_conf=0.0, background=None, alpha=0.5, flip=False,
+                       scales=(1.0,)):
         """Event students.  event_tensor: fp32 [B, nr_events_data_b * C, H, W] as the loader's voxelizer produces it.
         stateful=False runs the sub-windows from empty states (what validation does).  stateful=True treats them as the NEXT
         windows of one recording (B = 1): the states carry over from the previous stateful call until reset(); one prediction per
         call.  want_recon=True adds 'recon': the E2VID image of the last sub-window, u8 [B, H, W], through PostProcessor.process_u8
-        with the reference's defaults.  background: u8 [B, H, W] to blend under the colours, or 'recon' for that image."""
+        with the reference's defaults.  background: u8 [B, H, W] to blend under the colours, or 'recon' for that image.
+        flip=True: the mean class probability of the tensor and of the tensor mirrored along W, on
+        hip.ensemble_render; view 0 is the plain prediction ('recon' and the overlay come from it).  The mirrored recording is
+        another recording: stateful calls carry one state set per view, reset() clears both, and a stateful call WITHOUT flip
+        drops the mirrored one (it missed a window).  scales other than (1.0,) are refused: the reconstructor is built for one size."""
         if not self.is_event:
             raise ValueError(f"predict_events serves the event students {EVENT_OPTIONS}, not {self.config_option!r}")
         over_recon = isinstance(background, str)
         if over_recon and background != 'recon':
             raise ValueError(f"background must be a uint8 tensor, None or 'recon', got {background!r}")
+        views = tta_views(flip, scales)
+        if any(scale != 1.0 for scale, _ in views):
+            raise ValueError("the event students take flip only: scales other than (1.0,) need a reconstructor per size")
+        if len(views) > 1:
+            self._refuse_vocabulary_tta()
+            crop = self._rec.crop
+            if crop.padding_left != crop.padding_right:
+                raise ValueError(f"flip inference needs the reconstructor's left and right padding equal, got {crop.padding_left} "
+                                 f"and {crop.padding_right}: the mirrored tensor would be padded on the other side")
+        elif stateful:
+            self._mirror_states = None
         logits, grey = self._event_logits(event_tensor, bool(stateful), bool(want_recon) or over_recon, self._vocab is not None)
         if grey is not None and tuple(grey.shape[1:]) != tuple(logits.shape[2:]):
             raise ValueError("the reconstruction is cropped to the sensor, the logits are at the padded size: no overlay for sizes "
                              "that are not multiples of 8")
-        render = self._render if self._vocab is None else self._render_vocabulary
-        out = render(logits, background=grey if over_recon else background, alpha=alpha, min_conf=min_conf)
+        kw = dict(background=grey if over_recon else background, alpha=alpha, min_conf=min_conf)
+        if len(views) > 1:
+            mirror, _ = self._event_logits(event_tensor.flip(-1), bool(stateful), False, mirrored=True)
+            out = self._render_views([logits, mirror], [False, True], **kw)
+        else:
+            out = (self._render if self._vocab is None else self._render_vocabulary)(logits, **kw)
         if want_recon:
             out['recon'] = grey
         return out
 
     # ------------------------------------------------------------------------------------------------------------------- batches
     @torch.no_grad()
-    def predict(self, batch, min_conf=0.0, background=None, alpha=0.5):
-        """{'labels', 'conf', 'rgb'} of a prepared batch of the trainer's loader (events, labels, frame | reconstruction, ...)."""
+    def predict(self, batch, min_conf=0.0, background=None, alpha=0.5, flip=False, scales=(1.0,)):
+        """{'labels', 'conf', 'rgb'} of a prepared batch of the trainer's loader (events, labels, frame | reconstruction, ...).
+        flip / scales: the mean class probability over the views of tta_views(flip, scales) on
+        hip.ensemble_render -- the image rescaled to (int(H s + 0.5), int(W s + 0.5)) by hip.bilinear_resize and / or mirrored
+        along W, one network pass per view through the plain path's own calls.  The event students take flip only
+        (predict_events); a linear probe takes flip only (its logits are at the full resolution: raw views)."""
         if self.is_event:
-            return self.predict_events(batch[0], min_conf=min_conf, background=background, alpha=alpha)
+            return self.predict_events(batch[0], min_conf=min_conf, background=background, alpha=alpha, flip=flip, scales=scales)
         model = self.trainer.models_dict['model_recon']
         kw = dict(background=background, alpha=alpha, min_conf=min_conf)
+        views = tta_views(flip, scales)
+        if len(views) > 1:
+            self._refuse_vocabulary_tta()
+            img = batch[2]
+            size = tuple(img.shape[-2:])
+            flips = [m for _, m in views]
+            if model.if_linear_probing:
+                if any(scale != 1.0 for scale, _ in views):
+                    raise ValueError("a linear probe acts on the full-resolution logits of ONE size: scales other than (1.0,) "
+                                     "are refused, flip works")
+                mirrored = tuple(batch[:2]) + (img.flip(-1),) + tuple(batch[3:])
+                return self._render_views([self.trainer.val_logits(mirrored if m else batch, self.precision) for m in flips],
+                                          flips, **kw)
+            lows = []
+            for scale, m in views:
+                x = img if scale == 1.0 else hip.bilinear_resize(img, size=(int(size[0] * scale + 0.5), int(size[1] * scale + 0.5)))
+                lows.append(model.logits_at_stride(x.flip(-1) if m else x, self.precision))
+            return self._render_views(lows, flips, size=size, **kw)
         if model.if_linear_probing:                           # the probe sits behind the resize: full-resolution logits
             return self._render(self.trainer.val_logits(batch, self.precision), **kw)
         if self._vocab is not None:               # (never with a probe: set_vocabulary_embeddings refuses it)

@@ -4,7 +4,7 @@ and, on request, confidence maps, rendered by hip.segment_render from openess_am
 
     python tools/segment.py -o OUT [--settings YAML] [--config-option frame2voxel | recon2voxel | frame2recon]
                             [--checkpoint FILE] [--precision bf16 | fp32] [--min-conf 0] [--alpha 0.5] [--max-frames N]
-                            [--save-confidence] [--png-encoder host | gpu]
+                            [--save-confidence] [--png-encoder host | gpu] [--tta flip] [--tta-scales 0.75,1,1.25]
                             [--split val | -i events.txt [-N EVENTS] [--skipevents N] [--stateful] [--overlay recon]]
                             [--classes "road,car|vehicle,person" | --classes FILE [--merge max | mean] [--templates single]
                             [--clip-text-checkpoint FILE] [--bpe FILE]]
@@ -20,6 +20,11 @@ and, on request, confidence maps, rendered by hip.segment_render from openess_am
 
   --png-encoder gpu      the label and colour PNGs are encoded on the device (hip.png_encode_files) and written
                          as they come; host (default): the maps cross to the host and Pillow encodes them.  The same pixels.
+
+  --tta flip             every prediction is the mean class probability of the input and of its mirror image (DESIGN.md K39,
+                         hip.ensemble_render); with --stateful the mirrored recording carries recurrent states of its own.
+  --tta-scales           frame2recon: the image is also rescaled by these factors (a list holding 1; with --tta flip each scale
+                         twice, at most 8 views).  Labels, mIoU and accuracy are the ensemble's.  Not with --classes.
 
   --classes              an open vocabulary: a comma list, or a file with one class per line; `a|b` gives one
                          class several names.  CLIP's text tower (--clip-text-checkpoint, --bpe; default: the settings' keys)
@@ -66,8 +71,32 @@ def build_parser():
     ap.add_argument("--templates", default=None, help="single (default), none, or a file with one template containing {} per line")
     ap.add_argument("--clip-text-checkpoint", default=None, help="CLIP weights for --classes (default: the settings' clip_text_checkpoint)")
     ap.add_argument("--bpe", default=None, help="BPE merges file for --classes (default: the settings' clip_bpe_path)")
+    ap.add_argument("--tta", default=None, choices=("flip",), help="average the class probabilities with those of the mirrored input")
+    ap.add_argument("--tta-scales", default=None, help="comma list of image scales holding 1, e.g. 0.75,1,1.25 (frame2recon only)")
     ap.add_argument("-o", "--output", required=True)
     return ap
+
+
+def parse_tta(ap, a, s):
+    """--tta / --tta-scales checked without a GPU: (flip, scales) as Segmenter.predict takes them"""
+    from openess_amd.inference import tta_views
+    flip, scales = a.tta == "flip", (1.0,)
+    if a.tta_scales is not None:
+        if a.config_option != "frame2recon":
+            ap.error("--tta-scales needs --config-option frame2recon (the event students' reconstructor is built for one size)")
+        try:
+            scales = tuple(float(v) for v in a.tta_scales.split(","))
+        except ValueError:
+            ap.error(f"--tta-scales: a comma list of numbers, got {a.tta_scales!r}")
+        if bool(getattr(s, "if_linear_probing", False)) and not getattr(s, "if_finetuning", False) and scales != (1.0,):
+            ap.error("--tta-scales: a linear probe acts on the full-resolution logits of one size; --tta flip works")
+    try:
+        views = tta_views(flip, scales)
+    except ValueError as e:
+        ap.error(f"--tta-scales: {e}")
+    if len(views) > 1 and a.classes is not None:
+        ap.error("--tta / --tta-scales with --classes: the ensemble render takes no grouped classes yet (a follow-up)")
+    return flip, scales, len(views)
 
 
 def parse_vocabulary(ap, a, s):
@@ -131,6 +160,7 @@ def check_args(ap, a):
         width, height = int(head[0]), int(head[1])
         if [height, width] != [int(v) for v in s.img_size_b]:
             ap.error(f"{a.input_file}: sensor size {height} x {width} is not the settings' shape {list(s.img_size_b)}")
+    a.tta_flip, a.tta_scale_list, a.tta_views = parse_tta(ap, a, s)
     a.vocabulary = parse_vocabulary(ap, a, s)
     return s
 
@@ -181,6 +211,11 @@ def _timed(seg, fn):
     return out, [e0.elapsed_time(e1) - render, render]
 
 
+def _tta(a):
+    """the Segmenter's flip / scales keywords; none at all without --tta / --tta-scales: the plain call as it always was"""
+    return dict(flip=a.tta_flip, scales=a.tta_scale_list) if a.tta_views > 1 else {}
+
+
 def run_val(seg, a, writer):
     import torch
     from openess_amd.evaluation.metrics import MetricsSemseg
@@ -195,7 +230,8 @@ def run_val(seg, a, writer):
         batch = tr.prepare_batch(sample, 'val')[:-4]
         stems = [os.path.splitext(os.path.basename(str(p)))[0] for p in sample[-1]]
         want_overlay = a.overlay == "recon"
-        out, dt = _timed(seg, lambda: seg.predict(batch, min_conf=a.min_conf, background='recon' if want_overlay else None, alpha=a.alpha))
+        out, dt = _timed(seg, lambda: seg.predict(batch, min_conf=a.min_conf, background='recon' if want_overlay else None, alpha=a.alpha,
+                                                  **_tta(a)))
         ms = [ms[0] + dt[0], ms[1] + dt[1]]
         keep = len(stems) if a.max_frames is None else min(len(stems), a.max_frames - writer.frames)
         if met is not None and torch.is_tensor(batch[1]):
@@ -240,7 +276,7 @@ def run_events(seg, a, writer):
         if a.max_frames is not None and k >= a.max_frames:
             break
         out, dt = _timed(seg, lambda: seg.predict_events(ev, stateful=a.stateful, min_conf=a.min_conf, alpha=a.alpha,
-                                                    background='recon' if a.overlay == "recon" else None))
+                                                    background='recon' if a.overlay == "recon" else None, **_tta(a)))
         ms = [ms[0] + dt[0], ms[1] + dt[1]]
         writer.write(['frame_{:010d}'.format(k)], out)
         k += 1
@@ -266,6 +302,7 @@ def main(argv=None):
            "ms_per_frame": {"network": round(res["network_render_ms"][0] / n, 3), "render": round(res.pop("network_render_ms")[1] / n, 3), "write": round(1e3 * writer.seconds / n, 3)},
            "output": a.output, "checkpoint": a.checkpoint, "classes": seg.num_classes,
            "vocabulary": None if a.vocabulary is None else {"merge": a.vocabulary["merge"], "templates": a.vocabulary["templates"]}, "device": torch.cuda.get_device_name(0)}
+    out["tta"] = {"flip": a.tta_flip, "scales": list(a.tta_scale_list), "views": a.tta_views}
     if a.png_encoder == "gpu":
         out["png_encoder"] = "gpu"
     out.update(res)
